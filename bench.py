@@ -6,10 +6,13 @@ Metric (BASELINE.json): field-evals/s of the sumcheck prover over a 24-variable 
 table: Sumcheck::poly_sum + Sumcheck::prove (sumcheck/benches/sumcheck_benchmark.rs:13-22 minus
 the verifier) -- block sums, k-variable folds and the Fiat-Shamir transcript on the device --
 with the table already resident in HBM.  value = (tables' entries consumed by all ranks) / time.
-Timing: after `warmup` steps, batches of EXACTLY `steps` steps, each between barrier + synchronize (MAX over ranks per batch), until
->= 0.3 s are measured; the line reports the median batch and min / median / max under `batches`.
+Timing: after `warmup` steps, ONE batch of EXACTLY `steps` steps between barrier + synchronize (MAX over ranks); value and
+ms_per_step are that batch.  --dump-outputs DIR writes the last timed step's proof as DIR/<name>.npy (float64, 32-bit limb halves).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (the streaming k-variable fold, limb products on the matrix cores)
+A plain run stops there.  With --full, more batches of `steps` steps follow until >= 0.3 s are measured (min / median / max under
+`batches`), and the extra objects below.  The --no-* options pick among them.
+
+Extra objects on the JSON line (--full): `roofline` for the dominant kernel (the streaming k-variable fold, limb products on the matrix cores)
 from HIP events on its launch stream, and `cpu_baseline`: the CPU oracle (a C port of the reference
 algorithm, single-threaded like the reference) timed on rank 0 at N=1 (plus the same port on all host cores at once).
 Informational objects that never enter `value`: `pipelined` (the same proofs with up to eight in flight), `fold` (the single-variable
@@ -119,21 +122,26 @@ def _timed(fn, torch, reps=5, min_total=MIN_LEG_SECONDS, max_batches=40):
     return out
 
 
+def _one_batch(step, steps, barrier, dist, world, torch):
+    """ONE batch of EXACTLY `steps` steps bracketed by barrier + synchronize, MAX over ranks.  -> (seconds, last step's result)"""
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        r = step()
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    return dt, r
+
+
 def _batches(step, steps, barrier, dist, world, torch, min_total=MIN_LEG_SECONDS, max_batches=60):
     """Batches of EXACTLY `steps` steps, each bracketed by barrier + synchronize, MAX over ranks per batch; as many batches as it takes
     to measure min_total seconds (the same count on every rank: decided on rank 0's clock).  -> (seconds per batch, last result)"""
     def one():
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            r = step()
-        barrier()
-        dt = time.perf_counter() - t0
-        if world > 1:
-            tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = float(tt.item())
-        return dt, r
+        return _one_batch(step, steps, barrier, dist, world, torch)
     dt, res = one()
     n_more = max(2, min(max_batches - 1, int(min_total / max(dt, 1e-9))))
     if world > 1:
@@ -243,6 +251,21 @@ def _profile(N, ctx, name):
 def _synthetic(zk, torch, n, seed):
     import numpy as np
     return torch.from_numpy(zk.Fr.synthetic(n, seed).view(np.int64)).cuda()
+
+
+def _dump_outputs(path, res, np):
+    """--dump-outputs: what the last timed step handed its caller -- the proof's sum, its round polynomials and the Fiat-Shamir
+    challenges -- as float64 .npy files.  Every Montgomery limb is split into its two 32-bit halves (exact in float64), so an array of
+    n field elements is [n, 8], lowest half first, and two builds compare bit for bit."""
+    if hasattr(res[0], "univariate_poly"):
+        s, rp, ch = res[0].sum, res[0].univariate_poly, res[1]   # Sumcheck::prove: (SumcheckProof, challenges)
+    else:
+        s, rp, ch = res                                          # the sharded prover: (sum, round polynomials, challenges)
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("sum", s), ("univariate_poly", rp), ("challenges", ch)):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        halves = a.view(np.uint32).reshape(a.shape[:-1] + (2 * a.shape[-1],))
+        np.save(os.path.join(path, name + ".npy"), halves.astype(np.float64))
 
 
 def _same_on_all_ranks(dist, torch, np, arr):
@@ -893,8 +916,20 @@ def main():
     ap.add_argument("--no-pipelined", action="store_true", help="skip the proofs-in-flight leg (profiling: keeps the kernel averages those of the synchronous steps)")
     ap.add_argument("--config4-log-n", type=int, default=23, help="N > 1: log2 of the per-GPU points of the configs[4]-shaped commit (2^26 over 8 = 2^23)")
     ap.add_argument("--no-exchange", action="store_true", help="skip the exchange-cost measurement and the N = 8 prediction")
-    ap.add_argument("--selftest", action="store_true", help="run the sharded provers' self-test (always on at N > 1) on one GPU too")
+    ap.add_argument("--selftest", action="store_true", help="run the sharded provers' self-test (on at N > 1 with --full) on one GPU too")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the batch spread, roofline, proofs in flight, the other "
+                    "legs, CPU baselines, the N > 1 self-test and checks (the --no-* options pick among them); off: warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's proof (sum, round polynomials, challenges) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # the legs' options select among what --full measures: a plain run would ignore them (and print none of those objects)
+        legs = ("no_cpu_baseline", "msm_log_n", "no_msm", "composed_log_n", "no_composed", "no_gkr", "ntt_log_n", "no_ntt", "no_fold",
+                "no_h2d", "no_gkr_threads", "no_pipelined", "config4_log_n", "no_exchange")
+        given = [d for d in legs if getattr(args, d) != ap.get_default(d) and not (d == "no_exchange" and args.selftest)]
+        if given:
+            ap.error("%s select(s) what --full measures: add --full" % ", ".join("--" + d.replace("_", "-") for d in given))
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and env_world is None:
@@ -939,7 +974,7 @@ def main():
     # group once), a host-staged callback in the one-GPU dry run, none on one rank
     comm = D.Comm.get(N.Context.get(), world, rank, dist if world > 1 else None)
     exchange = None
-    if world > 1 or args.selftest:
+    if (world > 1 and args.full) or args.selftest:
         # ---- self-test before anything is timed: the measured exchange first, then one small proof of every sharded prover against
         # rank 0 and against the single-GPU prover; a mismatch ends the job (non-zero status on every rank)
         if world > 1 and not args.no_exchange:
@@ -972,11 +1007,48 @@ def main():
     res = None
     for _ in range(args.warmup):
         res = step()
-    # batches of exactly `steps` steps, each between barrier + synchronize, until >= 0.3 s are measured; the line reports the MEDIAN batch
-    # (a 20-step batch is 7 ms: box-to-box and run-to-run spread is larger than most single changes) and min / max beside it
-    batch_s, res = _batches(step, args.steps, barrier, dist, world, torch)
-    dt = sorted(batch_s)[len(batch_s) // 2]
-    step_stats = _stats([b / args.steps for b in batch_s], 1e3)
+    # the headline: ONE batch of exactly `steps` steps between barrier + synchronize (MAX over ranks)
+    dt, res = _one_batch(step, args.steps, barrier, dist, world, torch)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, res, np)
+    head = {
+        "metric": "field-evals/s (sumcheck 2^%d) + MSM points/s (KZG 2^%d) per BASELINE.json; value = the sumcheck prover's "
+                  "field-evals/s, the MSM half is under \"msm\"" % (args.log_n, args.msm_log_n),
+        "value": round(float(n) * world * args.steps / dt, 1),
+        "unit": "field-evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * (dt / args.steps), 4),       # the same rounding as the spread under `batches` (--full)
+    }
+    config = {"field": "BLS12-381 Fr (255-bit Montgomery, 8 x u32 limbs); G1 over Fq (381-bit)",
+              "workload": "24-var multilinear sumcheck prover (poly_sum + prove), BLS12-381 Fr" if args.log_n == 24
+              else "%d-var multilinear sumcheck prover" % args.log_n,
+              "evals_per_gpu": n,
+              "inputs": "uniform field elements, splitmix64-seeded xoshiro256** (SURVEY 8d), table seed 0x5EED000000000001 + 16 rank",
+              "exchanges_per_prove": exchanges[0] if world > 1 else 0,
+              "sharding": ("one %d-entry table sharded by low index bits over %d GPUs; overlapped stage: RCCL all-gathers of the coarse block sums, of the folded fine sums (beside the shard's local fold) and of the 256-entry local tables; replicated transcript" % (n * world, world))
+              if world > 1 else "single GPU"}
+    tail = {
+        "higher_is_better": True,
+        "scaling": "weak",
+        **({"dry_run": "ZKHIP_BENCH_ONE_GPU: all ranks on one GPU, exchange over gloo -- not a measurement"} if one_gpu else {}),
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+    }
+    if not args.full:
+        # a plain run: warm-up, the timed steps, the outputs, the line -- nothing else
+        if rank == 0:
+            print(json.dumps({**head, **tail, "config": config}))
+        D.Comm.close_all()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # --full: more batches of exactly `steps` steps, each between barrier + synchronize, until >= 0.3 s are measured, for the spread
+    # (a 20-step batch is 7 ms: box-to-box and run-to-run spread is larger than most single changes); the headline batch is among them
+    batch_s, _ = _batches(step, args.steps, barrier, dist, world, torch)
+    step_stats = _stats([b / args.steps for b in [dt] + batch_s], 1e3)
     # ---- roofline of the dominant kernel: HIP events around every fold launch on the launch stream
     # (BEFORE the proofs-in-flight leg: once its lanes exist -- four more low-priority fold streams beside the synchronous prover's on four hardware queues --
     # the events around the big fold span ~7 us more than the kernel runs (91.5 against 84.9 us; rocprofv3's kernel trace: 80.4 us either way).  The
@@ -1186,8 +1258,7 @@ def main():
     if world > 1:
         barrier()                        # the ranks that ran no CPU baseline wait here for rank 0
     if rank == 0:
-        total_evals = float(n) * world * args.steps
-        if world > 1:                    # which transport the sharded provers ran on, and why if it is not the library's RCCL communicator
+        if world > 1:                   # which transport the sharded provers ran on, and why if it is not the library's RCCL communicator
             import ctypes as C
             ver = C.c_int(0)
             ok = N.lib().zkhip_rccl_version(C.byref(ver)) == 0
@@ -1202,7 +1273,7 @@ def main():
                 d = d[k]
             return d
         # every leg's headline figure, flat and FIRST in the line (a record that keeps only the head or the tail of the line keeps these)
-        legs = {"step_ms": round(1e3 * dt / args.steps, 4), "step_hbm_frac": roofline.get("step_hbm_frac"),
+        legs = {"step_ms": head["ms_per_step"], "step_hbm_frac": roofline.get("step_hbm_frac"),
                 "pipelined_ms": g(pipelined, "ms_per_step"),
                 "fine_sums_us": g(per_kernel, "fine_sums", "avg_launch_us"), "fine_sums_frac": g(per_kernel, "fine_sums", "frac"),
                 "kfold_us": g(per_kernel, "multifold", "avg_launch_us"), "kfold_frac": g(per_kernel, "multifold", "frac"),
@@ -1234,31 +1305,12 @@ def main():
             composed["other_shapes"] = composed_shapes
         out = {
             "legs": legs,
-            "metric": "field-evals/s (sumcheck 2^%d) + MSM points/s (KZG 2^%d) per BASELINE.json; value = the sumcheck prover's "
-                      "field-evals/s, the MSM half is under \"msm\"" % (args.log_n, args.msm_log_n),
-            "value": round(total_evals / dt, 1),
-            "unit": "field-evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "batches": {**step_stats, "unit": "ms per step", "note": "batches of exactly `steps` steps between barrier + synchronize; value / ms_per_step = the median batch"},
+            **head,
+            "batches": {**step_stats, "unit": "ms per step", "note": "batches of exactly `steps` steps between barrier + synchronize; value / ms_per_step = "
+                                                                      "the first batch after the warm-up (the one a plain run times), the rest give the spread"},
             "pipelined": pipelined,
-            "higher_is_better": True,
-            "scaling": "weak",
-            **({"dry_run": "ZKHIP_BENCH_ONE_GPU: all ranks on one GPU, exchange over gloo -- not a measurement"} if one_gpu else {}),
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic",
-            "config": {"field": "BLS12-381 Fr (255-bit Montgomery, 8 x u32 limbs); G1 over Fq (381-bit)",
-                       "workload": "24-var multilinear sumcheck prover (poly_sum + prove), BLS12-381 Fr" if args.log_n == 24
-                       else "%d-var multilinear sumcheck prover" % args.log_n,
-                       "evals_per_gpu": n,
-                       "inputs": "uniform field elements, splitmix64-seeded xoshiro256** (SURVEY 8d), table seed 0x5EED000000000001 + 16 rank",
-                       "exchanges_per_prove": exchanges[0] if world > 1 else 0,
-                       "transcript_replicated_on_all_ranks": transcript_same,
-                       "sharding": ("one %d-entry table sharded by low index bits over %d GPUs; overlapped stage: RCCL all-gathers of the coarse block sums, of the folded fine sums (beside the shard's local fold) and of the 256-entry local tables; replicated transcript" % (n * world, world))
-                       if world > 1 else "single GPU"},
+            **tail,
+            "config": {**config, "transcript_replicated_on_all_ranks": transcript_same},
             "roofline": roofline,
             "cpu_baseline": cpu,
             "fold": fold,

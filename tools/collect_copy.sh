@@ -1,9 +1,9 @@
 #!/bin/bash
-# usage (this container, repo root, after `gpurun -- tools/collect.sh <round>` merged gpurun_out/<round>/): tools/collect_copy.sh <round>
+# usage (repo root, once tools/collect.sh <round> has written $COLLECT_OUT/<round>/, default collect_out/): tools/collect_copy.sh <round>
 # copies what is judged into profiles/<round>/
 set -e
 N=${1:?round name, e.g. r04}
-R=gpurun_out/$N P=profiles/$N
+R=${COLLECT_OUT:-collect_out}/$N P=profiles/$N
 mkdir -p $P
 cp $R/stats/runc/*kernel_stats.csv $P/a_bench_kernel_stats.csv
 cp $R/bench_under_rocprof.json $P/a_bench_line_under_rocprof.json

@@ -31,7 +31,7 @@ def per_kernel(path, counter):
 def main():
     fetch, nf = per_kernel(sys.argv[1], "FETCH_SIZE")
     write, _ = per_kernel(sys.argv[2], "WRITE_SIZE")
-    out = {"_about": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python3 bench.py --steps 3 --warmup 1 "
+    out = {"_about": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python3 bench.py --full --steps 3 --warmup 1 "
                      "--no-cpu-baseline --no-msm --no-composed --no-gkr --no-ntt --no-h2d --no-exchange` on MI355X; FETCH_SIZE doubled per the gfx950 correction; units of the "
                      "counters: KB; hbm_bytes_per_launch = 2 * FETCH + WRITE",
            "kernel_sources_sha16": kernel_sources_fingerprint(), "kernel_sources": list(STREAMING_KERNEL_SOURCES), "kernels": {}}
