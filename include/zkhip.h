@@ -549,7 +549,7 @@ int zkhip_kzg_commit_batch(zkhip_ctx *ctx, const uint64_t *d_points_xy, const ui
  * Returns ZKHIP_ERR_SHAPE when no window widths fit the sort's partitions (more than 64 problems' worth). */
 int zkhip_msm_geometry_info(const size_t *h_offsets, uint32_t n_problems, uint16_t *h_win_first, uint8_t *h_win_bits,
                             uint32_t *h_totals);
-/* SRS generation on the device (G1 side; the G2 powers are only used by the pairing verifier, out of scope).
+/* SRS generation on the device, G1 side (the G2 side: zkhip_srs_multilinear_g2 / zkhip_srs_univariate_g2 below).
  *   multilinear: TrustedSetup::generate_powers_of_tau_in_g1 (kzg/src/trusted_setup.rs:25-35):
  *                point i = G * prod_j (bit_j(i) ? tau_j : 1 - tau_j), hypercube bits MSB first; 2^n_vars points.
  *   univariate:  UnivariateKZG::generate_srs (kzg/src/univariate_kzg.rs:18-35): point i = G * tau^i, i = 0..=max_degree.
@@ -605,6 +605,49 @@ int zkhip_dense_degree(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs
 /* Sum of n affine points given on the host (combining per-GPU partial commitments after an all-gather). */
 int zkhip_g1_sum_affine(const uint64_t *h_points_xy, const uint8_t *h_points_inf, size_t n, uint64_t *h_out_xy,
                         uint8_t *h_out_inf);
+
+/* ---- KZG verification: G2, the BLS12-381 pairing (kzg/src/{trusted_setup,multilinear_kzg,univariate_kzg,utils}.rs) ---- */
+/* G2 affine   = uint64_t[24] (x.c0, x.c1, y.c0, y.c1; 6 Montgomery limbs each, R = 2^384) + a uint8_t infinity flag per point
+ *               in a separate array.  Points are on the M-type twist y^2 = x^3 + 4 (u + 1); the generator is arkworks'.
+ * GT          = uint64_t[72]: 12 Fq coefficients in arkworks order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 (Montgomery),
+ *               the value f^((p^12 - 1) / r) exactly, so equal pairings have equal limbs.
+ * G2 SRS (device outputs, d_out_xy[n*24], d_out_inf[n]):
+ *   multilinear: TrustedSetup::generate_powers_of_tau_in_g2 (trusted_setup.rs:37-45): point i = tau_i G2, n = n_vars;
+ *   univariate:  UnivariateKZG::generate_srs (univariate_kzg.rs:18-35): point i = tau^i G2, i = 0..=max_degree. */
+int zkhip_srs_multilinear_g2(zkhip_ctx *ctx, const uint64_t *h_tau, uint32_t n_vars, uint64_t *d_out_xy, uint8_t *d_out_inf);
+int zkhip_srs_univariate_g2(zkhip_ctx *ctx, const uint64_t *h_tau, size_t max_degree, uint64_t *d_out_xy, uint8_t *d_out_inf);
+/* Prepared second arguments: the 68 Miller-loop line coefficients of each G2 point, zkhip_g2_prepared_bytes(n) bytes for n points.
+ *   zkhip_g2_prepare : entry i = point i (for zkhip_pairing_prepared);
+ *   zkhip_kzg_prepare: entry 0 = the generator G2, entry i = point i - 1 (n + 1 entries; what the verifiers below take).
+ * Both check every finite point: off the twist or outside the prime-order subgroup -> ZKHIP_ERR_ARG.  Synchronous. */
+size_t zkhip_g2_prepared_bytes(size_t n);
+int zkhip_g2_prepare(zkhip_ctx *ctx, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, void *d_prepared);
+int zkhip_kzg_prepare(zkhip_ctx *ctx, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, void *d_prepared);
+/* n independent pairings e(P_k, Q_k) -> d_out_gt[72 k] (device).  A point at infinity on either side gives 1; a finite input off its
+ * curve or outside the subgroup -> ZKHIP_ERR_ARG.  _prepared takes Q_k as zkhip_g2_prepare's entry k.  Synchronous. */
+int zkhip_pairing(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy,
+                  const uint8_t *d_g2_inf, size_t n, uint64_t *d_out_gt);
+int zkhip_pairing_prepared(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const void *d_prepared, size_t n,
+                           uint64_t *d_out_gt);
+/* MultilinearKZGInterface::verify (multilinear_kzg.rs:90-112) for `batch` independent openings of n_vars variables:
+ *   h_commits_xy[12 b], h_commits_inf[b], h_evals[4 b] (Fr), h_points[4 (b n_vars + i)] (Fr), h_proofs_xy[12 (b n_vars + i)],
+ *   h_proofs_inf[b n_vars + i]; the SRS's G2 half d_g2_xy / d_g2_inf (n_g2 points), or its zkhip_kzg_prepare lines (d_prepared,
+ *   nullable: NULL prepares them inside the call).  h_ok[b] = 1 when opening b verifies.
+ * The reference's check e(C - v G1, G2) == prod e(pi_i, tau_i G2 - z_i G2) is computed as the equivalent
+ *   e(C - v G1 + sum z_i pi_i, G2) * prod e(-pi_i, tau_i G2) == 1:
+ * n + 1 Miller loops per opening, one lane each, a product tree and one final exponentiation per opening.
+ * n_g2 != n_vars -> ZKHIP_ERR_SHAPE (utils.rs:49-50); a commitment or proof off the curve or outside the subgroup -> ZKHIP_ERR_ARG. */
+int zkhip_kzg_verify_batch(zkhip_ctx *ctx, size_t batch, uint32_t n_vars, const uint64_t *h_commits_xy,
+                           const uint8_t *h_commits_inf, const uint64_t *h_evals, const uint64_t *h_points,
+                           const uint64_t *h_proofs_xy, const uint8_t *h_proofs_inf, const uint64_t *d_g2_xy,
+                           const uint8_t *d_g2_inf, size_t n_g2, const void *d_prepared, uint8_t *h_ok);
+/* UnivariateKZGInterface::verify (univariate_kzg.rs:83-104), the same shape with one point and one proof per opening:
+ * e(C - v G1 + z pi, G2) * e(-pi, tau G2) == 1, tau G2 = powers_of_tau_in_g2[1]; d_prepared = zkhip_kzg_prepare of that one point.
+ * n_g2 < 2 -> ZKHIP_ERR_INDEX (the reference indexes [1]). */
+int zkhip_univariate_kzg_verify_batch(zkhip_ctx *ctx, size_t batch, const uint64_t *h_commits_xy, const uint8_t *h_commits_inf,
+                                      const uint64_t *h_evals, const uint64_t *h_points, const uint64_t *h_proofs_xy,
+                                      const uint8_t *h_proofs_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf,
+                                      size_t n_g2, const void *d_prepared, uint8_t *h_ok);
 
 /* ---- NTT / Domain / polynomial product (polynomial/src/univariate/) ------------------------- */
 /* Domain::new (domain.rs:31-48) for a power-of-two size: generator = F::get_root_of_unity(size), its inverse,

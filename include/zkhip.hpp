@@ -423,12 +423,42 @@ struct DenseUnivariatePolynomial {                                              
     size_t n;
     std::shared_ptr<DeviceBuffer> dev;
 };
-class TrustedSetup {                                                                           // trusted_setup.rs:9-13 (G1 side)
+class TrustedSetup {                                                                           // trusted_setup.rs:9-13
   public:
-    static TrustedSetup setup(const std::vector<Fr>& eval_points) {                            // :15-35
+    // g2 = true: also generate_powers_of_tau_in_g2 (:37-45), what `verify` needs; the default does the G1 half only
+    static TrustedSetup setup(const std::vector<Fr>& eval_points, bool g2 = false) {          // :15-35
         TrustedSetup s((size_t)1 << eval_points.size());
         check(zkhip_srs_multilinear_g1(ctx(), eval_points.empty() ? nullptr : eval_points[0].l, (uint32_t)eval_points.size(), s.pts_->u64(), s.inf_->u8()), "setup");
+        if (g2) {
+            s.alloc_g2(eval_points.size());
+            check(zkhip_srs_multilinear_g2(ctx(), eval_points.empty() ? nullptr : eval_points[0].l, (uint32_t)eval_points.size(), s.g2_xy_->u64(), s.g2_inf_->u8()),
+                  "setup_g2");
+        }
         return s;
+    }
+    // the G2 half (powers_of_tau_in_g2): n_g2() points, affine, on the device; none unless built with g2 = true
+    size_t n_g2() const { return n_g2_; }
+    const uint64_t* g2_points() const { return g2_xy_ ? g2_xy_->u64() : nullptr; }
+    const uint8_t* g2_inf() const { return g2_inf_ ? g2_inf_->u8() : nullptr; }
+    void alloc_g2(size_t n) {
+        n_g2_ = n;
+        g2_xy_ = std::make_shared<DeviceBuffer>(192 * (n ? n : 1));
+        g2_inf_ = std::make_shared<DeviceBuffer>(n ? n : 1);
+    }
+    // the Miller-loop lines of [G2, G2 half] (univariate: [G2, tau G2]) every verify against this SRS uses (zkhip_kzg_prepare): built once
+    const void* prepared(bool univariate) {
+        auto& buf = univariate ? prep_uni_ : prep_ml_;
+        if (!buf) {
+            if (!g2_xy_) throw std::invalid_argument("this TrustedSetup has no G2 half: build it with g2 = true");
+            if (univariate && n_g2_ < 2) throw std::out_of_range("index out of bounds: powers_of_tau_in_g2[1]");
+            const size_t n = univariate ? 1 : n_g2_;
+            auto b = std::make_shared<DeviceBuffer>(zkhip_g2_prepared_bytes(n + 1));
+            int st = zkhip_kzg_prepare(ctx(), g2_xy_->u64() + (univariate ? 24 : 0), g2_inf_->u8() + (univariate ? 1 : 0), n, b->u8());
+            if (st == ZKHIP_ERR_ARG) throw std::invalid_argument("kzg_prepare: a G2 point is off the twist or outside the subgroup");
+            check(st, "kzg_prepare");
+            buf = b;
+        }
+        return buf->u8();
     }
     size_t len() const { return n_; }
     // shifted-SRS table (zkhip_srs_precompute): built once per SRS, then every commitment uses it
@@ -457,10 +487,17 @@ class TrustedSetup {                                                            
     const uint64_t* points() const { return pts_->u64(); }
     const uint8_t* inf() const { return inf_->u8(); }
     explicit TrustedSetup(size_t n) : pts_(std::make_shared<DeviceBuffer>(96 * n)), inf_(std::make_shared<DeviceBuffer>(n)), n_(n) {}
-    std::shared_ptr<DeviceBuffer> pts_, inf_, table_, folded_xy_, folded_inf_, level_tables_;
+    std::shared_ptr<DeviceBuffer> pts_, inf_, table_, folded_xy_, folded_inf_, level_tables_, g2_xy_, g2_inf_, prep_ml_, prep_uni_;
   private:
-    size_t n_;
+    size_t n_, n_g2_ = 0;
 };
+// the verifiers' status -> the reference's panics / a refused point
+inline void check_verify(int st, const char* what) {
+    if (st == ZKHIP_ERR_SHAPE) throw Panic("Length mismatch");
+    if (st == ZKHIP_ERR_INDEX) throw std::out_of_range("index out of bounds: powers_of_tau_in_g2[1]");
+    if (st == ZKHIP_ERR_ARG) throw std::invalid_argument(std::string(what) + ": a point is off its curve or outside the prime-order subgroup");
+    check(st, what);
+}
 inline G1Affine commit_impl(const TrustedSetup& srs, const uint64_t* d_scalars, size_t n, int require_equal) {
     G1Affine g; uint8_t inf = 0;
     int st = srs.table() ? zkhip_kzg_commit_table(ctx(), srs.table(), srs.inf(), srs.len(), d_scalars, n, require_equal, g.xy, &inf)
@@ -506,6 +543,21 @@ struct MultilinearKZG {
         }
         return pr;
     }
+    // MultilinearKZGInterface::verify (multilinear_kzg.rs:90-112)
+    static bool verify(const G1Affine& commit, const std::vector<Fr>& verifier_points, const MultilinearKZGProof& proof, TrustedSetup& srs) {
+        const size_t nv = verifier_points.size();
+        if (!srs.g2_points()) throw std::invalid_argument("this TrustedSetup has no G2 half: build it with g2 = true");
+        if (proof.proofs.size() != nv || srs.n_g2() != nv) throw Panic("Length mismatch");          // utils.rs:49-50
+        const void* prep = srs.prepared(false);
+        std::vector<uint64_t> pxy(12 * (nv ? nv : 1));
+        std::vector<uint8_t> pinf(nv ? nv : 1);
+        for (size_t i = 0; i < nv; ++i) { std::memcpy(&pxy[12 * i], proof.proofs[i].xy, 96); pinf[i] = proof.proofs[i].infinity; }
+        uint8_t cinf = commit.infinity, ok = 0;
+        check_verify(zkhip_kzg_verify_batch(ctx(), 1, (uint32_t)nv, commit.xy, &cinf, proof.evaluation.l, nv ? verifier_points[0].l : nullptr, pxy.data(),
+                                            pinf.data(), srs.g2_points(), srs.g2_inf(), srs.n_g2(), prep, &ok),
+                     "multilinear verify");
+        return ok != 0;
+    }
 };
 struct UnivariateKZGProof {                                                                    // univariate_kzg.rs:11-15
     Fr evaluation;
@@ -522,10 +574,23 @@ struct UnivariateKZG {
         pr.proof.infinity = inf != 0;
         return pr;
     }
-    static TrustedSetup generate_srs(const Fr& tau, size_t max_degree) {                       // univariate_kzg.rs:18-35
+    static TrustedSetup generate_srs(const Fr& tau, size_t max_degree, bool g2 = false) {      // univariate_kzg.rs:18-35
         TrustedSetup s(max_degree + 1);
         check(zkhip_srs_univariate_g1(ctx(), tau.l, max_degree, s.pts_->u64(), s.inf_->u8()), "generate_srs");
+        if (g2) {
+            s.alloc_g2(max_degree + 1);
+            check(zkhip_srs_univariate_g2(ctx(), tau.l, max_degree, s.g2_xy_->u64(), s.g2_inf_->u8()), "generate_srs_g2");
+        }
         return s;
+    }
+    // UnivariateKZGInterface::verify (univariate_kzg.rs:83-104)
+    static bool verify(const G1Affine& commit, const Fr& verifier_point, const UnivariateKZGProof& proof, TrustedSetup& srs) {
+        const void* prep = srs.prepared(true);
+        uint8_t cinf = commit.infinity, pinf = proof.proof.infinity, ok = 0;
+        check_verify(zkhip_univariate_kzg_verify_batch(ctx(), 1, commit.xy, &cinf, proof.evaluation.l, verifier_point.l, proof.proof.xy, &pinf,
+                                                       srs.g2_points(), srs.g2_inf(), srs.n_g2(), prep, &ok),
+                     "univariate verify");
+        return ok != 0;
     }
     static G1Affine commitment(const DenseUnivariatePolynomial& poly, const TrustedSetup& srs) { return commit_impl(srs, poly.dev->u64(), poly.n, 0); }   // :37-58
 };

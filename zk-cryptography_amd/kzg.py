@@ -1,9 +1,11 @@
-"""kzg::{TrustedSetup, MultilinearKZG, UnivariateKZG} -- the commit path on the GPU.
+"""kzg::{TrustedSetup, MultilinearKZG, UnivariateKZG} on the GPU: commit, open and verify.
 
-Mirrors kzg/src/interface.rs:10-55 for `commitment` (a Pippenger multi-scalar multiplication over
-BLS12-381 G1), `open` (one commitment per variable against the folded SRS) and the G1 half of the trusted
-setup.  The pairing `verify` is out of scope.  A commitment is returned as affine coordinates (x, y Montgomery limbs + infinity flag):
-the reference's Jacobian representation is algorithm dependent, equality is defined on the affine point.
+Mirrors kzg/src/interface.rs:10-55: `commitment` (a Pippenger multi-scalar multiplication over BLS12-381 G1), `open` (one
+commitment per variable against the folded SRS), `verify` (the BLS12-381 optimal ate pairing: one Miller loop per pairing and
+lane over prepared G2 lines, a product tree and one final exponentiation per opening; `verify_batch` checks many openings in one
+pass) and both halves of the trusted setup (the G2 half on request: `setup(..., g2=True)`).  Points are returned as affine
+coordinates (Montgomery limbs + infinity flag): the reference's projective representation is algorithm dependent, equality is
+defined on the affine point.
 """
 import ctypes as C
 
@@ -28,6 +30,93 @@ class G1Affine:
         x = sum(int(self.xy[k]) << (64 * k) for k in range(6)) * rinv % q
         y = sum(int(self.xy[6 + k]) << (64 * k) for k in range(6)) * rinv % q
         return x, y
+
+
+class G2Affine:
+    """A point of the twist y^2 = x^3 + 4 (u + 1): x.c0, x.c1, y.c0, y.c1 as Montgomery limbs (uint64 [24]) + infinity flag."""
+
+    def __init__(self, xy, inf):
+        self.xy = np.ascontiguousarray(xy, dtype=np.uint64).reshape(24)
+        self.infinity = bool(inf)
+
+    def __eq__(self, o):
+        return isinstance(o, G2Affine) and self.infinity == o.infinity and (self.infinity or np.array_equal(self.xy, o.xy))
+
+    def coords(self):
+        """((x.c0, x.c1), (y.c0, y.c1)) as canonical python ints"""
+        v = [_fq_int(self.xy[6 * k: 6 * k + 6]) for k in range(4)]
+        return (v[0], v[1]), (v[2], v[3])
+
+
+_Q = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+
+
+def _fq_int(limbs):
+    """6 Montgomery limbs -> canonical int"""
+    return sum(int(limbs[k]) << (64 * k) for k in range(6)) * pow(pow(2, 384, _Q), -1, _Q) % _Q
+
+
+def gt_ints(gt):
+    """one GT value (uint64 [72], as pairing() returns) -> its 12 Fq coefficients as canonical ints, arkworks order"""
+    gt = np.asarray(gt, dtype=np.uint64).reshape(72)
+    return [_fq_int(gt[6 * k: 6 * k + 6]) for k in range(12)]
+
+
+def _g1_arrays(points):
+    xy = np.zeros((max(len(points), 1), 12), dtype=np.uint64)
+    inf = np.zeros(max(len(points), 1), dtype=np.uint8)
+    for i, p in enumerate(points):
+        xy[i], inf[i] = p.xy, 1 if p.infinity else 0
+    return xy, inf
+
+
+def _g2_device(points):
+    import torch
+    xy = np.zeros((max(len(points), 1), 24), dtype=np.uint64)
+    inf = np.zeros(max(len(points), 1), dtype=np.uint8)
+    for i, q in enumerate(points):
+        xy[i], inf[i] = q.xy, 1 if q.infinity else 0
+    return torch.from_numpy(xy.view(np.int64)).cuda(), torch.from_numpy(inf).cuda()
+
+
+def g2_prepare(g2_points):
+    """zkhip_g2_prepare: the Miller-loop lines of each G2 point (a uint8 CUDA tensor) for pairing(..., prepared=...)"""
+    import torch
+    n = len(g2_points)
+    qxy, qinf = _g2_device(g2_points)
+    N.lib().zkhip_g2_prepared_bytes.restype = C.c_size_t
+    prep = torch.empty(max(N.lib().zkhip_g2_prepared_bytes(C.c_size_t(n)), 1), dtype=torch.uint8, device=qxy.device)
+    ctx = N.Context.get(qxy.device.index)
+    st = N.lib().zkhip_g2_prepare(ctx.handle, N.ptr(qxy), N.ptr(qinf), C.c_size_t(n), N.ptr(prep))
+    _check_points(st, "g2_prepare")
+    return prep
+
+
+def _check_points(st, what):
+    if st == N.ERR_ARG:
+        raise ValueError("%s: a point is off its curve or outside the prime-order subgroup" % what)
+    N.check(st, what)
+
+
+def pairing(g1_points, g2_points=None, prepared=None):
+    """zkhip_pairing: e(g1_points[k], g2_points[k]) for every k -> uint64 [n, 72] GT values (gt_ints() for canonical ints).
+    With `prepared` (g2_prepare's lines) instead of g2_points: zkhip_pairing_prepared."""
+    import torch
+    n = len(g1_points)
+    pxy, pinf = _g1_arrays(g1_points)
+    pxy_d = torch.from_numpy(pxy.view(np.int64)).cuda()
+    pinf_d = torch.from_numpy(pinf).cuda()
+    out = torch.empty((max(n, 1), 72), dtype=torch.int64, device=pxy_d.device)
+    ctx = N.Context.get(pxy_d.device.index)
+    if prepared is not None:
+        st = N.lib().zkhip_pairing_prepared(ctx.handle, N.ptr(pxy_d), N.ptr(pinf_d), N.ptr(prepared), C.c_size_t(n), N.ptr(out))
+    else:
+        if len(g2_points) != n:
+            raise AssertionError("pairing: as many G2 as G1 points")
+        qxy, qinf = _g2_device(g2_points)
+        st = N.lib().zkhip_pairing(ctx.handle, N.ptr(pxy_d), N.ptr(pinf_d), N.ptr(qxy), N.ptr(qinf), C.c_size_t(n), N.ptr(out))
+    _check_points(st, "pairing")
+    return out.cpu().numpy().view(np.uint64)[:n]
 
 
 class DenseUnivariatePolynomial:
@@ -79,15 +168,29 @@ class DenseUnivariatePolynomial:
 
 
 class TrustedSetup:
-    """kzg/src/trusted_setup.rs:9-13, G1 side only, stored affine in HBM: points int64 [n, 12], inf uint8 [n]."""
+    """kzg/src/trusted_setup.rs:9-13, stored affine in HBM: G1 points int64 [n, 12], inf uint8 [n]; the G2 half (what `verify`
+    needs) when asked for: powers_of_tau_in_g2 int64 [m, 24], g2_inf uint8 [m], else None."""
 
-    def __init__(self, points_xy, inf):
+    def __init__(self, points_xy, inf, g2_xy=None, g2_inf=None):
         import torch
         if not isinstance(points_xy, torch.Tensor):
             points_xy = torch.from_numpy(np.ascontiguousarray(points_xy, dtype=np.uint64).view(np.int64)).cuda()
             inf = torch.from_numpy(np.ascontiguousarray(inf, dtype=np.uint8)).cuda()
         self.powers_of_tau_in_g1 = points_xy.contiguous()
         self.inf = inf.contiguous()
+        if g2_xy is not None and not isinstance(g2_xy, torch.Tensor):
+            g2_xy = torch.from_numpy(np.ascontiguousarray(g2_xy, dtype=np.uint64).reshape(-1, 24).view(np.int64)).cuda()
+            g2_inf = torch.from_numpy(np.ascontiguousarray(g2_inf, dtype=np.uint8)).cuda()
+        self.powers_of_tau_in_g2 = None if g2_xy is None else g2_xy.contiguous()
+        self.g2_inf = None if g2_inf is None else g2_inf.contiguous()
+
+    def g2_points(self):
+        """the G2 half as a list of G2Affine"""
+        if self.powers_of_tau_in_g2 is None:
+            return []
+        xy = self.powers_of_tau_in_g2.cpu().numpy().view(np.uint64)
+        inf = self.g2_inf.cpu().numpy()
+        return [G2Affine(xy[i], inf[i]) for i in range(xy.shape[0])]
 
     def __len__(self):
         return self.powers_of_tau_in_g1.shape[0]
@@ -96,7 +199,9 @@ class TrustedSetup:
         """Identity of the SRS the derived caches were built from: the tensors' storage and torch's in-place version counters (an
         in-place edit of `powers_of_tau_in_g1` / `inf`, or assigning new tensors, invalidates the shifted table and the folded levels)."""
         p, i = self.powers_of_tau_in_g1, self.inf
-        return (p.data_ptr(), p.shape[0], p._version, i.data_ptr(), i._version)
+        g2 = getattr(self, "powers_of_tau_in_g2", None)
+        g2s = () if g2 is None else (g2.data_ptr(), g2.shape[0], g2._version, self.g2_inf.data_ptr(), self.g2_inf._version)
+        return (p.data_ptr(), p.shape[0], p._version, i.data_ptr(), i._version) + g2s
 
     def _fingerprint(self):
         """Content check for what the stamp cannot see -- writes through raw pointers (a kernel filling the tensors via data_ptr())
@@ -121,6 +226,31 @@ class TrustedSetup:
                 except Exception:       # noqa: BLE001 -- interpreter shutdown
                     pass
         self._table = self._folded = self._level_tables = None
+        self._prepared = {}
+
+    def prepared_lines(self, univariate):
+        """The Miller-loop lines of [G2, the G2 half] (multilinear) or [G2, tau G2] (univariate) that every `verify` against this SRS
+        uses (zkhip_kzg_prepare, ~19 KiB per point): built once, kept with the other derived tables."""
+        if self.powers_of_tau_in_g2 is None:
+            raise ValueError("this TrustedSetup has no G2 half: build it with setup(..., g2=True) / generate_srs(..., g2=True)")
+        self._check_caches()
+        prepared = getattr(self, "_prepared", None)
+        if prepared is None:
+            prepared = self._prepared = {}
+        if univariate not in prepared:
+            import torch
+            g2, inf = self.powers_of_tau_in_g2, self.g2_inf
+            if univariate:
+                if g2.shape[0] < 2:
+                    raise IndexError("powers_of_tau_in_g2[1]: the G2 half has %d points" % g2.shape[0])
+                g2, inf = g2[1:2], inf[1:2]
+            n = g2.shape[0]
+            N.lib().zkhip_g2_prepared_bytes.restype = C.c_size_t
+            buf = torch.empty(N.lib().zkhip_g2_prepared_bytes(C.c_size_t(n + 1)), dtype=torch.uint8, device=g2.device)
+            ctx = N.Context.get(g2.device.index)
+            _check_points(N.lib().zkhip_kzg_prepare(ctx.handle, N.ptr(g2), N.ptr(inf), C.c_size_t(n), N.ptr(buf)), "kzg_prepare")
+            prepared[univariate] = buf
+        return prepared[univariate]
 
     def __del__(self):
         self._drop_tables()
@@ -220,15 +350,26 @@ class TrustedSetup:
         return (torch.empty((n, 12), dtype=torch.int64, device="cuda"), torch.empty((n,), dtype=torch.uint8, device="cuda"))
 
     @staticmethod
-    def setup(eval_points):
-        """TrustedSetup::setup (trusted_setup.rs:15-35): G * eq_i(tau) over the boolean hypercube, MSB first."""
+    def setup(eval_points, g2=False):
+        """TrustedSetup::setup (trusted_setup.rs:15-35): G * eq_i(tau) over the boolean hypercube, MSB first; with g2=True also
+        generate_powers_of_tau_in_g2 (:37-45): tau_i * G2, what `verify` needs."""
         tau = _fr_host(eval_points)
         nv = tau.shape[0]
         pts, inf = TrustedSetup._alloc(1 << nv)
         ctx = N.Context.get()
         N.check(N.lib().zkhip_srs_multilinear_g1(ctx.handle, tau.ctypes.data_as(C.c_void_p), C.c_uint32(nv),
                                                  N.ptr(pts), N.ptr(inf)), "srs_multilinear")
-        return TrustedSetup(pts, inf)
+        if not g2:
+            return TrustedSetup(pts, inf)
+        qxy, qinf = TrustedSetup._alloc_g2(nv)
+        N.check(N.lib().zkhip_srs_multilinear_g2(ctx.handle, tau.ctypes.data_as(C.c_void_p), C.c_uint32(nv),
+                                                 N.ptr(qxy), N.ptr(qinf)), "srs_multilinear_g2")
+        return TrustedSetup(pts, inf, qxy, qinf)
+
+    @staticmethod
+    def _alloc_g2(n):
+        import torch
+        return (torch.zeros((n, 24), dtype=torch.int64, device="cuda"), torch.zeros((n,), dtype=torch.uint8, device="cuda"))
 
 
 def _commit(points, inf, n_points, scalars, n_scalars, require_equal_len, table=None):
@@ -343,6 +484,46 @@ class MultilinearKZG:
         return MultilinearKZGProof(ev, [G1Affine(pxy[i], pinf[i]) for i in range(nv)])
 
 
+    @staticmethod
+    def verify(commit, verifier_points, proof, srs):
+        """MultilinearKZGInterface::verify (multilinear_kzg.rs:90-112) -> bool"""
+        return bool(MultilinearKZG.verify_batch([commit], [verifier_points], [proof], srs)[0])
+
+    @staticmethod
+    def verify_batch(commits, verifier_points, proofs, srs):
+        """`verify` of many openings of the same number of variables against one SRS in one pass -> np.ndarray[bool]"""
+        b = len(commits)
+        if not (len(verifier_points) == len(proofs) == b):
+            raise AssertionError("verify_batch: one point vector and one proof per commitment")
+        if srs.powers_of_tau_in_g2 is None:
+            srs.prepared_lines(False)                       # raises the missing-G2 error
+        n_g2 = len(srs.powers_of_tau_in_g2)
+        pts = [_fr_host(v) for v in verifier_points]
+        nv = pts[0].shape[0] if b else n_g2
+        for i in range(b):
+            if pts[i].shape[0] != nv or len(proofs[i].proofs) != nv:
+                raise AssertionError("Length mismatch")
+        if nv != n_g2:
+            raise AssertionError("Length mismatch")         # sum_pairing_results (utils.rs:49-50)
+        prep = srs.prepared_lines(False)
+        cxy, cinf = _g1_arrays(commits)
+        pxy, pinf = _g1_arrays([q for p in proofs for q in p.proofs])
+        ev = np.zeros((max(b, 1), 4), dtype=np.uint64)
+        z = np.zeros((max(b * nv, 1), 4), dtype=np.uint64)
+        for i in range(b):
+            ev[i] = np.asarray(proofs[i].evaluation, dtype=np.uint64).reshape(4)
+            z[i * nv: (i + 1) * nv] = pts[i]
+        ok = np.zeros(max(b, 1), dtype=np.uint8)
+        ctx = N.Context.get(prep.device.index)
+        vp = C.c_void_p
+        st = N.lib().zkhip_kzg_verify_batch(ctx.handle, C.c_size_t(b), C.c_uint32(nv), cxy.ctypes.data_as(vp), cinf.ctypes.data_as(vp),
+                                            ev.ctypes.data_as(vp), z.ctypes.data_as(vp), pxy.ctypes.data_as(vp), pinf.ctypes.data_as(vp),
+                                            N.ptr(srs.powers_of_tau_in_g2), N.ptr(srs.g2_inf), C.c_size_t(n_g2), N.ptr(prep),
+                                            ok.ctypes.data_as(vp))
+        _check_points(st, "multilinear verify")
+        return ok[:b].astype(bool)
+
+
 class UnivariateKZGProof:
     """kzg/src/univariate_kzg.rs:11-15: evaluation (Montgomery limbs uint64 [4]) + the quotient's commitment"""
 
@@ -367,14 +548,48 @@ class UnivariateKZG:
         return UnivariateKZGProof(ev, G1Affine(xy, inf.value))
 
     @staticmethod
-    def generate_srs(tau, max_degree):
-        """UnivariateKZGInterface::generate_srs (univariate_kzg.rs:18-35), G1 powers"""
+    def generate_srs(tau, max_degree, g2=False):
+        """UnivariateKZGInterface::generate_srs (univariate_kzg.rs:18-35): G1 powers; with g2=True also the G2 powers tau^i G2"""
         t = _fr_host(tau)
         pts, inf = TrustedSetup._alloc(max_degree + 1)
         ctx = N.Context.get()
         N.check(N.lib().zkhip_srs_univariate_g1(ctx.handle, t.ctypes.data_as(C.c_void_p), C.c_size_t(max_degree),
                                                 N.ptr(pts), N.ptr(inf)), "srs_univariate")
-        return TrustedSetup(pts, inf)
+        if not g2:
+            return TrustedSetup(pts, inf)
+        qxy, qinf = TrustedSetup._alloc_g2(max_degree + 1)
+        N.check(N.lib().zkhip_srs_univariate_g2(ctx.handle, t.ctypes.data_as(C.c_void_p), C.c_size_t(max_degree),
+                                                N.ptr(qxy), N.ptr(qinf)), "srs_univariate_g2")
+        return TrustedSetup(pts, inf, qxy, qinf)
+
+    @staticmethod
+    def verify(commit, verifier_point, proof, srs):
+        """UnivariateKZGInterface::verify (univariate_kzg.rs:83-104) -> bool"""
+        return bool(UnivariateKZG.verify_batch([commit], [verifier_point], [proof], srs)[0])
+
+    @staticmethod
+    def verify_batch(commits, verifier_points, proofs, srs):
+        """`verify` of many openings against one SRS in one pass -> np.ndarray[bool], one verdict per opening"""
+        b = len(commits)
+        if not (len(verifier_points) == len(proofs) == b):
+            raise AssertionError("verify_batch: one point and one proof per commitment")
+        prep = srs.prepared_lines(True)
+        cxy, cinf = _g1_arrays(commits)
+        pxy, pinf = _g1_arrays([p.proof for p in proofs])
+        ev = np.zeros((max(b, 1), 4), dtype=np.uint64)
+        z = np.zeros((max(b, 1), 4), dtype=np.uint64)
+        for i in range(b):
+            ev[i] = np.asarray(proofs[i].evaluation, dtype=np.uint64).reshape(4)
+            z[i] = _fr_host(verifier_points[i]).reshape(4)
+        ok = np.zeros(max(b, 1), dtype=np.uint8)
+        ctx = N.Context.get(prep.device.index)
+        vp = C.c_void_p
+        st = N.lib().zkhip_univariate_kzg_verify_batch(ctx.handle, C.c_size_t(b), cxy.ctypes.data_as(vp), cinf.ctypes.data_as(vp),
+                                                       ev.ctypes.data_as(vp), z.ctypes.data_as(vp), pxy.ctypes.data_as(vp),
+                                                       pinf.ctypes.data_as(vp), N.ptr(srs.powers_of_tau_in_g2), N.ptr(srs.g2_inf),
+                                                       C.c_size_t(len(srs.powers_of_tau_in_g2)), N.ptr(prep), ok.ctypes.data_as(vp))
+        _check_points(st, "univariate verify")
+        return ok[:b].astype(bool)
 
     @staticmethod
     def commitment(poly, srs):
