@@ -213,7 +213,33 @@ static void test_pool() {
     }
 }
 
+// loans end in every order, by end(), by destruction and by being overwritten; the desk's count comes back to zero
+static void test_loan() {
+    ZkLoanDesk desk;
+    EXPECT(!desk.lent());
+    {
+        ZkLoan a(desk), b(desk), none;
+        EXPECT(desk.out == 2 && a && b && !none);
+        ZkLoan c(std::move(a));                    // a move hands the loan on: still two
+        EXPECT(desk.out == 2 && !a && c);
+        b.end(); b.end();                          // ending twice returns it once
+        EXPECT(desk.out == 1 && desk.lent());
+        none = ZkLoan(desk);
+        EXPECT(desk.out == 2);
+        none = std::move(c);                       // overwriting returns the loan held before
+        EXPECT(desk.out == 1 && none && !c);
+    }
+    EXPECT(desk.out == 0 && !desk.lent());
+    for (int order = 0; order < 6; ++order) {      // three loans ended in each of the six orders
+        ZkLoan l[3] = {ZkLoan(desk), ZkLoan(desk), ZkLoan(desk)};
+        const int perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+        for (int k = 0; k < 3; ++k) { l[perm[order][k]].end(); EXPECT(desk.out == 2 - k); }
+    }
+    EXPECT(desk.out == 0);
+}
+
 int main() {
+    test_loan();
     test_fr();
     test_transcript();
     test_g1();

@@ -186,7 +186,7 @@ struct ComposedRun {
         const size_t bytes_off = pipe_off + 2 * PIPE_REC_BYTES;
         const size_t chunk = std::min<size_t>(n, (size_t)1 << 18);   // entries per staging buffer of prove()'s table-bytes pass
         ZK_TRY(c->reserve_ws(bytes_off + (multi && !partial ? 64 * chunk : 0)));
-        ws = (char*)c->d_ws;
+        ws = (char*)c->ws.ptr;
         d_stage_w = (uint64_t*)(ws + w_off);
         d_pipe_rec[0] = (uint64_t*)(ws + pipe_off);
         d_pipe_rec[1] = (uint64_t*)(ws + pipe_off + PIPE_REC_BYTES);
@@ -201,12 +201,12 @@ struct ComposedRun {
                 std::vector<zkhost::Fr> m = zkhost::interpolation_matrix(d);
                 std::memcpy(&mats[(size_t)d * (CMP_MAX_K + 1) * (CMP_MAX_K + 1) * 4], m.data(), m.size() * 32);
             }
-            void* mem = nullptr;
-            if (hipMalloc(&mem, sizeof(ComposedDev)) != hipSuccess) return ZKHIP_ERR_NOMEM;
-            if (hipMemcpy(mem, img.data(), sizeof(ComposedDev), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(mem); return ZKHIP_ERR_HIP; }
-            c->d_composed = mem;
+            DevMem mem;
+            if (dev_alloc(mem, sizeof(ComposedDev)) != hipSuccess) return ZKHIP_ERR_NOMEM;
+            if (hipMemcpy(mem.get(), img.data(), sizeof(ComposedDev), hipMemcpyHostToDevice) != hipSuccess) return ZKHIP_ERR_HIP;
+            c->d_composed = std::move(mem);
         }
-        st = (ComposedDev*)c->d_composed;
+        st = (ComposedDev*)c->d_composed.get();
         d_partials = c->small_u64(ZK_SMALL_PARTIALS);
         d_rp = c->small_u64(ZK_SMALL_ROUNDPOLYS);
         d_ch = c->small_u64(ZK_SMALL_CHALLENGES);
@@ -231,15 +231,15 @@ struct ComposedRun {
                 const int sl = (int)(k & 1);
                 uint8_t* stage = d_bytes + (size_t)sl * 32 * chunk;
                 hipLaunchKernelGGL(to_bytes_kernel, dim3(mle_grid_stream(len)), dim3(MLE_BLOCK), 0, c->stream, ptrs[q] + 4 * off, len, (uint32_t*)stage);
-                ZK_HIP(c, hipMemcpyAsync(c->msm_pin[sl], stage, 32 * len, hipMemcpyDeviceToHost, c->stream));
-                ZK_HIP(c, hipEventRecord(c->msm_ev[sl], c->stream));
+                ZK_HIP(c, hipMemcpyAsync(c->msm_pin[sl].ptr, stage, 32 * len, hipMemcpyDeviceToHost, c->stream));
+                ZK_HIP(c, hipEventRecord(c->msm_ev[sl].get(), c->stream));
                 return ZKHIP_OK;
             };
             ZK_TRY(issue(0));
             for (size_t k = 0; k < n_chunks; ++k) {
                 if (k + 1 < n_chunks) ZK_TRY(issue(k + 1));            // its buffers held chunk k - 1, hashed in the last iteration
-                ZK_HIP(c, hipEventSynchronize(c->msm_ev[k & 1]));
-                sha.update((const uint8_t*)c->msm_pin[k & 1], 32 * chunk_len(k));
+                ZK_HIP(c, hipEventSynchronize(c->msm_ev[k & 1].get()));
+                sha.update((const uint8_t*)c->msm_pin[k & 1].ptr, 32 * chunk_len(k));
             }
             Sha256State hs = {};
             std::memcpy(hs.h, sha.h, 32);
@@ -774,6 +774,7 @@ int zk_mc_shape(const uint32_t* sizes, uint32_t n_terms, uint32_t n_lin, uint32_
 struct zkhip_mc_state {
     ComposedRun run;
     uint32_t world = 1;
+    ZkLoan ws_loan;              // the session's tables live in the context's workspace: lent from begin to finish / abort
     int sums_pending = 0;        // which record is out and not absorbed yet: 0 none, 1 a round record (zkhip_mc_round_sums), 2 a stage record
     size_t pending_cn = 0;       // entries per table when that record was taken (the matching absorb must find the session where it left it)
 };
@@ -797,22 +798,15 @@ extern "C" int zkhip_mc_begin_ex(zkhip_ctx* c, const uint64_t* const* d_local_ta
     const uint32_t rounds = log2_exact(n_local) + log2_exact(world);
     if (rounds == 0 || out_base + rounds > ZK_MAX_ROUNDS) return ZKHIP_ERR_SHAPE;
     ZK_TRY(c->activate());
-    if (c->ws_lent) return ZKHIP_ERR_BUSY;      // one session per context: its tables live in the context's workspace
-    zkhip_mc_state* s = new (std::nothrow) zkhip_mc_state();
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // one session per context: its tables live in the context's workspace
+    std::unique_ptr<zkhip_mc_state> s(new (std::nothrow) zkhip_mc_state());
     if (!s) return ZKHIP_ERR_NOMEM;
     s->world = world;
-    const int rc = s->run.setup(c, d_local_tables, term_sizes, n_terms, n_local, rounds, multi, h_sum, 1, d_local_lin, cont);
+    ZK_TRY(s->run.setup(c, d_local_tables, term_sizes, n_terms, n_local, rounds, multi, h_sum, 1, d_local_lin, cont));
     s->run.out_base = out_base;
-    if (rc != ZKHIP_OK) {
-        delete s;
-        return rc;
-    }
-    if (world > s->run.tail_len) {   // shards of one entry per table must fit the replicated tail when gathered
-        delete s;
-        return ZKHIP_ERR_SHAPE;
-    }
-    c->ws_lent = true;              // until finish / abort: every other user of the workspace gets ZKHIP_ERR_BUSY
-    *out = s;
+    if (world > s->run.tail_len) return ZKHIP_ERR_SHAPE;   // shards of one entry per table must fit the replicated tail when gathered
+    s->ws_loan = ZkLoan(c->ws_loans);      // until finish / abort: every other user of the workspace gets ZKHIP_ERR_BUSY
+    *out = s.release();
     return ZKHIP_OK;
 }
 extern "C" int zkhip_mc_begin(zkhip_ctx* c, const uint64_t* const* d_local_tables, const uint32_t* term_sizes, uint32_t n_terms,
@@ -923,7 +917,6 @@ extern "C" int zkhip_mc_finish(zkhip_mc_state* s, uint32_t* h_lens, uint64_t* h_
         if (!h_round_polys || !h_challenges || (s->run.multi && !h_lens) || s->run.round != s->run.n_rounds) rc = ZKHIP_ERR_ARG;
         else if ((rc = s->run.c->activate()) == ZKHIP_OK) rc = s->run.collect(h_lens, h_round_polys, h_challenges);
     }
-    s->run.c->ws_lent = false;
     delete s;
     return rc;
 }
@@ -932,7 +925,6 @@ extern "C" int zkhip_mc_abort(zkhip_mc_state* s) {
     zkhip_ctx* c = s->run.c;
     int rc = ZKHIP_OK;
     if (c->activate() != ZKHIP_OK || hipStreamSynchronize(c->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    c->ws_lent = false;
     delete s;
     return rc;
 }

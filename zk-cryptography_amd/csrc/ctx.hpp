@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "hip_own.hpp"
 #include "host_util.hpp"
 
 #define ZK_MAX_ROUNDS 48          /* rounds of one sumcheck: tables of 2^48 entries are far beyond 288 GB; a GKR layer of width 2^24 takes 2 x 24 */
@@ -55,40 +56,46 @@ enum : size_t {
         if (_s != ZKHIP_OK) return _s; \
     } while (0)
 
-struct ZkProfEvent { hipEvent_t start, stop; };
+struct ZkProfEvent { zk::Event start, stop; };
 struct ZkProfRecord { const char* name; size_t event; double bytes; };
 
+// library structs a context owns without knowing their layout: each deleter is defined in the unit that defines the struct
+struct NttCache;                                                        // ntt.hip
+struct NttCacheDelete { void operator()(NttCache*) const; };
+struct MsmPending;                                                      // msm.hip
+struct MsmPendingDelete { void operator()(MsmPending*) const; };
+namespace zk { struct MsmGeometry; }                                    // msm_geometry.hpp
+struct ZkCtxDestroy { void operator()(zkhip_ctx* c) const { (void)zkhip_ctx_destroy(c); } };   // a context is drained, not just deleted
+using ZkCtxOwner = std::unique_ptr<zkhip_ctx, ZkCtxDestroy>;
+
+// Every member that stands for a HIP resource is an owner (hip_own.hpp); a plain handle is a view of one owned elsewhere.  Members go
+// away in reverse declaration order, after zkhip_ctx_destroy has made the device current, destroyed the GKR lanes and drained every
+// stream the context created -- so among buffers, events and streams the order does not matter.  It does for host_pool: see there.
 struct zkhip_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    hipStream_t stream = nullptr;    // the caller's stream (NULL = the device's default stream), or a view of owned_stream
+    zk::Stream owned_stream;         // a GKR lane's stream: the only contexts that create their own
     int last_hip = 0;
-    void* d_ws = nullptr;       // large workspace (ping-pong tables, MSM buckets, ...)
-    size_t ws_bytes = 0;
-    void* d_fingerprint = nullptr;   // zkhip_srs_fingerprint's 52 words, its stream (highest priority) and the event that orders it behind the caller's
-    hipStream_t guard_stream = nullptr;
-    hipEvent_t guard_ev = nullptr;
-    void* d_composed = nullptr;      // composed provers: ComposedDev (transcript + interpolation matrices of every degree), uploaded once
-    void* d_gen_table = nullptr;   // SRS generation: d * 2^(8w) * G for 32 windows x 255 digits, affine (+ infinity flags); built on first use
-    void* ntt_state = nullptr;     // twiddle tables and pass plans of the transforms this context has run (ntt.hip); ntt_free releases them
-    void (*ntt_free)(void*) = nullptr;
-    void* d_aux = nullptr;      // second grow-only buffer for entry points that call others which own d_ws (kzg_open)
+    zk::GrowBuf ws;                  // large workspace (ping-pong tables, MSM buckets, ...); see reserve_ws / ws_loans
+    zk::DevMem d_fingerprint;        // zkhip_srs_fingerprint's 52 words, its stream (highest priority) and the event that orders it behind the caller's
+    zk::Stream guard_stream;
+    zk::Event guard_ev;
+    zk::DevMem d_composed;           // composed provers: ComposedDev (transcript + interpolation matrices of every degree), uploaded once (untyped: ComposedDev needs composed_kernels.hpp)
+    zk::DevMem d_gen_table;          // SRS generation: d * 2^(8w) * G for 32 windows x 255 digits, affine (+ infinity flags); built on first use
+    std::unique_ptr<NttCache, NttCacheDelete> ntt_state;   // twiddle tables and pass plans of the transforms this context has run (ntt.hip)
+    zk::GrowBuf aux;                 // second grow-only buffer for entry points that call others which own the workspace (kzg_open)
     uint32_t outer_token = 0;   // sessions that feed an outer transcript (composed_kernels.hpp): a value no earlier session's flags hold
-    size_t aux_bytes = 0;
     // pinned result buffers + events for commits whose host epilogue is deferred (msm_enqueue / msm_finish), and the side
     // streams on which MultilinearKZG::open runs its per-round commits next to each other
     static constexpr int MSM_SLOTS = 6;
-    void* msm_pin[MSM_SLOTS] = {};
-    size_t msm_pin_bytes[MSM_SLOTS] = {};
-    hipEvent_t msm_ev[MSM_SLOTS] = {};
-    hipStream_t side[MSM_SLOTS] = {};
-    hipEvent_t fork_ev = nullptr, join_ev = nullptr, serial_ev = nullptr;
+    zk::GrowBuf msm_pin[MSM_SLOTS];
+    zk::Event msm_ev[MSM_SLOTS];
+    zk::Stream side[MSM_SLOTS];
+    zk::Event fork_ev, join_ev, serial_ev;
     int ensure_side_streams() {
         for (int i = 0; i < MSM_SLOTS; ++i)
-            if (!side[i] && hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (!fork_ev && hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (!join_ev && hipEventCreateWithFlags(&join_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (!serial_ev && hipEventCreateWithFlags(&serial_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
+            if (zk::ensure_stream(side[i]) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (zk::ensure_event(fork_ev) != hipSuccess || zk::ensure_event(join_ev) != hipSuccess || zk::ensure_event(serial_ev) != hipSuccess) return ZKHIP_ERR_HIP;
         return ZKHIP_OK;
     }
     // The basic prover's streaming fold runs on a LOW-priority stream of its own next to the serial transcript kernel
@@ -96,18 +103,15 @@ struct zkhip_ctx {
     // (DESIGN.md section 5): a CU-masked fold stream that leaves one CU to the serial kernel -- such streams can only be
     // created "blocking", and the implicit synchronisation with the NULL stream (PyTorch's default) cost 30-60 us per
     // fork / join; sharing a CU with fold waves -- the transcript wave runs at half speed.
-    hipStream_t fold_stream = nullptr;
+    zk::Stream fold_stream;
     int ensure_fold_stream() {
-        if (fold_stream) return ensure_side_streams();
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (hipStreamCreateWithPriority(&fold_stream, hipStreamNonBlocking, least) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (zk::ensure_stream(fold_stream, zk::Prio::Low) != hipSuccess) return ZKHIP_ERR_HIP;
         return ensure_side_streams();
     }
     // coarse block sums left by zkhip_mle_block_sums for the prover's first rounds: a ring (canonical, then Montgomery: 64 KiB
     // each; more entries than proofs in flight), so that the sums of a table whose proof is in flight survive the poly_sum() of the next tables
     static constexpr int COARSE_RING = 16;
-    void* d_coarse[COARSE_RING] = {};
+    zk::DevMem d_coarse[COARSE_RING];
     const void* coarse_of[COARSE_RING] = {}; size_t coarse_n[COARSE_RING] = {}; uint32_t coarse_k1[COARSE_RING] = {};
     int coarse_owner[COARSE_RING] = {};     // result slot + 1 of the proof that still reads the entry (0: nobody): such an entry is never handed out
     int coarse_next = 0;
@@ -116,7 +120,7 @@ struct zkhip_ctx {
             const int k = coarse_next;
             coarse_next = (coarse_next + 1) % COARSE_RING;
             if (coarse_owner[k]) continue;          // a proof in flight reads it from a stream of its own: no event orders a rewrite behind that
-            if (!d_coarse[k] && hipMalloc(&d_coarse[k], 2 * 1024 * 32) != hipSuccess) return ZKHIP_ERR_NOMEM;
+            if (!d_coarse[k] && zk::dev_alloc(d_coarse[k], 2 * 1024 * 32) != hipSuccess) return ZKHIP_ERR_NOMEM;
             coarse_of[k] = nullptr;
             *slot = k;
             return ZKHIP_OK;
@@ -133,11 +137,11 @@ struct zkhip_ctx {
     // hardware queues, and two streams that take turns in one queue wait for each other's kernels (profiles/r06/NOTES.md section 7: with six
     // serial streams on four queues the first rounds of a proof stood behind another lane's 100 us serial kernel)
     struct ProofLane {
-        hipStream_t serial = nullptr, fold = nullptr;
-        bool borrowed = false;                  // the streams are those of lane k - 4
-        hipEvent_t begin_ev = nullptr, fork_ev = nullptr, serial_ev = nullptr;
-        void* ws = nullptr; size_t ws_bytes = 0;
-        void* small = nullptr;
+        hipStream_t serial = nullptr, fold = nullptr;   // views: of own_serial / own_fold, or of the streams of lane k - 4
+        zk::Stream own_serial, own_fold;
+        zk::Event begin_ev, fork_ev, serial_ev;
+        zk::GrowBuf ws;
+        zk::DevMem small;
     };
     static constexpr int PROOF_SLOTS = 8;      // proofs in flight (measured at 2^24 with 2 .. 12, see bench.py `pipelined`; nothing is gained beyond 8)
     static constexpr int LANE_STREAMS = 4;     // = the hardware queues of one stream priority
@@ -173,12 +177,11 @@ struct zkhip_ctx {
         if (k >= LANE_STREAMS) {
             const int rc = ensure_lane_streams(k - LANE_STREAMS);
             if (rc != ZKHIP_OK) return rc;
-            L.serial = lanes[k - LANE_STREAMS].serial; L.borrowed = true;
+            L.serial = lanes[k - LANE_STREAMS].serial;
             return ZKHIP_OK;
         }
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (hipStreamCreateWithPriority(&L.serial, hipStreamNonBlocking, greatest) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (zk::ensure_stream(L.own_serial, zk::Prio::High) != hipSuccess) return ZKHIP_ERR_HIP;
+        L.serial = L.own_serial.get();
         // (measured and dropped, profiles/r06/NOTES.md: some lanes' serial stream at normal instead of high priority, or their fold stream at
         // normal instead of low: 0.27-0.32 ms per proof in flight instead of 0.23; the serial kernels must get in front of every streaming pass)
         return ZKHIP_OK;
@@ -200,83 +203,57 @@ struct zkhip_ctx {
             L.fold = lanes[k - LANE_STREAMS].fold;
             return ZKHIP_OK;
         }
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (hipStreamCreateWithPriority(&L.fold, hipStreamNonBlocking, least) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (zk::ensure_stream(L.own_fold, zk::Prio::Low) != hipSuccess) return ZKHIP_ERR_HIP;
+        L.fold = L.own_fold.get();
         return ZKHIP_OK;
     }
     int ensure_lane(int k, size_t ws_need) {
         ProofLane& L = lanes[k];
         { const int rc = ensure_lane_streams(k); if (rc != ZKHIP_OK) return rc; }
         { const int rc = ensure_lane_fold(k); if (rc != ZKHIP_OK) return rc; }
-        if (!L.small) {
-            if (hipEventCreateWithFlags(&L.begin_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-            if (hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-            if (hipEventCreateWithFlags(&L.serial_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-            if (hipMalloc(&L.small, ZK_SMALL_BYTES) != hipSuccess) return ZKHIP_ERR_NOMEM;
-        }
-        if (ws_need > L.ws_bytes) {                 // grow-only; the lane is idle here (its ticket is free)
-            if (L.ws) { if (hipStreamSynchronize(L.serial) != hipSuccess || (L.fold && hipStreamSynchronize(L.fold) != hipSuccess)) return ZKHIP_ERR_HIP; hipFree(L.ws); }
-            L.ws = nullptr; L.ws_bytes = 0;
-            if (hipMalloc(&L.ws, ws_need) != hipSuccess) return ZKHIP_ERR_NOMEM;
-            L.ws_bytes = ws_need;
-        }
-        return ZKHIP_OK;
+        if (zk::ensure_event(L.begin_ev) != hipSuccess || zk::ensure_event(L.fork_ev) != hipSuccess || zk::ensure_event(L.serial_ev) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (!L.small && zk::dev_alloc(L.small, ZK_SMALL_BYTES) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        // grow-only; the lane is idle here (its ticket is free), but what it enqueued last may still read a block it already has
+        if (L.ws.ptr) return L.ws.reserve(ws_need, {L.serial, L.fold});
+        return L.ws.reserve(ws_need);
     }
     int reserve_msm_pin(int slot, size_t bytes) {
-        if (!msm_ev[slot] && hipEventCreateWithFlags(&msm_ev[slot], hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (bytes <= msm_pin_bytes[slot]) return ZKHIP_OK;
-        if (msm_pin[slot]) hipHostFree(msm_pin[slot]);
-        msm_pin[slot] = nullptr; msm_pin_bytes[slot] = 0;
-        if (hipHostMalloc(&msm_pin[slot], bytes, hipHostMallocDefault) != hipSuccess) return ZKHIP_ERR_NOMEM;
-        msm_pin_bytes[slot] = bytes;
-        return ZKHIP_OK;
+        if (zk::ensure_event(msm_ev[slot]) != hipSuccess) return ZKHIP_ERR_HIP;
+        return msm_pin[slot].reserve_pinned(bytes);
     }
     // geometry tables of the commit in slot `slot` (msm_build_geometry): device copy + pinned staging, kept while the geometry is the same
-    void* msm_tab_dev[MSM_SLOTS] = {};
-    void* msm_tab_pin[MSM_SLOTS] = {};
-    size_t msm_tab_bytes[MSM_SLOTS] = {};
-    std::shared_ptr<const void> msm_tab_geo[MSM_SLOTS];   // the geometry whose tables the device copy holds (kept alive: its address is its identity)
+    zk::GrowBuf msm_tab_dev[MSM_SLOTS], msm_tab_pin[MSM_SLOTS];
+    std::shared_ptr<const zk::MsmGeometry> msm_tab_geo[MSM_SLOTS];   // the geometry whose tables the device copy holds (kept alive: its address is its identity)
     int reserve_msm_tab(int slot, size_t bytes) {
-        if (bytes <= msm_tab_bytes[slot]) return ZKHIP_OK;
-        if (msm_tab_dev[slot]) hipFree(msm_tab_dev[slot]);
-        if (msm_tab_pin[slot]) hipHostFree(msm_tab_pin[slot]);
-        msm_tab_dev[slot] = nullptr; msm_tab_pin[slot] = nullptr; msm_tab_bytes[slot] = 0; msm_tab_geo[slot].reset();
         const size_t cap = (bytes + 65535) & ~(size_t)65535;
-        if (hipMalloc(&msm_tab_dev[slot], cap) != hipSuccess) return ZKHIP_ERR_NOMEM;
-        if (hipHostMalloc(&msm_tab_pin[slot], cap, hipHostMallocDefault) != hipSuccess) return ZKHIP_ERR_NOMEM;
-        msm_tab_bytes[slot] = cap;
-        return ZKHIP_OK;
+        if (cap > msm_tab_dev[slot].bytes || cap > msm_tab_pin[slot].bytes) msm_tab_geo[slot].reset();      // new blocks: nothing uploaded yet
+        ZK_TRY(msm_tab_dev[slot].reserve(cap));
+        return msm_tab_pin[slot].reserve_pinned(cap);
     }
-    ZkHostPool* host_pool = nullptr;     // host epilogues of batched commits (created on first use, min(hardware threads, 32) - 1 workers)
-    ZkHostPool* pool() {
-        if (!host_pool) {
-            const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-            host_pool = new (std::nothrow) ZkHostPool(std::min(hw, 32u) - 1);
-        }
-        return host_pool;
-    }
-    std::vector<zkhip_ctx*> gkr_lanes;   // child contexts of zkhip_gkr_prove_batch (a stream, scratch and transcript state each), destroyed with this one
+    std::vector<ZkCtxOwner> gkr_lanes;   // child contexts of zkhip_gkr_prove_batch (a stream, scratch and transcript state each), destroyed with this one
     // a lane replays a circuit's launch chain as a HIP graph (gkr.hip): its own copy of the layer values + the graph and the addresses it holds
     bool gkr_lane = false;
     zkhip_ctx* gkr_parent = nullptr;            // a lane's owner: the lanes' proofs that allocate or record a graph take turns under its gkr_warm_mu
     std::mutex gkr_warm_mu;
-    void* d_gkr_in = nullptr; size_t gkr_in_bytes = 0;
+    zk::GrowBuf gkr_in;
     struct GkrGraph {
-        void* exec = nullptr;                       // hipGraphExec_t
+        zk::GraphExec exec;
         const void *cir = nullptr, *aux = nullptr, *in = nullptr, *ws = nullptr, *pin = nullptr, *composed = nullptr;
         const void *warm_cir = nullptr, *warm_aux = nullptr, *warm_ws = nullptr;      // a plain proof of this circuit has run here (allocations made)
     } gkr_graph;
-    bool ws_lent = false;       // the workspace currently backs a split-phase prover state or commits in flight
+    // The workspace backs a split-phase prover state or commits in flight: every such borrower holds a ZkLoan of ws_loans for as long
+    // as it lives, and reserve_ws refuses while one is out.
+    ZkLoanDesk ws_loans;
     // commits in flight (zkhip_kzg_commit_begin / _end): two slots, each with a region of the workspace, a side stream and a
     // pinned result buffer of its own; `async_pend` is an MsmPending allocated by msm.hip
     static constexpr int ASYNC_SLOTS = 3;   // commits in flight (zkhip_kzg_commit_begin); measured with the pipeline filling and draining inside the timed region: 2 / 3 / 4 slots = 3.03 / 2.91 / 2.98 ms per 2^20-point commit
-    void* async_pend[ASYNC_SLOTS] = {};
+    std::unique_ptr<MsmPending, MsmPendingDelete> async_pend[ASYNC_SLOTS];
     size_t async_region = 0;
     // one cached set of small split-phase buffers, so that a steady stream of sharded proves never allocates
-    void* sc_small = nullptr; void* sc_stage = nullptr; size_t sc_stage_cap = 0; bool sc_lent = false;
-    void* d_small = nullptr;    // fixed small scratch, layout above
-    void* h_pinned = nullptr;
+    zk::DevMem sc_small, sc_stage; size_t sc_stage_cap = 0;
+    ZkLoanDesk sc_loans;        // held by the state that uses the cached pair
+    zk::DevMem d_small;         // fixed small scratch, layout above
+    zk::PinMem h_pinned;
     bool profiling = false;
     std::vector<ZkProfEvent> prof_events;
     size_t prof_used = 0;
@@ -298,14 +275,14 @@ struct zkhip_ctx {
     }
     // Host wait for a stream's work so far: polls an event for up to ~2 ms (a prover call is a few hundred
     // microseconds; a blocking wait's wake-up costs 10-20 us of idle GPU before the next call), then blocks.
-    hipEvent_t done_ev = nullptr;
+    zk::Event done_ev;
     int wait_stream(hipStream_t s = nullptr) {
         if (!s) s = stream;
-        if (!done_ev && hipEventCreateWithFlags(&done_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (hipEventRecord(done_ev, s) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (s != stream && hipStreamWaitEvent(stream, done_ev, 0) != hipSuccess) return ZKHIP_ERR_HIP;   // the caller's stream stays ordered behind it
+        if (zk::ensure_event(done_ev) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (hipEventRecord(done_ev.get(), s) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (s != stream && hipStreamWaitEvent(stream, done_ev.get(), 0) != hipSuccess) return ZKHIP_ERR_HIP;   // the caller's stream stays ordered behind it
         for (int spin = 0; spin < 200000; ++spin) {
-            const hipError_t e = hipEventQuery(done_ev);
+            const hipError_t e = hipEventQuery(done_ev.get());
             if (e == hipSuccess) return ZKHIP_OK;
             if (e != hipErrorNotReady) { last_hip = (int)e; return ZKHIP_ERR_HIP; }
         }
@@ -325,42 +302,40 @@ struct zkhip_ctx {
     }
     // result slots of the basic prover: pinned copies of [state .. round polynomials] + the event their copy completes at;
     // proof_pending[k] = n_vars of the proof in flight in slot k (0: free)
-    void* proof_pin[PROOF_SLOTS] = {};
-    hipEvent_t proof_ev[PROOF_SLOTS] = {};
+    zk::PinMem proof_pin[PROOF_SLOTS];
+    zk::Event proof_ev[PROOF_SLOTS];
     uint32_t proof_pending[PROOF_SLOTS] = {};
     int ensure_proof_slot(int k) {
-        if (!proof_ev[k] && hipEventCreateWithFlags(&proof_ev[k], hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (!proof_pin[k] && hipHostMalloc(&proof_pin[k], ((ZK_SMALL_ROUNDPOLYS - ZK_SMALL_STATE) + 8 * ZK_MAX_ROUNDS) * 8, hipHostMallocDefault) != hipSuccess)
-            return ZKHIP_ERR_NOMEM;
+        if (zk::ensure_event(proof_ev[k]) != hipSuccess) return ZKHIP_ERR_HIP;
+        if (!proof_pin[k] && zk::pin_alloc(proof_pin[k], ((ZK_SMALL_ROUNDPOLYS - ZK_SMALL_STATE) + 8 * ZK_MAX_ROUNDS) * 8) != hipSuccess) return ZKHIP_ERR_NOMEM;
         return ZKHIP_OK;
     }
-    uint64_t* small_u64(size_t off) { return (uint64_t*)d_small + off; }
-    uint64_t* pinned_u64(size_t off) { return (uint64_t*)h_pinned + off; }
-    // grow-only workspace; growth synchronises (never inside a steady-state timed loop)
-    int reserve_aux(size_t bytes) {
-        if (bytes <= aux_bytes) return ZKHIP_OK;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { last_hip = (int)e; return ZKHIP_ERR_HIP; }
-        if (d_aux) hipFree(d_aux);
-        d_aux = nullptr;
-        aux_bytes = 0;
-        e = hipMalloc(&d_aux, bytes);
-        if (e != hipSuccess) { last_hip = (int)e; return ZKHIP_ERR_NOMEM; }
-        aux_bytes = bytes;
-        return ZKHIP_OK;
+    // proofs still in flight write their results into the pinned slots from their lanes' streams, and no buffer may go away under a
+    // kernel: zkhip_ctx_destroy waits for the caller's stream and for every stream the context created
+    void drain_streams() {
+        hipStreamSynchronize(stream);
+        if (fold_stream) hipStreamSynchronize(fold_stream.get());
+        for (auto& L : lanes) { if (L.serial) hipStreamSynchronize(L.serial); if (L.fold) hipStreamSynchronize(L.fold); }
+        for (auto& s : side) if (s) hipStreamSynchronize(s.get());
+        if (guard_stream) hipStreamSynchronize(guard_stream.get());
     }
+    uint64_t* small_u64(size_t off) { return (uint64_t*)d_small.get() + off; }
+    uint64_t* pinned_u64(size_t off) { return (uint64_t*)h_pinned.get() + off; }
+    // grow-only workspaces; growth synchronises (never inside a steady-state timed loop)
+    int reserve_aux(size_t bytes) { return aux.reserve(bytes, {stream}, &last_hip); }
     int reserve_ws(size_t bytes) {
-        if (ws_lent) return ZKHIP_ERR_BUSY;     // a live split-phase session owns it: neither overwrite nor free it
-        if (bytes <= ws_bytes) return ZKHIP_OK;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { last_hip = (int)e; return ZKHIP_ERR_HIP; }
-        if (d_ws) hipFree(d_ws);
-        d_ws = nullptr;
-        ws_bytes = 0;
-        e = hipMalloc(&d_ws, bytes);
-        if (e != hipSuccess) { last_hip = (int)e; return ZKHIP_ERR_NOMEM; }
-        ws_bytes = bytes;
-        return ZKHIP_OK;
+        if (ws_loans.lent()) return ZKHIP_ERR_BUSY;     // a live split-phase session or a commit in flight uses it: neither overwrite nor free it
+        return ws.reserve(bytes, {stream}, &last_hip);
+    }
+    // host epilogues of batched commits (created on first use, min(hardware threads, 32) - 1 workers).  Declared last: its threads are
+    // joined before anything a job of theirs could reference goes away.
+    std::unique_ptr<ZkHostPool> host_pool;
+    ZkHostPool* pool() {
+        if (!host_pool) {
+            const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+            host_pool.reset(new (std::nothrow) ZkHostPool(std::min(hw, 32u) - 1));
+        }
+        return host_pool.get();
     }
 };
 
@@ -375,15 +350,15 @@ struct ProfScope {
         if (!on) return;
         if (c->prof_used == c->prof_events.size()) {
             ZkProfEvent ev;
-            hipEventCreate(&ev.start);
-            hipEventCreate(&ev.stop);
-            c->prof_events.push_back(ev);
+            (void)zk::ensure_event(ev.start, hipEventDefault);
+            (void)zk::ensure_event(ev.stop, hipEventDefault);
+            c->prof_events.push_back(std::move(ev));
         }
         idx = c->prof_used++;
-        hipEventRecord(c->prof_events[idx].start, s);
+        hipEventRecord(c->prof_events[idx].start.get(), s);
         c->prof_records.push_back({name, idx, bytes});
     }
     ~ProfScope() {
-        if (on) hipEventRecord(c->prof_events[idx].stop, s);
+        if (on) hipEventRecord(c->prof_events[idx].stop.get(), s);
     }
 };

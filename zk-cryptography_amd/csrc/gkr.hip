@@ -590,21 +590,22 @@ struct zkhip_circuit {
     zkhip_ctx* c = nullptr;
     uint32_t n_layers = 0;
     std::vector<LayerDev> layers;
-    void* d_mem = nullptr;
+    zk::DevMem d_mem;
 };
 
 extern "C" void zkhip_circuit_destroy(zkhip_circuit* cir) {
     if (!cir) return;
     if (cir->c) {       // the graphs the batch lanes recorded for this circuit hold its addresses (and another circuit may get this very address)
-        for (zkhip_ctx* lane : cir->c->gkr_lanes) {
+        for (auto& lane : cir->c->gkr_lanes) {
             zkhip_ctx::GkrGraph& gg = lane->gkr_graph;
             if (gg.cir == cir || gg.warm_cir == cir) {
-                if (gg.exec) { (void)hipStreamSynchronize(lane->stream); (void)hipGraphExecDestroy((hipGraphExec_t)gg.exec); }
+                if (gg.exec) (void)hipStreamSynchronize(lane->stream);
                 gg = zkhip_ctx::GkrGraph();
             }
         }
     }
-    if (cir->d_mem && cir->c && cir->c->activate() == ZKHIP_OK) (void)hipFree(cir->d_mem);
+    // the device arrays go with the circuit on its context's device; if that cannot be made current they are left to the runtime
+    if (cir->d_mem && !(cir->c && cir->c->activate() == ZKHIP_OK)) (void)cir->d_mem.release();
     delete cir;
 }
 
@@ -625,14 +626,12 @@ extern "C" int zkhip_circuit_create(zkhip_ctx* c, uint32_t n_layers, const size_
         total += 2 * al(4 * (w_len + 1 + ng)) + 2 * al(4 * ng) + al(ng);
         g_off += ng;
     }
-    zkhip_circuit* cir = new (std::nothrow) zkhip_circuit();
+    struct Destroy { void operator()(zkhip_circuit* p) const { zkhip_circuit_destroy(p); } };
+    std::unique_ptr<zkhip_circuit, Destroy> cir(new (std::nothrow) zkhip_circuit());
     if (!cir) return ZKHIP_ERR_NOMEM;
     cir->c = c;
     cir->n_layers = n_layers;
-    if (hipMalloc(&cir->d_mem, total ? total : 256) != hipSuccess) {
-        delete cir;
-        return ZKHIP_ERR_NOMEM;
-    }
+    if (zk::dev_alloc(cir->d_mem, total ? total : 256) != hipSuccess) return ZKHIP_ERR_NOMEM;
     // stage everything in one host buffer, one upload
     std::vector<char> host(total);
     std::vector<uint32_t> csr;
@@ -644,7 +643,7 @@ extern "C" int zkhip_circuit_create(zkhip_ctx* c, uint32_t n_layers, const size_
         ld.n_gates = ng;
         ld.w_len = w_len;
         ld.bad_label = bad[l] != 0;
-        char* base = (char*)cir->d_mem;
+        char* base = (char*)cir->d_mem.get();
         if (!bad[l]) {
             group_gates(h_in0 + g_off, ng, w_len, csr);
             std::memcpy(host.data() + off, csr.data(), 4 * csr.size());
@@ -664,12 +663,10 @@ extern "C" int zkhip_circuit_create(zkhip_ctx* c, uint32_t n_layers, const size_
         cir->layers.push_back(ld);
         g_off += ng;
     }
-    if (total && (hipMemcpyAsync(cir->d_mem, host.data(), total, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                  hipStreamSynchronize(c->stream) != hipSuccess)) {
-        zkhip_circuit_destroy(cir);
+    if (total && (hipMemcpyAsync(cir->d_mem.get(), host.data(), total, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                  hipStreamSynchronize(c->stream) != hipSuccess))
         return ZKHIP_ERR_HIP;
-    }
-    *out = cir;
+    *out = cir.release();
     return ZKHIP_OK;
 }
 
@@ -700,17 +697,16 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
     if (lane) {
         size_t total = 0;
         for (uint32_t k = 0; k <= n_layers; ++k) total += h_layer_len[k];
-        if (32 * total > c->gkr_in_bytes) {
-            ZK_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_gkr_in) (void)hipFree(c->d_gkr_in);
-            c->d_gkr_in = nullptr; c->gkr_in_bytes = 0;
-            if (hipMalloc(&c->d_gkr_in, 32 * total) != hipSuccess) return ZKHIP_ERR_NOMEM;
-            c->gkr_in_bytes = 32 * total;
+        {
+            int hip = 0;
+            const int rc = c->gkr_in.reserve(32 * total, {c->stream}, &hip);
+            if (rc == ZKHIP_ERR_HIP) c->last_hip = hip;
+            ZK_TRY(rc);
         }
         staged.resize(n_layers + 1);
         size_t off = 0;
         for (uint32_t k = 0; k <= n_layers; ++k) {
-            uint64_t* dst = (uint64_t*)c->d_gkr_in + 4 * off;
+            uint64_t* dst = (uint64_t*)c->gkr_in.ptr + 4 * off;
             ZK_HIP(c, hipMemcpyAsync(dst, h_layer_ptrs[k], 32 * h_layer_len[k], hipMemcpyDeviceToDevice, c->stream));
             staged[k] = dst;
             off += h_layer_len[k];
@@ -728,7 +724,7 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
     const size_t dt_bytes = al(sizeof(zk::OuterDev)) + 256 + al(32 * ((size_t)n_layers + 1)) + 2 * al(32 * (size_t)n_layers) +
                             al(8 * (size_t)(4 + 64) * ZK_MAX_ROUNDS * n_layers);
     ZK_TRY(c->reserve_aux(o_eqh + al(32 * 2 * (size_t)zk::GKR_EQ_HALVES) + dt_bytes));
-    char* aux = (char*)c->d_aux;
+    char* aux = (char*)c->aux.ptr;
     uint64_t* d_w0 = (uint64_t*)(aux + o_w0);
     LayerScratch sc;
     sc.ha0 = (uint64_t*)(aux + o_tab); sc.ha1 = (uint64_t*)(aux + o_tab + tb); sc.hm = (uint64_t*)(aux + o_tab + 2 * tb);
@@ -815,7 +811,7 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
         // ---- the whole proof back in ONE copy: outer state (its error word) | next | sums | w_b | w_c | arena are neighbours on the device
         const size_t pin_bytes = o_arena + arena_bytes - o_outer;
         ZK_TRY(c->reserve_msm_pin(0, pin_bytes));
-        char* pin0 = (char*)c->msm_pin[0];
+        char* pin0 = (char*)c->msm_pin[0].ptr;
         auto enqueue_chain = [&](bool replayable) -> int {
             bool rows1_done = false;
             for (uint32_t li = 1; li <= n_layers; ++li) {
@@ -831,37 +827,38 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
         };
         // the graph of this (circuit, lane): valid while every buffer the chain touches is where it was when it was recorded
         zkhip_ctx::GkrGraph& gg = c->gkr_graph;
-        const bool same = lane && gg.exec && gg.cir == cir && gg.aux == c->d_aux && gg.in == c->d_gkr_in && gg.ws == c->d_ws && gg.pin == c->msm_pin[0] &&
-                          gg.composed == c->d_composed;
-        if (lane && gg.exec && !same) { (void)hipGraphExecDestroy((hipGraphExec_t)gg.exec); gg = zkhip_ctx::GkrGraph(); }
+        const bool same = lane && gg.exec && gg.cir == cir && gg.aux == c->aux.ptr && gg.in == c->gkr_in.ptr && gg.ws == c->ws.ptr && gg.pin == c->msm_pin[0].ptr &&
+                          gg.composed == c->d_composed.get();
+        if (lane && gg.exec && !same) gg = zkhip_ctx::GkrGraph();
         if (lane && gg.exec) {
-            ZK_HIP(c, hipGraphLaunch((hipGraphExec_t)gg.exec, c->stream));
-        } else if (lane && gg.warm_cir == cir && gg.warm_aux == c->d_aux && gg.warm_ws == c->d_ws) {
+            ZK_HIP(c, hipGraphLaunch(gg.exec.get(), c->stream));
+        } else if (lane && gg.warm_cir == cir && gg.warm_aux == c->aux.ptr && gg.warm_ws == c->ws.ptr) {
             // the second proof of this circuit on the lane (the first one, launched plainly, made every allocation): record, instantiate, launch
             // Relaxed mode: the recorded region is kernel launches and one copy; the OTHER lanes' threads allocate, free and synchronise at the
             // same time (a capture in the stricter modes was invalidated by them: hipErrorStreamCaptureInvalidated, tools/stress_parity.py)
-            hipGraph_t graph = nullptr;
+            hipGraph_t captured = nullptr;
             ZK_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
             const int crc = enqueue_chain(true);
-            const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
+            const hipError_t ee = hipStreamEndCapture(c->stream, &captured);
+            zk::Graph graph(captured);                        // only instantiated from: gone at the end of this block
             if (crc != ZKHIP_OK || ee != hipSuccess || !graph) {
                 // not recordable here (whatever the reason): nothing was launched; forget the attempt and launch this proof plainly -- a real
                 // error (a shape, a launch failure) comes back from there
-                if (graph) (void)hipGraphDestroy(graph);
+                graph.reset();
                 (void)hipGetLastError();
                 gg.warm_cir = nullptr;
                 ZK_TRY(enqueue_chain(true));
             } else {
                 hipGraphExec_t exec = nullptr;
-                const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
+                const hipError_t ie = hipGraphInstantiate(&exec, graph.get(), nullptr, nullptr, 0);
+                graph.reset();
                 if (ie != hipSuccess || !exec) { c->last_hip = (int)ie; return ZKHIP_ERR_HIP; }
-                gg.exec = exec; gg.cir = cir; gg.aux = c->d_aux; gg.in = c->d_gkr_in; gg.ws = c->d_ws; gg.pin = c->msm_pin[0]; gg.composed = c->d_composed;
+                gg.exec.reset(exec); gg.cir = cir; gg.aux = c->aux.ptr; gg.in = c->gkr_in.ptr; gg.ws = c->ws.ptr; gg.pin = c->msm_pin[0].ptr; gg.composed = c->d_composed.get();
                 ZK_HIP(c, hipGraphLaunch(exec, c->stream));
             }
         } else {
             ZK_TRY(enqueue_chain(lane));      // (a lane's plain chain is the replayable one too: the same kernels, the same bits)
-            if (lane) { gg.warm_cir = cir; gg.warm_aux = c->d_aux; gg.warm_ws = c->d_ws; }
+            if (lane) { gg.warm_cir = cir; gg.warm_aux = c->aux.ptr; gg.warm_ws = c->ws.ptr; }
         }
         ZK_HIP(c, hipStreamSynchronize(c->stream));
         // a hasher gave up waiting for a round's items (OuterDev::error = 1 + round).  The hasher is the LAST workgroup of a closing launch and
@@ -929,36 +926,35 @@ extern "C" int zkhip_gkr_prove_batch(zkhip_circuit* cir, uint32_t n_proofs, uint
     const uint32_t nl = cir->n_layers, stride = 2 * nl;
     const uint32_t lanes = std::min<uint32_t>(n_proofs, std::min<uint32_t>(max_lanes ? max_lanes : 8u, GKR_BATCH_LANES));
     while (c->gkr_lanes.size() < lanes) {
-        zkhip_ctx* lc = nullptr;
-        ZK_TRY(zkhip_ctx_create(&lc, c->device, nullptr));
+        zkhip_ctx* created = nullptr;
+        ZK_TRY(zkhip_ctx_create(&created, c->device, nullptr));
+        ZkCtxOwner lc(created);                                   // pushed on success; an early exit destroys it like any context
         // The lanes' streams are spread over the three stream priorities: the runtime keeps a pool of hardware queues PER PRIORITY (four each
         // by default), and two streams that share a hardware queue take turns in it at a cost -- measured on depth-8 proofs: a queue with
         // one chain is 86 % busy, a queue with two 51 % (profiles/r06/e_gkr_batch_kernel_stats.txt).  All lanes do the same work, so
         // what the priorities order is only who goes first.
-        hipStream_t s = nullptr;
         int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { zkhip_ctx_destroy(lc); return ZKHIP_ERR_HIP; }
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return ZKHIP_ERR_HIP;
         static const bool spread = [] { const char* e = std::getenv("ZKHIP_GKR_LANE_PRIO"); return !e || std::atoi(e) != 0; }();
         const int span = least - greatest + 1;                    // (numerically lower = higher priority)
         const int prio = spread && span > 1 ? greatest + (int)(c->gkr_lanes.size() % (size_t)span) : 0;
-        if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio) != hipSuccess) { zkhip_ctx_destroy(lc); return ZKHIP_ERR_HIP; }
-        lc->stream = s;
-        lc->own_stream = true;
+        if (zk::ensure_stream(lc->owned_stream, &prio) != hipSuccess) return ZKHIP_ERR_HIP;
+        lc->stream = lc->owned_stream.get();
         lc->gkr_lane = true;
         lc->gkr_parent = c;
-        c->gkr_lanes.push_back(lc);
+        c->gkr_lanes.push_back(std::move(lc));
     }
     // the lanes start behind what the caller's stream holds now (the layer values may still be on their way there)
-    if (!c->done_ev && hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
-    ZK_HIP(c, hipEventRecord(c->done_ev, c->stream));
-    for (uint32_t l = 0; l < lanes; ++l) ZK_HIP(c, hipStreamWaitEvent(c->gkr_lanes[l]->stream, c->done_ev, 0));
+    if (zk::ensure_event(c->done_ev) != hipSuccess) return ZKHIP_ERR_HIP;
+    ZK_HIP(c, hipEventRecord(c->done_ev.get(), c->stream));
+    for (uint32_t l = 0; l < lanes; ++l) ZK_HIP(c, hipStreamWaitEvent(c->gkr_lanes[l]->stream, c->done_ev.get(), 0));
     std::vector<int> rcs(n_proofs, ZKHIP_OK);
     const size_t o_sums = 4 * (size_t)nl, o_rounds = nl, o_lens = (size_t)nl * stride, o_polys = (size_t)nl * stride * GKR_MONO * 8, o_ch = (size_t)nl * stride * 4;
     // proofs are handed out one by one: a lane whose hardware queue gets less of the command processor (the lanes' busy shares in a kernel
     // trace range from 35 to 75 %, and differently from process to process) takes fewer of them instead of holding the call up
     std::atomic<uint32_t> next_proof{0};
     auto lane_work = [&](unsigned l) {
-        zkhip_ctx* lc = c->gkr_lanes[l];
+        zkhip_ctx* lc = c->gkr_lanes[l].get();
         for (uint32_t b = next_proof.fetch_add(1); b < n_proofs; b = next_proof.fetch_add(1)) {
             rcs[b] = lc->activate();
             if (rcs[b] != ZKHIP_OK) continue;
@@ -1043,7 +1039,7 @@ extern "C" int zkhip_gkr_layer_tables_sharded(zkhip_circuit* cir, uint32_t layer
     if (ld.bad_label) return ZKHIP_ERR_INDEX;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_aux(tables_scratch_bytes(ld.n_gates, w_len)));
-    const TablesScratch ts = carve_tables_scratch((char*)c->d_aux, ld.n_gates, w_len);
+    const TablesScratch ts = carve_tables_scratch((char*)c->aux.ptr, ld.n_gates, w_len);
     ZK_TRY(layer_tables_enqueue(cir, layer, d_w, w_len, h_rb, h_rc, h_alpha, h_beta, phase, world, rank, d_out, ts));
     if (phase == 0) return ZKHIP_OK;
     ZK_HIP(c, hipMemcpyAsync(c->pinned_u64(ZK_PIN_RES), ts.evals, 32, hipMemcpyDeviceToHost, c->stream));
@@ -1083,7 +1079,7 @@ extern "C" int zkhip_gkr_prove_sharded(zkhip_circuit* cir, zkhip_comm* comm, con
     }
     const size_t tb = al256(32 * max_rows), o_scr = 256, o_tab = o_scr + al256(max_scratch);
     ZK_TRY(c->reserve_aux(o_tab + 8 * tb));
-    char* aux = (char*)c->d_aux;
+    char* aux = (char*)c->aux.ptr;
     uint64_t* d_w0 = (uint64_t*)aux;
     uint64_t* tab[8];
     for (int q = 0; q < 8; ++q) tab[q] = (uint64_t*)(aux + o_tab + (size_t)q * tb);

@@ -25,6 +25,21 @@ struct ZkMcExtra {
 #include <mutex>
 #include <thread>
 #include <vector>
+// A loan of something its owner must not replace while it is out (the context's workspace, its cached split-phase buffers).  The
+// owner keeps a ZkLoanDesk and asks lent(); every borrower holds a ZkLoan for as long as it uses the thing: the loan is returned
+// when the borrower is destroyed, overwritten or calls end(), so no exit of a session has to remember a flag.
+struct ZkLoanDesk { int out = 0; bool lent() const { return out > 0; } };      // out: loans not yet returned
+class ZkLoan {
+    ZkLoanDesk* desk_ = nullptr;
+public:
+    ZkLoan() = default;
+    explicit ZkLoan(ZkLoanDesk& desk) : desk_(&desk) { ++desk.out; }
+    ZkLoan(ZkLoan&& o) noexcept : desk_(o.desk_) { o.desk_ = nullptr; }
+    ZkLoan& operator=(ZkLoan&& o) noexcept { if (this != &o) { end(); desk_ = o.desk_; o.desk_ = nullptr; } return *this; }
+    ~ZkLoan() { end(); }
+    void end() { if (desk_) { --desk_->out; desk_ = nullptr; } }
+    explicit operator bool() const { return desk_ != nullptr; }
+};
 // A few host threads kept for the life of a context: the per-problem host epilogues of a batched commit (~0.25 ms of serial point
 // arithmetic each, twenty of them behind MultilinearKZG::open) start within microseconds, where twenty std::thread constructions cost as much
 // as the work.  run(n, fn) calls fn(0) .. fn(n - 1), each exactly once, on the workers and the calling thread, and returns when all are done.

@@ -65,7 +65,9 @@ struct MsmPending {
     MsmProblems pr;
     size_t n_out = 0;
     int slot = 0;
+    ZkLoan ws_loan;     // a commit in flight (zkhip_kzg_commit_begin) holds the workspace until it has ended
 };
+void MsmPendingDelete::operator()(MsmPending* p) const { delete p; }
 static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t* d_points_inf, const uint64_t* d_scalars, size_t n,
                        const MsmProblems& pr_in, const uint32_t* d_table, size_t table_stride, size_t ws_off, int slot, MsmPending* pend,
                        size_t* ws_used) {
@@ -108,8 +110,10 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
     const size_t total = o_part + al(slots_cap * 256);
     if (ws_used) *ws_used = total;
     if (!pend) return ZKHIP_OK;                     // size query only
-    ZK_TRY(c->reserve_ws(ws_off + total));
-    char* ws = (char*)c->d_ws + ws_off;
+    // a commit in flight lives in a region of the workspace its caller reserved before it took the loan: nothing to reserve, it must fit
+    if (pend->ws_loan) { if (ws_off + total > c->ws.bytes) return ZKHIP_ERR_BUSY; }
+    else ZK_TRY(c->reserve_ws(ws_off + total));
+    char* ws = (char*)c->ws.ptr + ws_off;
     uint32_t* counts = (uint32_t*)(ws + o_counts);
     uint32_t* offsets = (uint32_t*)(ws + o_offsets);
     uint32_t* sorted = (uint32_t*)(ws + o_sorted);
@@ -134,9 +138,9 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
         const size_t b_part = al(geo.part_set.size() * 2), b_rcwg = al(geo.rcwg_set.size() * 2), b_term = al(geo.termwg_set.size() * 2);
         const size_t bytes = b_wins + b_sets + b_part + b_rcwg + b_term;
         ZK_TRY(c->reserve_msm_tab(slot, bytes));
-        char* dev = (char*)c->msm_tab_dev[slot];
-        if (c->msm_tab_geo[slot].get() != (const void*)geo_p.get()) {
-            char* pin = (char*)c->msm_tab_pin[slot];
+        char* dev = (char*)c->msm_tab_dev[slot].ptr;
+        if (c->msm_tab_geo[slot] != geo_p) {
+            char* pin = (char*)c->msm_tab_pin[slot].ptr;
             // the staging buffer may still feed the upload of the slot's previous commit only if that commit has not been waited for;
             // every caller ends (msm_finish / stream synchronize) a slot's commit before it enqueues the next one there
             std::memcpy(pin, geo.wins.data(), geo.wins.size() * sizeof(MsmWin));
@@ -206,8 +210,8 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
     }
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(c->reserve_msm_pin(slot, n_out * 192));
-    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[slot], terms, n_out * 192, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipEventRecord(c->msm_ev[slot], c->stream));
+    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[slot].ptr, terms, n_out * 192, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipEventRecord(c->msm_ev[slot].get(), c->stream));
     pend->geo = geo_p;
     pend->pr = pr;
     pend->n_out = n_out;
@@ -215,10 +219,10 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
     return ZKHIP_OK;
 }
 static int msm_finish(zkhip_ctx* c, const MsmPending& pend, uint64_t* h_out_xy, uint8_t* h_out_inf) {
-    ZK_HIP(c, hipEventSynchronize(c->msm_ev[pend.slot]));
+    ZK_HIP(c, hipEventSynchronize(c->msm_ev[pend.slot].get()));
     const MsmGeometry& geo = *pend.geo;
     const MsmProblems& pr = pend.pr;
-    const uint64_t* h_terms = (const uint64_t*)c->msm_pin[pend.slot];
+    const uint64_t* h_terms = (const uint64_t*)c->msm_pin[pend.slot].ptr;
     // host epilogue, per problem: sum over its (set, term) points of 2^exp * point
     auto finish = [&](uint32_t j) {
         std::vector<zkhost::Xyzz> pts;
@@ -394,51 +398,42 @@ extern "C" int zkhip_kzg_commit_begin(zkhip_ctx* c, const uint64_t* d_points_xy,
     ZK_TRY(msm_enqueue(c, nullptr, nullptr, nullptr, n, one, (const uint32_t*)d_table, n_points, 0, 0, nullptr, &used));
     used = (used + 4095) & ~(size_t)4095;
     if (!any) {
-        if (c->ws_lent) return ZKHIP_ERR_BUSY;
+        if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
         ZK_TRY(c->reserve_ws(zkhip_ctx::ASYNC_SLOTS * used));
-        c->async_region = std::max(used, c->ws_bytes / zkhip_ctx::ASYNC_SLOTS & ~(size_t)4095);
+        c->async_region = std::max(used, c->ws.bytes / zkhip_ctx::ASYNC_SLOTS & ~(size_t)4095);
     } else if (used > c->async_region) {
         return ZKHIP_ERR_BUSY;            // a larger commit than the one in flight: end that one first
     }
     ZK_TRY(c->ensure_side_streams());
-    MsmPending* pend = new (std::nothrow) MsmPending();
+    std::unique_ptr<MsmPending, MsmPendingDelete> pend(new (std::nothrow) MsmPending());
     if (!pend) return ZKHIP_ERR_NOMEM;
+    pend->ws_loan = ZkLoan(c->ws_loans);      // the workspace stays lent until the last commit in flight has ended
     hipStream_t const main_stream = c->stream;
     int rc = ZKHIP_OK;
-    if (hipEventRecord(c->fork_ev, main_stream) != hipSuccess || hipStreamWaitEvent(c->side[slot], c->fork_ev, 0) != hipSuccess) rc = ZKHIP_ERR_HIP;
+    if (hipEventRecord(c->fork_ev.get(), main_stream) != hipSuccess || hipStreamWaitEvent(c->side[slot].get(), c->fork_ev.get(), 0) != hipSuccess) rc = ZKHIP_ERR_HIP;
     if (rc == ZKHIP_OK) {
-        const bool lent = c->ws_lent;
-        c->ws_lent = false;               // the reservation above covers both regions; msm_enqueue's own reserve is a no-op
-        c->stream = c->side[slot];
+        c->stream = c->side[slot].get();
         rc = msm_enqueue(c, d_points_xy, d_points_inf, d_scalars, n, one, (const uint32_t*)d_table, n_points, (size_t)slot * c->async_region, slot,
-                         pend, nullptr);
+                         pend.get(), nullptr);
         c->stream = main_stream;
-        c->ws_lent = lent;
     }
     if (rc != ZKHIP_OK) {
         // a partially enqueued commit may have kernels running on the side stream: drain them before the slot, its workspace
         // region and its pinned buffer are handed out again
-        hipStreamSynchronize(c->side[slot]);
-        delete pend;
+        hipStreamSynchronize(c->side[slot].get());
         return rc;
     }
-    c->async_pend[slot] = pend;
-    c->ws_lent = true;                    // until the last commit in flight has ended
+    c->async_pend[slot] = std::move(pend);
     *ticket = (uint32_t)slot;
     return ZKHIP_OK;
 }
 extern "C" int zkhip_kzg_commit_end(zkhip_ctx* c, uint32_t ticket, uint64_t* h_out_xy, uint8_t* h_out_inf) {
     if (!c || ticket >= (uint32_t)zkhip_ctx::ASYNC_SLOTS || !c->async_pend[ticket]) return ZKHIP_ERR_ARG;
-    MsmPending* pend = (MsmPending*)c->async_pend[ticket];
+    const std::unique_ptr<MsmPending, MsmPendingDelete> pend = std::move(c->async_pend[ticket]);     // ended (and its loan returned) on every exit
     int rc = c->activate();
     if (rc == ZKHIP_OK && h_out_xy && h_out_inf) rc = msm_finish(c, *pend, h_out_xy, h_out_inf);
-    else if (hipStreamSynchronize(c->side[ticket]) != hipSuccess) rc = ZKHIP_ERR_HIP;            // abandoned: just drain it
-    if (hipStreamWaitEvent(c->stream, c->msm_ev[ticket], 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // workspace reuse stays ordered
-    delete pend;
-    c->async_pend[ticket] = nullptr;
-    bool any = false;
-    for (int k = 0; k < zkhip_ctx::ASYNC_SLOTS; ++k) any = any || c->async_pend[k];
-    if (!any) c->ws_lent = false;
+    else if (hipStreamSynchronize(c->side[ticket].get()) != hipSuccess) rc = ZKHIP_ERR_HIP;            // abandoned: just drain it
+    if (hipStreamWaitEvent(c->stream, c->msm_ev[ticket].get(), 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // workspace reuse stays ordered
     return rc;
 }
 
@@ -456,22 +451,18 @@ extern "C" int zkhip_srs_fingerprint(zkhip_ctx* c, const uint64_t* d_points_xy, 
     if (!c || !d_points_xy || !h_out) return ZKHIP_ERR_ARG;
     if (n_points == 0) { std::memset(h_out, 0, 52 * 8); return ZKHIP_OK; }
     ZK_TRY(c->activate());
-    if (!c->d_fingerprint) ZK_HIP(c, hipMalloc(&c->d_fingerprint, 512));      // a buffer of its own: commits in flight hold the workspace
-    if (!c->guard_stream) {
-        // a stream of the highest priority: with commits in flight the one-wave kernel takes the next slot that frees instead of queueing
-        // behind the thousands of workgroups of an accumulate pass (109 us per call on the caller's stream, rocprofv3 of the bench's in-flight leg)
-        int least = 0, greatest = 0;
-        ZK_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        ZK_HIP(c, hipStreamCreateWithPriority(&c->guard_stream, hipStreamNonBlocking, greatest));
-        ZK_HIP(c, hipEventCreateWithFlags(&c->guard_ev, hipEventDisableTiming));
-    }
+    if (!c->d_fingerprint) ZK_HIP(c, dev_alloc(c->d_fingerprint, 512));      // a buffer of its own: commits in flight hold the workspace
+    // a stream of the highest priority: with commits in flight the one-wave kernel takes the next slot that frees instead of queueing
+    // behind the thousands of workgroups of an accumulate pass (109 us per call on the caller's stream, rocprofv3 of the bench's in-flight leg)
+    ZK_HIP(c, ensure_stream(c->guard_stream, Prio::High));
+    ZK_HIP(c, ensure_event(c->guard_ev));
     uint64_t* pin = c->pinned_u64(ZK_PIN_PTS);      // (evaluation points' staging area: no prover runs during this call)
     static_assert(ZK_PIN_PROOF - ZK_PIN_PTS >= 52, "staging area too small");
-    ZK_HIP(c, hipEventRecord(c->guard_ev, c->stream));                         // behind whatever the caller's stream still does to the SRS
-    ZK_HIP(c, hipStreamWaitEvent(c->guard_stream, c->guard_ev, 0));
-    hipLaunchKernelGGL(srs_fingerprint_kernel, dim3(1), dim3(64), 0, c->guard_stream, d_points_xy, d_points_inf, n_points, (uint64_t*)c->d_fingerprint);
-    ZK_HIP(c, hipMemcpyAsync(pin, c->d_fingerprint, 52 * 8, hipMemcpyDeviceToHost, c->guard_stream));
-    ZK_HIP(c, hipStreamSynchronize(c->guard_stream));
+    ZK_HIP(c, hipEventRecord(c->guard_ev.get(), c->stream));                         // behind whatever the caller's stream still does to the SRS
+    ZK_HIP(c, hipStreamWaitEvent(c->guard_stream.get(), c->guard_ev.get(), 0));
+    hipLaunchKernelGGL(srs_fingerprint_kernel, dim3(1), dim3(64), 0, c->guard_stream.get(), d_points_xy, d_points_inf, n_points, (uint64_t*)c->d_fingerprint.get());
+    ZK_HIP(c, hipMemcpyAsync(pin, c->d_fingerprint.get(), 52 * 8, hipMemcpyDeviceToHost, c->guard_stream.get()));
+    ZK_HIP(c, hipStreamSynchronize(c->guard_stream.get()));
     std::memcpy(h_out, pin, 52 * 8);
     return ZKHIP_OK;
 }
@@ -489,7 +480,7 @@ static int build_shift_table(zkhip_ctx* c, const uint64_t* d_points_xy, const ui
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_xyzz = 0, o_aff = al(192 * n), o_inf = o_aff + al(96 * n);
     ZK_TRY(c->reserve_ws(o_inf + al(n)));
-    char* ws = (char*)c->d_ws;
+    char* ws = (char*)c->ws.ptr;
     const unsigned grid = (unsigned)((n + MSM_BLOCK - 1) / MSM_BLOCK);
     hipLaunchKernelGGL(msm_convert_points_kernel, dim3(std::min<unsigned>(grid, 256 * 8)), dim3(MSM_BLOCK), 0, c->stream, d_points_xy, n, table);
     if (d_points_inf) {   // entries of points at infinity: all-zero coordinates (their scalars are skipped by the sort anyway)
@@ -562,7 +553,7 @@ extern "C" int zkhip_srs_level_tables(zkhip_ctx* c, const uint64_t* d_folded_xy,
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t o_pts = 0, o_xyzz = al(128 * (size_t)a.total_points), o_aff = o_xyzz + al(192 * entry), o_inf = o_aff + al(96 * entry);
         ZK_TRY(c->reserve_ws(o_inf + al(entry)));
-        char* ws = (char*)c->d_ws;
+        char* ws = (char*)c->ws.ptr;
         uint32_t* d_pts = (uint32_t*)(ws + o_pts);
         hipLaunchKernelGGL(msm_convert_points_kernel, dim3((a.total_points + MSM_BLOCK - 1) / MSM_BLOCK), dim3(MSM_BLOCK), 0, c->stream, d_folded_xy + 12 * off,
                            (size_t)a.total_points, d_pts);
@@ -618,8 +609,8 @@ static int msm_small_batch(zkhip_ctx* c, const uint32_t* d_table, const uint8_t*
     a.total_slots = a.slot_first[nprob];
     const size_t part_bytes = (size_t)a.planes * a.total_slots * 256, terms_bytes = (size_t)nprob * a.planes * 192;
     ZK_TRY(c->reserve_ws(part_bytes + 256 + terms_bytes));
-    a.partials = (uint32_t*)c->d_ws;
-    a.terms = (uint64_t*)((char*)c->d_ws + ((part_bytes + 255) & ~(size_t)255));
+    a.partials = (uint32_t*)c->ws.ptr;
+    a.terms = (uint64_t*)((char*)c->ws.ptr + ((part_bytes + 255) & ~(size_t)255));
     {
         ProfScope ps(c, "msm_small", 128.0 * (double)total_pairs / std::max<uint32_t>(1, a.W[0]));
         hipLaunchKernelGGL(msm_small_planes_kernel, dim3(a.total_slots, a.planes), dim3(64), 0, c->stream, a);
@@ -627,9 +618,9 @@ static int msm_small_batch(zkhip_ctx* c, const uint32_t* d_table, const uint8_t*
     }
     ZK_HIP(c, hipGetLastError());
     ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
-    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0], a.terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, a.terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
     ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const char* pin = (const char*)c->msm_pin[0];
+    const char* pin = (const char*)c->msm_pin[0].ptr;
     auto finish = [&](uint32_t j) {                                  // the weighted sum of a problem's plane sums: <= 20 doublings
         std::vector<zkhost::Xyzz> pts(a.hi[j]);
         std::vector<uint32_t> exps(a.hi[j]);
@@ -750,7 +741,7 @@ extern "C" int zkhip_srs_fold_levels(zkhip_ctx* c, const uint64_t* d_points_xy, 
     if (n_points < 2 || !is_pow2(n_points)) return ZKHIP_ERR_SHAPE;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws((n_points - 1) * 192));
-    return fold_srs_levels(c, d_points_xy, d_points_inf, n_points, (uint64_t*)c->d_ws, d_out_xy, d_out_inf);
+    return fold_srs_levels(c, d_points_xy, d_points_inf, n_points, (uint64_t*)c->ws.ptr, d_out_xy, d_out_inf);
 }
 
 extern "C" int zkhip_kzg_open(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uint64_t* h_points, size_t n_eval_points,
@@ -787,11 +778,11 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     const size_t o_fxy = o_pong + al((n / 4 + 1) * 32), o_finf = o_fxy + al((n - 1) * 96);
     const bool own_fold = d_folded_xy == nullptr;
     ZK_TRY(c->reserve_aux(own_fold ? o_finf + al(n - 1) : o_fxy));
-    char* aux = (char*)c->d_aux;
+    char* aux = (char*)c->aux.ptr;
     if (own_fold) {
         ZK_TRY(c->reserve_ws((n - 1) * 192));
         ProfScope ps(c, "open_fold_srs", 0.0);
-        ZK_TRY(fold_srs_levels(c, d_points_xy, d_points_inf, n, (uint64_t*)c->d_ws, (uint64_t*)(aux + o_fxy), (uint8_t*)(aux + o_finf)));
+        ZK_TRY(fold_srs_levels(c, d_points_xy, d_points_inf, n, (uint64_t*)c->ws.ptr, (uint64_t*)(aux + o_fxy), (uint8_t*)(aux + o_finf)));
         d_folded_xy = (const uint64_t*)(aux + o_fxy);
         d_folded_inf = (const uint8_t*)(aux + o_finf);
     }
@@ -893,7 +884,7 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
         ZK_TRY(c->reserve_ws(region_off[NSLOT] + used));
     }
     ZK_TRY(c->ensure_side_streams());
-    ZK_HIP(c, hipEventRecord(c->fork_ev, c->stream));
+    ZK_HIP(c, hipEventRecord(c->fork_ev.get(), c->stream));
     MsmPending pend[zkhip_ctx::MSM_SLOTS];
     int pend_round[zkhip_ctx::MSM_SLOTS];
     for (int k = 0; k < zkhip_ctx::MSM_SLOTS; ++k) pend_round[k] = -1;
@@ -907,8 +898,8 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     int rc = ZKHIP_OK;
     if (batch.n) {
         // on the caller's stream (nothing else runs there meanwhile); pipelines: on a side stream, and FIRST -- its chain of passes is the longest
-        hipStream_t on = pipelines ? c->side[sl_batch] : main_stream;
-        if (on != main_stream && hipStreamWaitEvent(on, c->fork_ev, 0) != hipSuccess) rc = ZKHIP_ERR_HIP;
+        hipStream_t on = pipelines ? c->side[sl_batch].get() : main_stream;
+        if (on != main_stream && hipStreamWaitEvent(on, c->fork_ev.get(), 0) != hipSuccess) rc = ZKHIP_ERR_HIP;
         if (rc == ZKHIP_OK) {
             c->stream = on;                                // msm_enqueue launches on the context's stream
             rc = msm_enqueue(c, d_folded_xy + 12 * batch_first_off, d_folded_inf + batch_first_off, d_q + 4 * batch_first_off,
@@ -923,8 +914,8 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
         MsmProblems one = {};
         one.n = 1;
         one.off[1] = (uint32_t)large[j].h;
-        if (hipStreamWaitEvent(c->side[sl], c->fork_ev, 0) != hipSuccess) { rc = ZKHIP_ERR_HIP; break; }
-        c->stream = c->side[sl];
+        if (hipStreamWaitEvent(c->side[sl].get(), c->fork_ev.get(), 0) != hipSuccess) { rc = ZKHIP_ERR_HIP; break; }
+        c->stream = c->side[sl].get();
         rc = msm_enqueue(c, d_folded_xy + 12 * large[j].off, d_folded_inf + large[j].off, d_q + 4 * large[j].off, large[j].h, one, nullptr, 0,
                          region_off[sl], sl, &pend[sl], nullptr);
         c->stream = main_stream;
@@ -937,7 +928,7 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
         for (int k = 0; k < zkhip_ctx::MSM_SLOTS; ++k) {
             if (pend_round[k] < 0) continue;
             ++left;
-            if (ready < 0 && hipEventQuery(c->msm_ev[k]) != hipErrorNotReady) ready = k;
+            if (ready < 0 && hipEventQuery(c->msm_ev[k].get()) != hipErrorNotReady) ready = k;
         }
         if (!left) break;
         if (ready < 0) { std::this_thread::yield(); continue; }
@@ -945,7 +936,7 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
         if (rc == ZKHIP_OK) rc = r2;
     }
     if (rc != ZKHIP_OK) {
-        for (int k = 0; k < zkhip_ctx::MSM_SLOTS; ++k) hipStreamSynchronize(c->side[k]);
+        for (int k = 0; k < zkhip_ctx::MSM_SLOTS; ++k) hipStreamSynchronize(c->side[k].get());
         return rc;
     }
     // the last remainder is poly(z): `evaluation`, and what the reference checks it against (:84-86)
@@ -977,7 +968,7 @@ extern "C" int zkhip_univariate_kzg_open(zkhip_ctx* c, const uint64_t* d_coeffs,
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_q = 0, o_vals = al(32 * n), o_carry = o_vals + al(32 * (size_t)n_blocks), o_eval = o_carry + al(32 * (size_t)n_blocks);
     ZK_TRY(c->reserve_aux(o_eval + 256));
-    char* aux = (char*)c->d_aux;
+    char* aux = (char*)c->aux.ptr;
     uint64_t* d_q = (uint64_t*)(aux + o_q);
     uint64_t* d_vals = (uint64_t*)(aux + o_vals);
     uint64_t* d_carry = (uint64_t*)(aux + o_carry);
@@ -1006,7 +997,7 @@ extern "C" int zkhip_dense_evaluate(zkhip_ctx* c, const uint64_t* d_coeffs, size
     const size_t per_block = (size_t)HS_T * HS_L;
     const uint32_t n_blocks = (uint32_t)((n + per_block - 1) / per_block);
     ZK_TRY(c->reserve_aux(64 * (size_t)n_blocks + 512));
-    uint64_t* d_vals = (uint64_t*)c->d_aux;
+    uint64_t* d_vals = (uint64_t*)c->aux.ptr;
     uint64_t* d_carry = d_vals + 4 * (size_t)n_blocks;
     uint64_t* d_eval = d_carry + 4 * (size_t)n_blocks;
     FrArg z = {};
@@ -1038,8 +1029,9 @@ extern "C" int zkhip_dense_degree(zkhip_ctx* c, const uint64_t* d_coeffs, size_t
 static int srs_gen_table(zkhip_ctx* c, const uint64_t** table_xy) {
     const size_t n_tab = (size_t)SRS_WINDOWS * SRS_DIGITS;
     if (!c->d_gen_table) {
-        void* mem = nullptr;
-        if (hipMalloc(&mem, n_tab * 97 + 256 + n_tab * 192) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        DevMem owner;
+        if (dev_alloc(owner, n_tab * 97 + 256 + n_tab * 192) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        void* const mem = owner.get();
         uint64_t* xy = (uint64_t*)mem;
         uint8_t* inf = (uint8_t*)mem + n_tab * 96;                 // never set: no multiple d * 2^(8w) * G with d < 256 is the identity
         uint64_t* xyzz = (uint64_t*)((char*)mem + ((n_tab * 97 + 255) & ~(size_t)255));
@@ -1047,17 +1039,17 @@ static int srs_gen_table(zkhip_ctx* c, const uint64_t** table_xy) {
         const size_t n_threads = (n_tab + SRS_CHUNK - 1) / SRS_CHUNK;
         hipLaunchKernelGGL(srs_batch_affine_kernel, dim3((unsigned)((n_threads + SRS_BLOCK - 1) / SRS_BLOCK)), dim3(SRS_BLOCK), 0,
                            c->stream, xyzz, n_tab, xy, inf);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(mem); return ZKHIP_ERR_HIP; }
-        c->d_gen_table = mem;
+        if (hipGetLastError() != hipSuccess) return ZKHIP_ERR_HIP;
+        c->d_gen_table = std::move(owner);
     }
-    *table_xy = (const uint64_t*)c->d_gen_table;
+    *table_xy = (const uint64_t*)c->d_gen_table.get();
     return ZKHIP_OK;
 }
 
 // scalars (device, n x 4) -> affine SRS points
 static int srs_from_scalars(zkhip_ctx* c, const uint64_t* d_scalars, size_t n, uint64_t* d_out_xy, uint8_t* d_out_inf) {
     // workspace layout: [scalars n*32 (owned by caller region)] ... we only need n*192 for XYZZ here
-    uint64_t* xyzz = (uint64_t*)((char*)c->d_ws + ((n * 32 + 255) & ~(size_t)255));
+    uint64_t* xyzz = (uint64_t*)((char*)c->ws.ptr + ((n * 32 + 255) & ~(size_t)255));
     const uint64_t* table = nullptr;
     ZK_TRY(srs_gen_table(c, &table));
     hipLaunchKernelGGL(srs_fixed_base_window_kernel, dim3((unsigned)((n + SRS_BLOCK - 1) / SRS_BLOCK)), dim3(SRS_BLOCK), 0, c->stream,
@@ -1078,7 +1070,7 @@ extern "C" int zkhip_srs_multilinear_g1(zkhip_ctx* c, const uint64_t* h_tau, uin
     ZK_TRY(c->reserve_ws(((n * 32 + 255) & ~(size_t)255) + n * 192));
     PtsArg tau = {};
     if (n_vars) std::memcpy(tau.v, h_tau, 32 * (size_t)n_vars);
-    uint64_t* d_scalars = (uint64_t*)c->d_ws;
+    uint64_t* d_scalars = (uint64_t*)c->ws.ptr;
     hipLaunchKernelGGL(srs_eq_scalars_kernel, dim3(mle_grid(n)), dim3(SRS_BLOCK), 0, c->stream, tau, n_vars, d_scalars);
     return srs_from_scalars(c, d_scalars, n, d_out_xy, d_out_inf);
 }
@@ -1091,7 +1083,7 @@ extern "C" int zkhip_srs_univariate_g1(zkhip_ctx* c, const uint64_t* h_tau, size
     ZK_TRY(c->reserve_ws(((n * 32 + 255) & ~(size_t)255) + n * 192));
     FrArg tau = {};
     std::memcpy(tau.v, h_tau, 32);
-    uint64_t* d_scalars = (uint64_t*)c->d_ws;
+    uint64_t* d_scalars = (uint64_t*)c->ws.ptr;
     hipLaunchKernelGGL(srs_power_scalars_kernel, dim3(mle_grid(n)), dim3(SRS_BLOCK), 0, c->stream, tau, n, d_scalars);
     return srs_from_scalars(c, d_scalars, n, d_out_xy, d_out_inf);
 }

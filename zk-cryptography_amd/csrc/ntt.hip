@@ -54,27 +54,16 @@ struct TwiddleKey {
         return inverse < o.inverse;
     }
 };
-struct NttPass { uint32_t s0, T; uint64_t* table; };
-struct NttPlan { uint64_t* tw1 = nullptr; std::vector<NttPass> passes; zkhost::Fr n_inv; };
+struct NttPass { uint32_t s0, T; DevMem table; };
+struct NttPlan { DevMem tw1; std::vector<NttPass> passes; zkhost::Fr n_inv; };
 struct NttCache {
-    std::map<TwiddleKey, uint64_t*> twiddles;
+    std::map<TwiddleKey, DevMem> twiddles;
     std::map<TwiddleKey, NttPlan> plans;
 };
-static void ntt_cache_free(void* p) {
-    NttCache* nc = (NttCache*)p;
-    for (auto& kv : nc->twiddles) (void)hipFree(kv.second);
-    for (auto& kv : nc->plans) {
-        if (kv.second.tw1) (void)hipFree(kv.second.tw1);
-        for (auto& ps : kv.second.passes) if (ps.table) (void)hipFree(ps.table);
-    }
-    delete nc;
-}
+void NttCacheDelete::operator()(NttCache* nc) const { delete nc; }
 static NttCache* ntt_cache(zkhip_ctx* c) {
-    if (!c->ntt_state) {
-        c->ntt_state = new (std::nothrow) NttCache();
-        c->ntt_free = ntt_cache_free;
-    }
-    return (NttCache*)c->ntt_state;
+    if (!c->ntt_state) c->ntt_state.reset(new (std::nothrow) NttCache());
+    return c->ntt_state.get();
 }
 
 static int get_twiddles(zkhip_ctx* c, uint32_t log_n, int inverse, uint64_t** out) {
@@ -82,21 +71,21 @@ static int get_twiddles(zkhip_ctx* c, uint32_t log_n, int inverse, uint64_t** ou
     if (!nc) return ZKHIP_ERR_NOMEM;
     TwiddleKey key{log_n, inverse};
     auto it = nc->twiddles.find(key);
-    if (it != nc->twiddles.end()) { *out = it->second; return ZKHIP_OK; }
+    if (it != nc->twiddles.end()) { *out = (uint64_t*)it->second.get(); return ZKHIP_OK; }
     const uint32_t log_half = log_n ? log_n - 1 : 0;
     const size_t half = (size_t)1 << log_half;
     zkhost::Fr w = root_of_unity(log_n);
     if (inverse) w = zkhost::fr_inv(w);
     std::vector<zkhost::Fr> pw(log_half ? log_half : 1);
     for (uint32_t k = 0; k < log_half; ++k) { pw[k] = w; w = zkhost::fr_mul(w, w); }
-    uint64_t *d_tab = nullptr, *d_pw = nullptr;
-    ZK_HIP(c, hipMalloc(&d_tab, half * 32));
-    ZK_HIP(c, hipMalloc(&d_pw, pw.size() * 32));
+    DevMem tab, powers;                             // built here, kept only when everything below went through
+    ZK_HIP(c, dev_alloc(tab, half * 32));
+    ZK_HIP(c, dev_alloc(powers, pw.size() * 32));
+    uint64_t *d_tab = (uint64_t*)tab.get(), *d_pw = (uint64_t*)powers.get();
     ZK_HIP(c, hipMemcpyAsync(d_pw, pw.data(), pw.size() * 32, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(ntt_twiddle_kernel, dim3(mle_grid(half)), dim3(MLE_BLOCK), 0, c->stream, d_pw, log_half, d_tab);
     ZK_HIP(c, hipStreamSynchronize(c->stream));
-    ZK_HIP(c, hipFree(d_pw));
-    nc->twiddles[key] = d_tab;
+    nc->twiddles[key] = std::move(tab);
     *out = d_tab;
     return ZKHIP_OK;
 }
@@ -112,8 +101,8 @@ static int get_plan(zkhip_ctx* c, uint32_t log_n, int inverse, NttPlan** out) {
     ZK_TRY(get_twiddles(c, log_n, inverse, &W));
     NttPlan plan;
     plan.n_inv = zkhost::fr_inv(zkhost::fr_from_u64((uint64_t)1 << log_n));
-    ZK_HIP(c, hipMalloc(&plan.tw1, 256 * 32));
-    hipLaunchKernelGGL(ntt_first_table_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, W, log_n, plan.tw1);
+    ZK_HIP(c, dev_alloc(plan.tw1, 256 * 32));
+    hipLaunchKernelGGL(ntt_first_table_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, W, log_n, (uint64_t*)plan.tw1.get());
     // the stages after the first eight, in passes of <= 7 spread evenly
     const uint32_t rest = log_n - NTT_FIRST_STAGES;
     const uint32_t n_pass = (rest + 6) / 7;
@@ -122,18 +111,18 @@ static int get_plan(zkhip_ctx* c, uint32_t log_n, int inverse, NttPlan** out) {
         const uint32_t T = (rest - (s0 - NTT_FIRST_STAGES) + (n_pass - p) - 1) / (n_pass - p);
         NttPass ps{s0, T, nullptr};
         const size_t entries = (((size_t)1 << T) - 1) << s0;
-        ZK_HIP(c, hipMalloc(&ps.table, entries * 32));
+        ZK_HIP(c, dev_alloc(ps.table, entries * 32));
         FrArg sc = {};
         const bool scaled = inverse && p + 1 == n_pass;
         if (scaled) std::memcpy(sc.v, plan.n_inv.l, 32);
         hipLaunchKernelGGL(ntt_pass_table_kernel, dim3(mle_grid_stream(entries)), dim3(MLE_BLOCK), 0, c->stream, W, log_n, s0, T, sc,
-                           scaled ? 1u : 0u, ps.table);
-        plan.passes.push_back(ps);
+                           scaled ? 1u : 0u, (uint64_t*)ps.table.get());
+        plan.passes.push_back(std::move(ps));
         s0 += T;
     }
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipStreamSynchronize(c->stream));
-    *out = &(nc->plans[key] = plan);
+    *out = &(nc->plans[key] = std::move(plan));
     return ZKHIP_OK;
 }
 
@@ -148,7 +137,7 @@ static int ntt_big(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint
     const unsigned grid = (unsigned)(n >> NTT_BIG_TILE_LOG);
     {
         ProfScope ps(c, "ntt_first8", 32.0 * (double)(n_src + n) + (d_src2 ? 32.0 * (double)n : 0.0));
-        hipLaunchKernelGGL(ntt_first8_kernel, dim3(grid), dim3(NTT_BIG_BLOCK), lds, c->stream, d_src, n_src, d_src2, d_scratch, log_n, plan->tw1);
+        hipLaunchKernelGGL(ntt_first8_kernel, dim3(grid), dim3(NTT_BIG_BLOCK), lds, c->stream, d_src, n_src, d_src2, d_scratch, log_n, (const uint64_t*)plan->tw1.get());
     }
     FrArg sc = {};
     std::memcpy(sc.v, plan->n_inv.l, 32);
@@ -157,10 +146,10 @@ static int ntt_big(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint
         const bool last = p + 1 == plan->passes.size();
         ProfScope pr(c, "ntt_pass", 32.0 * (double)(n + (last ? n_dst : n)) + 32.0 * (double)((((size_t)1 << ps.T) - 1) << ps.s0));
         if (last && inverse)
-            hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3(grid), dim3(NTT_BIG_BLOCK), lds, c->stream, d_scratch, d_dst, ps.s0, ps.T, ps.table, sc, n_dst);
+            hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3(grid), dim3(NTT_BIG_BLOCK), lds, c->stream, d_scratch, d_dst, ps.s0, ps.T, (const uint64_t*)ps.table.get(), sc, n_dst);
         else
             hipLaunchKernelGGL(ntt_pass_kernel<false>, dim3(grid), dim3(NTT_BIG_BLOCK), lds, c->stream, d_scratch, last ? d_dst : d_scratch, ps.s0, ps.T,
-                               ps.table, sc, last ? n_dst : n);
+                               (const uint64_t*)ps.table.get(), sc, last ? n_dst : n);
     }
     ZK_HIP(c, hipGetLastError());
     return ZKHIP_OK;
@@ -206,7 +195,7 @@ extern "C" int zkhip_ntt(zkhip_ctx* c, uint64_t* d_data, uint32_t log_n, int inv
     ZK_TRY(c->activate());
     const size_t n = (size_t)1 << log_n;
     ZK_TRY(c->reserve_ws(n * 32));
-    return ntt_inplace(c, d_data, log_n, inverse, (uint64_t*)c->d_ws);
+    return ntt_inplace(c, d_data, log_n, inverse, (uint64_t*)c->ws.ptr);
 }
 
 // Domain::fft / ifft as the reference calls them (domain.rs:108-118: clone, resize to the domain size with zeros, transform):
@@ -219,12 +208,12 @@ extern "C" int zkhip_domain_transform(zkhip_ctx* c, const uint64_t* d_src, size_
     if (n_src > n) return ZKHIP_ERR_SHAPE;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws(n * 32));
-    if (log_n >= 12) return ntt_big(c, d_src, n_src, nullptr, d_dst, n, log_n, inverse, (uint64_t*)c->d_ws);
+    if (log_n >= 12) return ntt_big(c, d_src, n_src, nullptr, d_dst, n, log_n, inverse, (uint64_t*)c->ws.ptr);
     if (d_dst != d_src) {
         if (n_src < n) ZK_HIP(c, hipMemsetAsync(d_dst + 4 * n_src, 0, (n - n_src) * 32, c->stream));
         if (n_src) ZK_HIP(c, hipMemcpyAsync(d_dst, d_src, n_src * 32, hipMemcpyDeviceToDevice, c->stream));
     } else if (n_src != n) return ZKHIP_ERR_ARG;
-    return ntt_inplace(c, d_dst, log_n, inverse, (uint64_t*)c->d_ws);
+    return ntt_inplace(c, d_dst, log_n, inverse, (uint64_t*)c->ws.ptr);
 }
 
 extern "C" int zkhip_pointwise_mul(zkhip_ctx* c, const uint64_t* d_a, const uint64_t* d_b, size_t n, uint64_t* d_out) {
@@ -246,7 +235,7 @@ extern "C" int zkhip_univariate_multiply(zkhip_ctx* c, const uint64_t* d_a, size
     if (log_n > 30) return ZKHIP_ERR_SHAPE;
     const size_t n = (size_t)1 << log_n;
     ZK_TRY(c->reserve_ws(3 * n * 32));
-    uint64_t* scratch = (uint64_t*)c->d_ws;
+    uint64_t* scratch = (uint64_t*)c->ws.ptr;
     uint64_t* ea = scratch + 4 * n;
     uint64_t* eb = ea + 4 * n;
     if (log_n >= 12) {

@@ -246,7 +246,7 @@ int verify_batch(zkhip_ctx* c, size_t batch, size_t n, const uint64_t* h_commits
     const size_t o_pairinf = carve(np), o_f = carve(np * 576), o_bad = carve(np + m), o_ok = carve(batch);
     const size_t o_prep = carve(d_prepared ? 0 : m * PREP_STRIDE_U64 * 8);
     ZK_TRY(c->reserve_ws(off));
-    char* ws = (char*)c->d_ws;
+    char* ws = (char*)c->ws.ptr;
     auto up = [&](size_t o, const void* h, size_t bytes) {
         return bytes ? hipMemcpyAsync(ws + o, h, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
     };
@@ -286,7 +286,7 @@ extern "C" int zkhip_srs_multilinear_g2(zkhip_ctx* c, const uint64_t* h_tau, uin
     if (!n_vars) return ZKHIP_OK;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws(32 * (size_t)n_vars));
-    uint64_t* d_s = (uint64_t*)c->d_ws;
+    uint64_t* d_s = (uint64_t*)c->ws.ptr;
     ZK_HIP(c, hipMemcpyAsync(d_s, h_tau, 32 * (size_t)n_vars, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(g2_srs_kernel, dim3(pair_grid(n_vars)), dim3(PAIR_BLOCK), 0, c->stream, d_s, (size_t)n_vars, d_out_xy, d_out_inf);
     ZK_HIP(c, hipGetLastError());
@@ -299,7 +299,7 @@ extern "C" int zkhip_srs_univariate_g2(zkhip_ctx* c, const uint64_t* h_tau, size
     ZK_TRY(c->activate());
     const size_t n = max_degree + 1;
     ZK_TRY(c->reserve_ws(256 + 32 * n));
-    uint64_t* d_tau = (uint64_t*)c->d_ws;
+    uint64_t* d_tau = (uint64_t*)c->ws.ptr;
     uint64_t* d_s = d_tau + 32;
     ZK_HIP(c, hipMemcpyAsync(d_tau, h_tau, 32, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(g2_power_scalars_kernel, dim3(pair_grid(n)), dim3(PAIR_BLOCK), 0, c->stream, d_tau, n, d_s);
@@ -316,14 +316,14 @@ extern "C" int zkhip_g2_prepare(zkhip_ctx* c, const uint64_t* d_g2_xy, const uin
     if (!n) return ZKHIP_OK;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws(n));
-    return prepare(c, d_g2_xy, d_g2_inf, n, 0, (uint64_t*)d_prepared, (uint8_t*)c->d_ws);
+    return prepare(c, d_g2_xy, d_g2_inf, n, 0, (uint64_t*)d_prepared, (uint8_t*)c->ws.ptr);
 }
 
 extern "C" int zkhip_kzg_prepare(zkhip_ctx* c, const uint64_t* d_g2_xy, const uint8_t* d_g2_inf, size_t n, void* d_prepared) {
     if (!c || !d_prepared || (n && !d_g2_xy)) return ZKHIP_ERR_ARG;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws(n + 1));
-    return prepare(c, d_g2_xy, d_g2_inf, n, 1, (uint64_t*)d_prepared, (uint8_t*)c->d_ws);
+    return prepare(c, d_g2_xy, d_g2_inf, n, 1, (uint64_t*)d_prepared, (uint8_t*)c->ws.ptr);
 }
 
 static int pairing_common(zkhip_ctx* c, const uint64_t* d_g1_xy, const uint8_t* d_g1_inf, const uint64_t* d_g2_xy,
@@ -333,8 +333,8 @@ static int pairing_common(zkhip_ctx* c, const uint64_t* d_g1_xy, const uint8_t* 
     ZK_TRY(c->activate());
     const size_t o_bad = align256(n * 576);
     ZK_TRY(c->reserve_ws(o_bad + n));
-    uint64_t* f = (uint64_t*)c->d_ws;
-    uint8_t* bad = (uint8_t*)c->d_ws + o_bad;
+    uint64_t* f = (uint64_t*)c->ws.ptr;
+    uint8_t* bad = (uint8_t*)c->ws.ptr + o_bad;
     hipLaunchKernelGGL(pairing_check_kernel, dim3(pair_grid(n)), dim3(PAIR_BLOCK), 0, c->stream, d_g1_xy, d_g1_inf,
                        d_prepared ? nullptr : d_g2_xy, d_g2_inf, n, bad);
     ZK_TRY(pairing_groups(c, d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, (const uint64_t*)d_prepared, 0, n, 1, f, d_out_gt, nullptr));

@@ -104,19 +104,20 @@ int zkhip_comm::all_gather(const void* d_send, void* d_recv, size_t bytes) {
 int zkhip_comm::setup_fault_buffers() {
     if (passthrough()) return ZKHIP_OK;              // one rank, no transport: an error simply returns
     ZK_TRY(c->activate());
-    if (hipMalloc(&poison_send, POISON_ELEMS * 32) != hipSuccess) return ZKHIP_ERR_NOMEM;
-    if (hipMalloc(&poison_recv, POISON_ELEMS * 32 * (size_t)world_) != hipSuccess) return ZKHIP_ERR_NOMEM;
-    if (hipHostMalloc((void**)&peer_flag_h, 64, hipHostMallocMapped) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    if (zk::dev_alloc(poison_send, POISON_ELEMS * 32) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    if (zk::dev_alloc(poison_recv, POISON_ELEMS * 32 * (size_t)world_) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    if (zk::pin_alloc(peer_flag_mem, 64, hipHostMallocMapped) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    peer_flag_h = (uint32_t*)peer_flag_mem.get();
     *peer_flag_h = 0;
     if (hipHostGetDevicePointer((void**)&peer_flag_d, peer_flag_h, 0) != hipSuccess) return ZKHIP_ERR_HIP;
-    hipLaunchKernelGGL(shard_poison_fill_kernel, dim3(256), dim3(256), 0, c->stream, (uint4*)poison_send, POISON_ELEMS * 2);
+    hipLaunchKernelGGL(shard_poison_fill_kernel, dim3(256), dim3(256), 0, c->stream, (uint4*)poison_send.get(), POISON_ELEMS * 2);
     ZK_HIP(c, hipGetLastError());
     return c->wait_stream();
 }
 int zkhip_comm::poison(size_t elems, const uint64_t** d_send, uint64_t** d_recv) {
     if (!poison_send || !poison_recv || elems > POISON_ELEMS) return ZKHIP_ERR_NOMEM;
-    *d_send = (const uint64_t*)poison_send;
-    *d_recv = (uint64_t*)poison_recv;
+    *d_send = (const uint64_t*)poison_send.get();
+    *d_recv = (uint64_t*)poison_recv.get();
     return ZKHIP_OK;
 }
 int zkhip_comm::check(const uint64_t* d_gathered, size_t elems) {
@@ -130,15 +131,17 @@ int zkhip_comm::check(const uint64_t* d_gathered, size_t elems) {
 // ---------------------------------------------------------------------------------------
 // communicator
 // ---------------------------------------------------------------------------------------
+// a communicator under construction: an early exit ends it like zkhip_comm_destroy does (drain, end the RCCL communicator, release)
+struct CommDestroy { void operator()(zkhip_comm* m) const { (void)zkhip_comm_destroy(m); } };
+using CommOwner = std::unique_ptr<zkhip_comm, CommDestroy>;
 extern "C" int zkhip_comm_create(zkhip_ctx* c, uint32_t rank, uint32_t world, zkhip_all_gather_fn fn, void* user, zkhip_comm** out) {
     if (!c || !out || world == 0 || rank >= world || (world > 1 && !fn)) return ZKHIP_ERR_ARG;
     if (!is_pow2(world)) return ZKHIP_ERR_SHAPE;          // the tables have 2^n entries
-    zkhip_comm* m = new (std::nothrow) zkhip_comm();
+    CommOwner m(new (std::nothrow) zkhip_comm());
     if (!m) return ZKHIP_ERR_NOMEM;
     m->c = c; m->rank_ = rank; m->world_ = world; m->fn = fn; m->user = user;
-    const int rc = m->setup_fault_buffers();
-    if (rc != ZKHIP_OK) { zkhip_comm_destroy(m); return rc; }
-    *out = m;
+    ZK_TRY(m->setup_fault_buffers());
+    *out = m.release();
     return ZKHIP_OK;
 }
 extern "C" int zkhip_rccl_unique_id(uint8_t* h_id128) {
@@ -159,15 +162,14 @@ extern "C" int zkhip_comm_create_rccl(zkhip_ctx* c, const uint8_t* h_id128, uint
     if (!is_pow2(world)) return ZKHIP_ERR_SHAPE;
     if (!rccl().ok) return ZKHIP_ERR_HIP;
     ZK_TRY(c->activate());
-    zkhip_comm* m = new (std::nothrow) zkhip_comm();
+    CommOwner m(new (std::nothrow) zkhip_comm());
     if (!m) return ZKHIP_ERR_NOMEM;
     m->c = c; m->rank_ = rank; m->world_ = world;
     RcclId id;
     std::memcpy(id.internal, h_id128, 128);
-    if (rccl().CommInitRank(&m->nccl, (int)world, id, (int)rank) != 0 || !m->nccl) { delete m; return ZKHIP_ERR_HIP; }
-    const int rc = m->setup_fault_buffers();
-    if (rc != ZKHIP_OK) { zkhip_comm_destroy(m); return rc; }
-    *out = m;
+    if (rccl().CommInitRank(&m->nccl, (int)world, id, (int)rank) != 0 || !m->nccl) { m->nccl = nullptr; return ZKHIP_ERR_HIP; }   // (no communicator to end)
+    ZK_TRY(m->setup_fault_buffers());
+    *out = m.release();
     return ZKHIP_OK;
 }
 extern "C" int zkhip_comm_destroy(zkhip_comm* m) {
@@ -175,14 +177,6 @@ extern "C" int zkhip_comm_destroy(zkhip_comm* m) {
     int rc = ZKHIP_OK;
     if (m->c->activate() != ZKHIP_OK || hipStreamSynchronize(m->c->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
     if (m->nccl && rccl().CommDestroy(m->nccl) != 0) rc = ZKHIP_ERR_HIP;
-    for (auto& b : m->buf) if (b) (void)hipFree(b);
-    if (m->poison_send) (void)hipFree(m->poison_send);
-    if (m->poison_recv) (void)hipFree(m->poison_recv);
-    if (m->peer_flag_h) (void)hipHostFree(m->peer_flag_h);
-    if (m->solo) {
-        for (auto& b : m->solo->buf) if (b) (void)hipFree(b);
-        delete m->solo;
-    }
     delete m;
     return rc;
 }
@@ -362,15 +356,15 @@ extern "C" int zkhip_kzg_commit_sharded(zkhip_comm* m, const uint64_t* d_points_
     uint64_t* pin = c->pinned_u64(ZK_PIN_PROOF);          // the proof staging area: no prover runs during a commit of the same context
     std::memcpy(pin, rec, 128);
     const bool own = local_rc == ZKHIP_OK;
-    uint64_t* send = own ? m->buffer(0, 4) : (uint64_t*)m->poison_recv;              // (a failed rank touches no allocator: the reserve)
-    uint64_t* recv = own ? m->buffer(1, 4 * (size_t)world) : (uint64_t*)m->poison_recv + 4 * 4;
+    uint64_t* send = own ? m->buffer(0, 4) : (uint64_t*)m->poison_recv.get();              // (a failed rank touches no allocator: the reserve)
+    uint64_t* recv = own ? m->buffer(1, 4 * (size_t)world) : (uint64_t*)m->poison_recv.get() + 4 * 4;
     if (!send || !recv) {
         if (!m->poison_recv) return ZKHIP_ERR_NOMEM;
         local_rc = ZKHIP_ERR_NOMEM;
         pin[13] = (uint64_t)(uint32_t)local_rc;
         std::memset(pin, 0, 96);
-        send = (uint64_t*)m->poison_recv;
-        recv = (uint64_t*)m->poison_recv + 4 * 4;
+        send = (uint64_t*)m->poison_recv.get();
+        recv = (uint64_t*)m->poison_recv.get() + 4 * 4;
     }
     ZK_HIP(c, hipMemcpyAsync(send, pin, 128, hipMemcpyHostToDevice, c->stream));
     ZK_TRY(m->all_gather(send, recv, 128));

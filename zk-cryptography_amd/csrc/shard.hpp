@@ -17,26 +17,26 @@ struct zkhip_comm {
     uint32_t rank_ = 0, world_ = 1;
     zkhip_all_gather_fn fn = nullptr;
     void* user = nullptr;
-    void* nccl = nullptr;                    // ncclComm_t when the library owns an RCCL communicator
+    void* nccl = nullptr;                    // ncclComm_t when the library owns an RCCL communicator (untyped: librccl is resolved at run time, shard.hip; ended by zkhip_comm_destroy)
     uint64_t n_exchanges = 0, n_bytes = 0;   // cumulative (zkhip_comm_stats)
-    void* buf[4] = {};                       // protocol scratch (send / gathered / interleaved records), grow-only
-    size_t cap[4] = {};
+    zk::GrowBuf buf[4];                      // protocol scratch (send / gathered / interleaved records)
     // failure propagation (shard_protocol.hpp): what a FAILED rank still needs to enter the remaining exchanges, set aside when the
     // communicator is created so that no allocation stands between a failure and its report; and the healthy ranks' sticky flag
-    void* poison_send = nullptr;             // POISON_ELEMS elements: the first all ones, the rest zero
-    void* poison_recv = nullptr;             // world x POISON_ELEMS elements
-    uint32_t* peer_flag_h = nullptr;         // host-mapped: raised by shard_check_kernel when a gathered record carries the poison mark
+    zk::DevMem poison_send;                  // POISON_ELEMS elements: the first all ones, the rest zero
+    zk::DevMem poison_recv;                  // world x POISON_ELEMS elements
+    zk::PinMem peer_flag_mem;                // host-mapped: raised by shard_check_kernel when a gathered record carries the poison mark
+    uint32_t* peer_flag_h = nullptr;         // views of peer_flag_mem: the host's and the device's address
     uint32_t* peer_flag_d = nullptr;
     int inject_at = -1, inject_rc = 0;       // test hook (zkhip_comm_inject_failure): fail in front of exchange inject_at of the next protocol run
-    static constexpr size_t POISON_ELEMS = (size_t)1 << 16;   // >= the longest record of any protocol (zk_shard_max_record(), checked per run)
-    zkhip_comm* solo = nullptr;              // a one-rank comm on the same context (steps of a sharded proof that run whole on every rank), kept
+    static constexpr size_t POISON_ELEMS = (size_t)1 << 16;   // >= the longest record of any protocol: poison() and check() refuse a longer one at every exchange
+    std::unique_ptr<zkhip_comm> solo;        // a one-rank comm on the same context (steps of a sharded proof that run whole on every rank), kept
     zkhip_comm* solo_comm() {
         if (world_ == 1) return this;
         if (!solo) {
-            solo = new (std::nothrow) zkhip_comm();
+            solo.reset(new (std::nothrow) zkhip_comm());
             if (solo) solo->c = c;
         }
-        return solo;
+        return solo.get();
     }
     uint32_t world() const { return world_; }
     bool passthrough() const { return world_ == 1 && !nccl && !fn; }
@@ -57,17 +57,10 @@ struct zkhip_comm {
         return true;
     }
     uint64_t* buffer(int id, size_t elems) {
+        // at least 64 KiB; growth drains the stream: kernels of an earlier protocol step may still read the old allocation
         const size_t need = (elems ? elems : 1) * 32;
-        if (need > cap[id]) {
-            // growth: kernels of an earlier protocol step may still read the old allocation
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
-            if (buf[id]) (void)hipFree(buf[id]);
-            buf[id] = nullptr; cap[id] = 0;
-            const size_t want = std::max<size_t>(need, (size_t)64 * 1024);
-            if (hipMalloc(&buf[id], want) != hipSuccess) return nullptr;
-            cap[id] = want;
-        }
-        return (uint64_t*)buf[id];
+        if (need > buf[id].bytes && buf[id].reserve(std::max<size_t>(need, (size_t)64 * 1024), {c->stream}) != ZKHIP_OK) return nullptr;
+        return (uint64_t*)buf[id].ptr;
     }
 };
 

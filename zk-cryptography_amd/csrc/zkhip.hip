@@ -47,70 +47,24 @@ extern "C" int zkhip_ctx_create(zkhip_ctx** out, int device, void* stream) {
     int count = 0;
     hipError_t e0 = hipGetDeviceCount(&count);
     if (e0 != hipSuccess || device < 0 || device >= count) { g_last_hip = (int)e0; return ZKHIP_ERR_HIP; }
-    zkhip_ctx* c = new zkhip_ctx();
+    std::unique_ptr<zkhip_ctx> c(new zkhip_ctx());      // (nothing is enqueued yet: an error exit just lets the members go)
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess) { delete c; return ZKHIP_ERR_HIP; }
+    if (hipSetDevice(device) != hipSuccess) return ZKHIP_ERR_HIP;
     c->stream = (hipStream_t)stream;   // NULL = the device's default (null) stream, ordered with everything
-    c->own_stream = false;
-    if (hipHostMalloc(&c->h_pinned, ZK_PINNED_BYTES, hipHostMallocDefault) != hipSuccess) { delete c; return ZKHIP_ERR_HIP; }
-    if (hipMalloc(&c->d_small, ZK_SMALL_BYTES) != hipSuccess) { delete c; return ZKHIP_ERR_NOMEM; }
-    *out = c;
+    if (pin_alloc(c->h_pinned, ZK_PINNED_BYTES) != hipSuccess) return ZKHIP_ERR_HIP;
+    if (dev_alloc(c->d_small, ZK_SMALL_BYTES) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    *out = c.release();
     return ZKHIP_OK;
 }
 
 extern "C" int zkhip_ctx_destroy(zkhip_ctx* c) {
     if (!c) return ZKHIP_ERR_ARG;
     hipSetDevice(c->device);
-    for (zkhip_ctx* lane : c->gkr_lanes) zkhip_ctx_destroy(lane);      // zkhip_gkr_prove_batch's lanes
-    c->gkr_lanes.clear();
+    c->gkr_lanes.clear();                                             // zkhip_gkr_prove_batch's lanes: each is destroyed like this context
     hipSetDevice(c->device);
     for (int k = 0; k < zkhip_ctx::ASYNC_SLOTS; ++k) if (c->async_pend[k]) zkhip_kzg_commit_end(c, (uint32_t)k, nullptr, nullptr);   // commits never collected
     (void)c->flush_deferred();
-    hipStreamSynchronize(c->stream);
-    if (c->gkr_graph.exec) (void)hipGraphExecDestroy((hipGraphExec_t)c->gkr_graph.exec);
-    if (c->d_gkr_in) (void)hipFree(c->d_gkr_in);
-    // proofs still in flight write their results into the pinned slots from their lanes' streams: drain every stream of the context first
-    if (c->fold_stream) hipStreamSynchronize(c->fold_stream);
-    for (auto& L : c->lanes) { if (L.serial) hipStreamSynchronize(L.serial); if (L.fold) hipStreamSynchronize(L.fold); }
-    for (int i = 0; i < zkhip_ctx::MSM_SLOTS; ++i) if (c->side[i]) hipStreamSynchronize(c->side[i]);
-    for (auto& e : c->prof_events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    if (c->d_ws) hipFree(c->d_ws);
-    if (c->d_aux) hipFree(c->d_aux);
-    if (c->d_gen_table) hipFree(c->d_gen_table);
-    if (c->d_composed) hipFree(c->d_composed);
-    if (c->d_fingerprint) hipFree(c->d_fingerprint);
-    if (c->guard_stream) { hipStreamSynchronize(c->guard_stream); hipStreamDestroy(c->guard_stream); }
-    if (c->guard_ev) hipEventDestroy(c->guard_ev);
-    if (c->ntt_state && c->ntt_free) c->ntt_free(c->ntt_state);
-    for (int i = 0; i < zkhip_ctx::MSM_SLOTS; ++i) {
-        if (c->msm_pin[i]) hipHostFree(c->msm_pin[i]);
-        if (c->msm_tab_dev[i]) hipFree(c->msm_tab_dev[i]);
-        if (c->msm_tab_pin[i]) hipHostFree(c->msm_tab_pin[i]);
-        if (c->msm_ev[i]) hipEventDestroy(c->msm_ev[i]);
-        if (c->side[i]) hipStreamDestroy(c->side[i]);
-    }
-    delete c->host_pool;
-    if (c->fork_ev) hipEventDestroy(c->fork_ev);
-    if (c->join_ev) hipEventDestroy(c->join_ev);
-    if (c->serial_ev) hipEventDestroy(c->serial_ev);
-    if (c->done_ev) hipEventDestroy(c->done_ev);
-    for (int k = 0; k < zkhip_ctx::PROOF_SLOTS; ++k) { if (c->proof_ev[k]) hipEventDestroy(c->proof_ev[k]); if (c->proof_pin[k]) hipHostFree(c->proof_pin[k]); }
-    if (c->fold_stream) hipStreamDestroy(c->fold_stream);
-    for (int k = 0; k < zkhip_ctx::COARSE_RING; ++k) if (c->d_coarse[k]) hipFree(c->d_coarse[k]);
-    for (auto& L : c->lanes) {
-        if (L.serial && !L.borrowed) hipStreamDestroy(L.serial);
-        if (L.fold && !L.borrowed) hipStreamDestroy(L.fold);
-        if (L.begin_ev) hipEventDestroy(L.begin_ev);
-        if (L.fork_ev) hipEventDestroy(L.fork_ev);
-        if (L.serial_ev) hipEventDestroy(L.serial_ev);
-        if (L.ws) hipFree(L.ws);
-        if (L.small) hipFree(L.small);
-    }
-    if (c->d_small) hipFree(c->d_small);
-    if (c->sc_small) hipFree(c->sc_small);
-    if (c->sc_stage) hipFree(c->sc_stage);
-    if (c->h_pinned) hipHostFree(c->h_pinned);
-    if (c->own_stream) hipStreamDestroy(c->stream);
+    c->drain_streams();      // before any member goes away (by its owner, in ~zkhip_ctx)
     delete c;
     return ZKHIP_OK;
 }
@@ -123,8 +77,8 @@ extern "C" int zkhip_ctx_set_stream(zkhip_ctx* c, void* stream) {
     ZK_TRY(c->activate());
     (void)c->flush_deferred();                  // proofs in flight finish on the stream they began on (a failure is reported by their prove_end)
     ZK_TRY(c->ensure_side_streams());
-    ZK_HIP(c, hipEventRecord(c->fork_ev, c->stream));
-    ZK_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->fork_ev, 0));
+    ZK_HIP(c, hipEventRecord(c->fork_ev.get(), c->stream));
+    ZK_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->fork_ev.get(), 0));
     c->stream = (hipStream_t)stream;
     return ZKHIP_OK;
 }
@@ -147,7 +101,7 @@ extern "C" int zkhip_free(zkhip_ctx* c, void* d_ptr) {
     if (!c) return ZKHIP_ERR_ARG;
     if (d_ptr) (void)zkhip_table_release(c, d_ptr);      // (a table of the commit path: its address is no longer a known table, msm.hip)
     ZK_HIP(c, hipStreamSynchronize(c->stream));
-    ZK_HIP(c, hipFree(d_ptr));
+    ZK_HIP(c, dev_free_raw(d_ptr));
     return ZKHIP_OK;
 }
 extern "C" int zkhip_memcpy_h2d(zkhip_ctx* c, void* d_dst, const void* h_src, size_t bytes) {
@@ -179,7 +133,7 @@ extern "C" int zkhip_profile_read(zkhip_ctx* c, const char* kernel, double* tota
     for (auto& r : c->prof_records) {
         if (std::strcmp(r.name, kernel) != 0) continue;
         float t = 0;
-        ZK_HIP(c, hipEventElapsedTime(&t, c->prof_events[r.event].start, c->prof_events[r.event].stop));
+        ZK_HIP(c, hipEventElapsedTime(&t, c->prof_events[r.event].start.get(), c->prof_events[r.event].stop.get()));
         ms += t; by += r.bytes; ++cnt;
     }
     if (total_ms) *total_ms = ms;
@@ -196,8 +150,8 @@ extern "C" int zkhip_profile_timeline(zkhip_ctx* c, uint32_t max_records, char* 
     for (auto& r : c->prof_records) {
         if (n == max_records) break;
         float a = 0, b = 0;
-        ZK_HIP(c, hipEventElapsedTime(&a, c->prof_events[c->prof_records[0].event].start, c->prof_events[r.event].start));
-        ZK_HIP(c, hipEventElapsedTime(&b, c->prof_events[c->prof_records[0].event].start, c->prof_events[r.event].stop));
+        ZK_HIP(c, hipEventElapsedTime(&a, c->prof_events[c->prof_records[0].event].start.get(), c->prof_events[r.event].start.get()));
+        ZK_HIP(c, hipEventElapsedTime(&b, c->prof_events[c->prof_records[0].event].start.get(), c->prof_events[r.event].stop.get()));
         std::snprintf(names + 32 * (size_t)n, 32, "%s", r.name);
         start_us[n] = 1e3 * a;
         stop_us[n] = 1e3 * b;
@@ -250,8 +204,44 @@ extern "C" int zkhip_mle_partial_evaluation(zkhip_ctx* c, const uint64_t* d_eval
     return launch_fold(c, d_evals, n, d_r, h_r, var_index, d_out, false, nullptr, nullptr);
 }
 
+// the k-variable fold of a cn-entry table in the shape that suits its output size; returns the per-workgroup sums' count
 static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cur, size_t cn, uint32_t k, const uint64_t* d_w,
-                            uint64_t* dst, uint64_t* pdst, uint32_t* n_parts);
+                            uint64_t* dst, uint64_t* pdst, uint32_t* n_parts) {
+    const size_t m = cn >> k;
+    uint32_t out_per_wg;
+    // diagnostics: ZKHIP_MF=0 keeps the VALU form for an A/B on the same box (tools/ab_multifold.sh); ZKHIP_MF=r (1..9) sets the rotation of
+    // the term order (tile T starts at term r * T mod 2^k; the default 1 -- 3 and 5 measured the same, 0 = every wave at term 0: 108 vs 112 us
+    // before the aligned planes); ZKHIP_MF_OCC=n caps the workgroups per CU through the LDS request (all 1024 workgroups are resident at once as it is, 4 per CU; capped at 2 per CU
+    // or with 36-78 KiB requested per workgroup the pass takes the same 83-85 us, alone and beside the proofs in flight: round 6)
+    static const int mf_cfg = [] { const char* e = getenv("ZKHIP_MF"); return e ? atoi(e) : 1; }();
+    if (m >= 8192 && k >= 4 && mf_cfg != 0) {   // streaming shape, limb products on the matrix cores (mfma_fold.hpp)
+        out_per_wg = 64;
+        ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
+        const unsigned tiles = (unsigned)(m / 64), rot = (unsigned)(mf_cfg % 10);
+        static const int mf_occ = [] { const char* e = getenv("ZKHIP_MF_OCC"); return e ? atoi(e) : 0; }();
+        size_t q_bytes = mfm_lds_bytes(std::min<uint32_t>(1u << k, (uint32_t)MFM_CHUNK));
+        if (mf_occ > 0) q_bytes = std::max(q_bytes, (size_t)(((158 * 1024 / mf_occ) - 1024) & ~255));
+        if (q_bytes > 64 * 1024) ZK_TRY(c->allow_big_lds((const void*)multifold_mfma_kernel<4, 4>, 158 * 1024));   // (the kernel has ~0.6 KiB of static LDS on top)
+        hipLaunchKernelGGL((multifold_mfma_kernel<4, 4>), dim3(tiles / 4), dim3(256), q_bytes, stream, cur, m, k, d_w, dst, pdst, rot);
+    } else if (m >= 8192) {   // streaming shape: 64 outputs per workgroup, its waves split the terms
+        out_per_wg = 64;
+        // >= 64 terms per lane: every lane pays one 9-word reduction (~a product), which at 16 terms per lane made the
+        // 6-variable fold of the overlapped plan 12 % slower than the 8-variable one
+        const uint32_t waves = k >= 8 ? 4 : k == 7 ? 2 : 1;
+        ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
+        hipLaunchKernelGGL((multifold_kernel<64, 4, true>), dim3((unsigned)(m / 64)), dim3(64 * waves), ((size_t)32 << k) + 32 * (size_t)(waves - 1) * 64,
+                           stream, cur, m, k, d_w, dst, pdst);
+    } else {                  // few outputs left: 16 per workgroup, up to 64 lanes share one output
+        out_per_wg = 16;
+        uint32_t waves = 16;
+        while (waves * 4 > (1u << k)) waves >>= 1;   // at least one term per lane group (k >= 3 here)
+        ProfScope ps(c, "multifold_small", 32.0 * (double)cn + 32.0 * (double)m, stream);
+        hipLaunchKernelGGL(multifold_kernel<16>, dim3((unsigned)(m / 16)), dim3(64 * waves), ((size_t)32 << k) + 32 * (size_t)(waves - 1) * 16, stream, cur, m, k, d_w, dst, pdst);
+    }
+    ZK_HIP(c, hipGetLastError());
+    if (n_parts) *n_parts = (uint32_t)(m / out_per_wg);
+    return ZKHIP_OK;
+}
 // Successive folds of variable 0 (or of h_var_indices); the points are host values, passed by value per launch.
 static int fold_chain(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uint64_t* h_pts,
                       const uint32_t* var_indices, size_t n_pts, uint64_t* d_out) {
@@ -264,7 +254,7 @@ static int fold_chain(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uin
     }
     const size_t need = (n / 2 + n / 4 + 8) * 32 + (256 + n / 512 + 4096) * 32;
     ZK_TRY(c->reserve_ws(need));
-    uint64_t* A = (uint64_t*)c->d_ws;
+    uint64_t* A = (uint64_t*)c->ws.ptr;
     uint64_t* B = A + 4 * (n / 2);
     uint64_t* d_w = B + 4 * (n / 4 + 4);
     uint64_t* d_dummy = d_w + 4 * 256;            // per-workgroup output sums of the k-variable fold (unused here; <= n / 512 of them)
@@ -349,7 +339,7 @@ extern "C" int zkhip_mle_evaluation(zkhip_ctx* c, const uint64_t* d_evals, size_
         const uint32_t k1 = std::min<uint32_t>(MF_MAX_LOGK, log_n - 13), k2 = log_n - k1, s2 = k2 / 2;
         const size_t m = n >> k1, tiles = m / 64, na = (size_t)1 << (k2 - s2), nb = (size_t)1 << s2;
         ZK_TRY(c->reserve_ws((256 + na + nb + tiles + 16) * 32));
-        uint64_t* d_w1 = (uint64_t*)c->d_ws;
+        uint64_t* d_w1 = (uint64_t*)c->ws.ptr;
         uint64_t* d_wa = d_w1 + 4 * 256;
         uint64_t* d_wb = d_wa + 4 * na;
         uint64_t* d_rec = d_wb + 4 * nb;
@@ -483,9 +473,9 @@ static int upload_gates(zkhip_ctx* c, const uint8_t* h_gate_type, const uint32_t
         packed[3 * g + 2] = h_in1[g];
     }
     ZK_TRY(c->reserve_ws(12 * n_gates + 256));
-    ZK_HIP(c, hipMemcpyAsync(c->d_ws, packed.data(), 12 * n_gates, hipMemcpyHostToDevice, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(c->ws.ptr, packed.data(), 12 * n_gates, hipMemcpyHostToDevice, c->stream));
     ZK_HIP(c, hipStreamSynchronize(c->stream));   // `packed` is a stack temporary
-    *d_gates = (uint32_t*)c->d_ws;
+    *d_gates = (uint32_t*)c->ws.ptr;
     return ZKHIP_OK;
 }
 extern "C" int zkhip_circuit_layer_eval(zkhip_ctx* c, const uint64_t* d_in, size_t n_in, const uint8_t* h_gate_type,
@@ -574,44 +564,6 @@ static int launch_small(zkhip_ctx* c, const SmallArgs& a, SumcheckDev* st, uint6
     return ZKHIP_OK;
 }
 
-// the k-variable fold of a cn-entry table in the shape that suits its output size; returns the per-workgroup sums' count
-static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cur, size_t cn, uint32_t k, const uint64_t* d_w,
-                            uint64_t* dst, uint64_t* pdst, uint32_t* n_parts) {
-    const size_t m = cn >> k;
-    uint32_t out_per_wg;
-    // diagnostics: ZKHIP_MF=0 keeps the VALU form for an A/B on the same box (tools/ab_multifold.sh); ZKHIP_MF=r (1..9) sets the rotation of
-    // the term order (tile T starts at term r * T mod 2^k; the default 1 -- 3 and 5 measured the same, 0 = every wave at term 0: 108 vs 112 us
-    // before the aligned planes); ZKHIP_MF_OCC=n caps the workgroups per CU through the LDS request (all 1024 workgroups are resident at once as it is, 4 per CU; capped at 2 per CU
-    // or with 36-78 KiB requested per workgroup the pass takes the same 83-85 us, alone and beside the proofs in flight: round 6)
-    static const int mf_cfg = [] { const char* e = getenv("ZKHIP_MF"); return e ? atoi(e) : 1; }();
-    if (m >= 8192 && k >= 4 && mf_cfg != 0) {   // streaming shape, limb products on the matrix cores (mfma_fold.hpp)
-        out_per_wg = 64;
-        ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
-        const unsigned tiles = (unsigned)(m / 64), rot = (unsigned)(mf_cfg % 10);
-        static const int mf_occ = [] { const char* e = getenv("ZKHIP_MF_OCC"); return e ? atoi(e) : 0; }();
-        size_t q_bytes = mfm_lds_bytes(std::min<uint32_t>(1u << k, (uint32_t)MFM_CHUNK));
-        if (mf_occ > 0) q_bytes = std::max(q_bytes, (size_t)(((158 * 1024 / mf_occ) - 1024) & ~255));
-        if (q_bytes > 64 * 1024) ZK_TRY(c->allow_big_lds((const void*)multifold_mfma_kernel<4, 4>, 158 * 1024));   // (the kernel has ~0.6 KiB of static LDS on top)
-        hipLaunchKernelGGL((multifold_mfma_kernel<4, 4>), dim3(tiles / 4), dim3(256), q_bytes, stream, cur, m, k, d_w, dst, pdst, rot);
-    } else if (m >= 8192) {   // streaming shape: 64 outputs per workgroup, its waves split the terms
-        out_per_wg = 64;
-        // >= 64 terms per lane: every lane pays one 9-word reduction (~a product), which at 16 terms per lane made the
-        // 6-variable fold of the overlapped plan 12 % slower than the 8-variable one
-        const uint32_t waves = k >= 8 ? 4 : k == 7 ? 2 : 1;
-        ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
-        hipLaunchKernelGGL((multifold_kernel<64, 4, true>), dim3((unsigned)(m / 64)), dim3(64 * waves), ((size_t)32 << k) + 32 * (size_t)(waves - 1) * 64,
-                           stream, cur, m, k, d_w, dst, pdst);
-    } else {                  // few outputs left: 16 per workgroup, up to 64 lanes share one output
-        out_per_wg = 16;
-        uint32_t waves = 16;
-        while (waves * 4 > (1u << k)) waves >>= 1;   // at least one term per lane group (k >= 3 here)
-        ProfScope ps(c, "multifold_small", 32.0 * (double)cn + 32.0 * (double)m, stream);
-        hipLaunchKernelGGL(multifold_kernel<16>, dim3((unsigned)(m / 16)), dim3(64 * waves), ((size_t)32 << k) + 32 * (size_t)(waves - 1) * 16, stream, cur, m, k, d_w, dst, pdst);
-    }
-    ZK_HIP(c, hipGetLastError());
-    if (n_parts) *n_parts = (uint32_t)(m / out_per_wg);
-    return ZKHIP_OK;
-}
 // k-variable fold of a small table spread over the chip: partial tables P[y][m], y < *n_slices (blockfold_kernel)
 struct BlockfoldShape { uint32_t log_ow, per, ny; };
 // OW outputs x (1024 / OW) term slices per workgroup; at least one term per slice; ny partial tables come out
@@ -697,7 +649,7 @@ static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint
     if (log_blocks > (uint32_t)MF_CAP_LOGK) {      // fine sums (the overlapped prover's granularity)
         if (m < (size_t)FINE_CHUNK) return ZKHIP_ERR_SHAPE;
         uint64_t* d_chunk = nullptr;
-        if (m > (size_t)FINE_CHUNK) { ZK_TRY(c->reserve_ws((n / FINE_CHUNK) * 32)); d_chunk = (uint64_t*)c->d_ws; }
+        if (m > (size_t)FINE_CHUNK) { ZK_TRY(c->reserve_ws((n / FINE_CHUNK) * 32)); d_chunk = (uint64_t*)c->ws.ptr; }
         ZK_TRY(launch_fine_sums(c, d_evals, n, log_blocks, d_out, d_chunk));
         // With the total: coarse sums at the granularity the prover's first rounds want (kept for it in the context's ring), then the
         // total from those.  Without (the deferred form): nothing more here -- the prover derives the coarse sums itself, on the
@@ -711,7 +663,7 @@ static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint
             const uint32_t k1 = overlapped_plan(n) && log_blocks == log2_exact(n) - 8 ? log_blocks - overlapped_k2(n) : 8;
             int cs = 0;
             ZK_TRY(c->next_coarse(&cs));
-            uint64_t* coarse_canon = (uint64_t*)c->d_coarse[cs], *coarse_mont = coarse_canon + 4 * 1024;
+            uint64_t* coarse_canon = (uint64_t*)c->d_coarse[cs].get(), *coarse_mont = coarse_canon + 4 * 1024;
             {
                 ProfScope ps(c, "coarse_sums", 0.0);
                 hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << k1), dim3(MLE_BLOCK), 0, c->stream, d_out, 1u << (log_blocks - k1), coarse_mont, coarse_canon);
@@ -727,7 +679,7 @@ static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint
         const size_t n_chunks = n / chunk;
         uint64_t* d_partials;
         if (n_chunks <= 8 * (size_t)ZK_MAX_PARTIALS) d_partials = c->small_u64(ZK_SMALL_PARTIALS);
-        else { ZK_TRY(c->reserve_ws(n_chunks * 32)); d_partials = (uint64_t*)c->d_ws; }
+        else { ZK_TRY(c->reserve_ws(n_chunks * 32)); d_partials = (uint64_t*)c->ws.ptr; }
         if (chunk >= (uint32_t)MLE_BLOCK) {
             ProfScope ps(c, "chunk_sums", 32.0 * (double)n);
             hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)n_chunks), dim3(MLE_BLOCK), 0, c->stream, d_evals, chunk, d_partials);
@@ -769,14 +721,14 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
     uint64_t *ws, *small;
     if (lane < 0) {
         ZK_TRY(c->reserve_ws(ws_need));
-        ws = (uint64_t*)c->d_ws; small = (uint64_t*)c->d_small; S = c->stream;
-        if (overlap) { ZK_TRY(c->ensure_fold_stream()); F = c->fold_stream; fork_ev = c->fork_ev; serial_ev = c->serial_ev; }
+        ws = (uint64_t*)c->ws.ptr; small = (uint64_t*)c->d_small.get(); S = c->stream;
+        if (overlap) { ZK_TRY(c->ensure_fold_stream()); F = c->fold_stream.get(); fork_ev = c->fork_ev.get(); serial_ev = c->serial_ev.get(); }
     } else {
         ZK_TRY(c->ensure_lane(lane, ws_need));
         zkhip_ctx::ProofLane& L = c->lanes[lane];
-        ws = (uint64_t*)L.ws; small = (uint64_t*)L.small; S = L.serial; F = L.fold; fork_ev = L.fork_ev; serial_ev = L.serial_ev;
-        ZK_HIP(c, hipEventRecord(L.begin_ev, c->stream));          // the table, its block sums and the claimed sum are ready behind this
-        ZK_HIP(c, hipStreamWaitEvent(S, L.begin_ev, 0));
+        ws = (uint64_t*)L.ws.ptr; small = (uint64_t*)L.small.get(); S = L.serial; F = L.fold; fork_ev = L.fork_ev.get(); serial_ev = L.serial_ev.get();
+        ZK_HIP(c, hipEventRecord(L.begin_ev.get(), c->stream));          // the table, its block sums and the claimed sum are ready behind this
+        ZK_HIP(c, hipStreamWaitEvent(S, L.begin_ev.get(), 0));
     }
     uint64_t* tabA = ws;
     uint64_t* tabB = tabA + 4 * tabA_entries;
@@ -793,7 +745,7 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
     uint64_t* d_fin = small + ZK_SMALL_RES;
     // the proof leaves through the LAST serial kernel: it writes [sum .. round polynomials] into the pinned slot itself (SmallArgs::host_delta)
     ZK_TRY(c->ensure_proof_slot(slot));
-    const long long host_delta = ((long long)(intptr_t)c->proof_pin[slot] - (long long)(intptr_t)(small + ZK_SMALL_STATE)) / 8;
+    const long long host_delta = ((long long)(intptr_t)c->proof_pin[slot].get() - (long long)(intptr_t)(small + ZK_SMALL_STATE)) / 8;
 
     FrArg claimed = {};
     uint32_t first = 1;
@@ -816,8 +768,8 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
             const bool on_callers = lane >= 0 && in_flight >= 3;
             ZK_TRY(launch_fine_sums(c, d_evals, n, g, d_fine, nullptr, on_callers ? c->stream : S));
             if (on_callers) {
-                ZK_HIP(c, hipEventRecord(c->lanes[lane].begin_ev, c->stream));
-                ZK_HIP(c, hipStreamWaitEvent(S, c->lanes[lane].begin_ev, 0));
+                ZK_HIP(c, hipEventRecord(c->lanes[lane].begin_ev.get(), c->stream));
+                ZK_HIP(c, hipStreamWaitEvent(S, c->lanes[lane].begin_ev.get(), 0));
             }
             fine = d_fine;
         }
@@ -830,9 +782,9 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
         if (cs < 0) {
             ZK_TRY(c->next_coarse(&cs));
             ProfScope ps(c, "coarse_sums", 0.0, S);
-            hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << k1), dim3(MLE_BLOCK), 0, S, fine, 1u << k2, (uint64_t*)nullptr, (uint64_t*)c->d_coarse[cs]);
+            hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << k1), dim3(MLE_BLOCK), 0, S, fine, 1u << k2, (uint64_t*)nullptr, (uint64_t*)c->d_coarse[cs].get());
         }
-        const uint64_t* coarse = (const uint64_t*)c->d_coarse[cs];
+        const uint64_t* coarse = (const uint64_t*)c->d_coarse[cs].get();
         c->coarse_of[cs] = nullptr;                 // the entry belongs to this proof from here on:
         c->coarse_owner[cs] = slot + 1;             // the ring skips it until the proof has been collected (sumcheck_collect / prove_end)
         SmallArgs a = {};
@@ -873,7 +825,7 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
                 t.src = d_p2; t.group = ny2; t.stride = 256; t.canon = 1; t.log_n = 8; t.n_rounds = 8; t.round0 = g; t.first = 0;
                 t.weights_out = nullptr; t.final_out = d_fin; t.host_delta = host_delta;
                 ZK_TRY(launch_small(c, t, st, d_rp, d_ch, 0, S));
-                ZK_HIP(c, hipEventRecord(c->proof_ev[slot], S));
+                ZK_HIP(c, hipEventRecord(c->proof_ev[slot].get(), S));
                 return ZKHIP_OK;
             });
             // how many second halves stay back: enough sums passes in front of a fold that its proof's first rounds are over when its turn
@@ -938,16 +890,16 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
     }
     // results -> host: written by the last kernel into the pinned slot (no copy launch); the collector polls the event behind it
     // the event the collector polls; the caller's stream stays ordered behind the proof (the next call reuses the scratch)
-    ZK_HIP(c, hipEventRecord(c->proof_ev[slot], tail_stream));
+    ZK_HIP(c, hipEventRecord(c->proof_ev[slot].get(), tail_stream));
     // (a proof on a lane of its own is joined to the caller's stream when it is collected, so that the caller's next poly_sum() does not wait for it)
-    if (lane < 0 && tail_stream != c->stream) ZK_HIP(c, hipStreamWaitEvent(c->stream, c->proof_ev[slot], 0));
+    if (lane < 0 && tail_stream != c->stream) ZK_HIP(c, hipStreamWaitEvent(c->stream, c->proof_ev[slot].get(), 0));
     return ZKHIP_OK;
 }
 static int sumcheck_collect(zkhip_ctx* c, int slot, uint32_t n_vars, uint64_t* h_sum, uint64_t* h_round_polys, uint64_t* h_challenges) {
-    const int wrc = c->wait_event(c->proof_ev[slot]);
+    const int wrc = c->wait_event(c->proof_ev[slot].get());
     c->release_coarse(slot);                    // the proof's kernels are done with their coarse sums (or the device is lost)
     ZK_TRY(wrc);
-    const uint64_t* pin = (const uint64_t*)c->proof_pin[slot];
+    const uint64_t* pin = (const uint64_t*)c->proof_pin[slot].get();
     const uint64_t* span = c->small_u64(ZK_SMALL_STATE);
     const SumcheckDev* st = (const SumcheckDev*)c->small_u64(ZK_SMALL_STATE);
     std::memcpy(h_sum, pin + ((const uint64_t*)st->sum - span), 32);
@@ -1017,8 +969,8 @@ extern "C" int zkhip_sumcheck_prove_end(zkhip_ctx* c, uint32_t ticket, uint64_t*
     }
     if (rc == ZKHIP_OK) {
         if (h_sum && h_round_polys && h_challenges) rc = sumcheck_collect(c, (int)ticket, n_vars, h_sum, h_round_polys, h_challenges);
-        else { rc = c->wait_event(c->proof_ev[ticket]); c->release_coarse((int)ticket); }   // abandoned: just wait it out
-        if (hipStreamWaitEvent(c->stream, c->proof_ev[ticket], 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // the caller's stream is ordered behind the proof again
+        else { rc = c->wait_event(c->proof_ev[ticket].get()); c->release_coarse((int)ticket); }   // abandoned: just wait it out
+        if (hipStreamWaitEvent(c->stream, c->proof_ev[ticket].get(), 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // the caller's stream is ordered behind the proof again
     }
     c->proof_pending[ticket] = 0;
     return rc;
@@ -1035,8 +987,10 @@ struct zkhip_sc_state {
     uint64_t* small;         // [SumcheckDev 64 u64][round polys 8*R][challenges 4*R][partials 8*MLE_MAX_GRID][tail 4*TAIL_N]
     uint32_t round, np;
     bool partials_valid;
-    bool owns_tables;        // false: A/B live in the context workspace (the common, single-state case)
-    bool uses_cache;         // small + stage buffers borrowed from the context
+    // A/B, small and stage_buf are views: of the context's workspace (ws_loan held; the common, single-state case) or of own_tables, and
+    // of the context's cached pair (sc_loan held) or of own_small / own_stage
+    DevMem own_tables, own_small, own_stage;
+    ZkLoan ws_loan, sc_loan;
     // stage form
     uint64_t* stage_buf;     // [weights 4*512][partials X 4*P][partials Y 4*P][block sums 4*513]
     size_t stage_parts_cap;
@@ -1064,41 +1018,34 @@ extern "C" int zkhip_sc_begin(zkhip_ctx* c, const uint64_t* d_local, size_t n_lo
     if (!c || !d_local || !out) return ZKHIP_ERR_ARG;
     if (!is_pow2(n_local)) return ZKHIP_ERR_SHAPE;
     ZK_TRY(c->activate());
-    zkhip_sc_state* st = new zkhip_sc_state();
+    std::unique_ptr<zkhip_sc_state> st(new zkhip_sc_state());      // an error exit releases what the state owns and returns its loans
     st->c = c; st->cur = d_local; st->cn = n_local; st->round = 0; st->np = 0; st->partials_valid = false;
-    st->A = st->B = st->small = nullptr;
+    st->A = st->B = st->small = st->stage_buf = nullptr;
     const size_t small_u64 = 64 + 12 * (size_t)ZK_MAX_ROUNDS + 8 * (size_t)MLE_MAX_GRID + 16;
     st->stage_parts_cap = std::max<size_t>(n_local / 256, 64) + 64;
-    st->uses_cache = false;
-    if (!c->sc_lent && c->sc_small && c->sc_stage_cap >= st->stage_parts_cap) {
-        st->small = (uint64_t*)c->sc_small;
-        st->stage_buf = (uint64_t*)c->sc_stage;
+    if (!c->sc_loans.lent() && c->sc_small && c->sc_stage_cap >= st->stage_parts_cap) {
+        st->sc_loan = ZkLoan(c->sc_loans);
         st->stage_parts_cap = c->sc_stage_cap;
-        st->uses_cache = true;
-        c->sc_lent = true;
     } else {
-        if (hipMalloc(&st->small, small_u64 * 8) != hipSuccess) { delete st; return ZKHIP_ERR_NOMEM; }
-        st->stage_buf = nullptr;
-        if (hipMalloc(&st->stage_buf, (((size_t)1 << MF_CAP_LOGK) + 2 * st->stage_parts_cap + ((size_t)1 << MF_CAP_LOGK) + 1 + 8) * 32) != hipSuccess) {
-            hipFree(st->small); delete st; return ZKHIP_ERR_NOMEM;
-        }
+        if (dev_alloc(st->own_small, small_u64 * 8) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        if (dev_alloc(st->own_stage, (((size_t)1 << MF_CAP_LOGK) + 2 * st->stage_parts_cap + ((size_t)1 << MF_CAP_LOGK) + 1 + 8) * 32) != hipSuccess) return ZKHIP_ERR_NOMEM;
     }
-    st->owns_tables = false;
+    st->small = (uint64_t*)(st->sc_loan ? c->sc_small : st->own_small).get();
+    st->stage_buf = (uint64_t*)(st->sc_loan ? c->sc_stage : st->own_stage).get();
     if (n_local >= 2) {
         const size_t bytes = (n_local / 2 + n_local / 4 + 4) * 32;
-        if (!c->ws_lent) {               // steady state: no allocation per prove
-            int rc = c->reserve_ws(bytes);
-            if (rc != ZKHIP_OK) { if (st->uses_cache) c->sc_lent = false; else { hipFree(st->small); hipFree(st->stage_buf); } delete st; return rc; }
-            st->A = (uint64_t*)c->d_ws;
-            c->ws_lent = true;
+        if (!c->ws_loans.lent()) {       // steady state: no allocation per prove
+            ZK_TRY(c->reserve_ws(bytes));
+            st->A = (uint64_t*)c->ws.ptr;
+            st->ws_loan = ZkLoan(c->ws_loans);
         } else {                         // several states alive at once (tests drive shards in lockstep)
-            if (hipMalloc(&st->A, bytes) != hipSuccess) { if (st->uses_cache) c->sc_lent = false; else { hipFree(st->small); hipFree(st->stage_buf); } delete st; return ZKHIP_ERR_NOMEM; }
-            st->owns_tables = true;
+            if (dev_alloc(st->own_tables, bytes) != hipSuccess) return ZKHIP_ERR_NOMEM;
+            st->A = (uint64_t*)st->own_tables.get();
         }
     }
     st->B = st->A ? st->A + 4 * (n_local / 2) : nullptr;
     st->stage_k_cur = 0; st->stage_world = 1; st->stage_idx = 0; st->n_parts = 0; st->parts = nullptr;
-    *out = st;
+    *out = st.release();
     return ZKHIP_OK;
 }
 
@@ -1251,10 +1198,10 @@ extern "C" int zkhip_sc_overlap_rounds1(zkhip_sc_state* st, const uint64_t* d_ga
     uint32_t ny = 0, n_parts = 0;
     ZK_TRY(launch_blockfold(c, c->stream, st->ov_fine(), 1u << k2, k1, st->ov_w1(), d_mid, &ny));
     if (ny != st->ov_ny1) return ZKHIP_ERR_SHAPE;
-    ZK_HIP(c, hipEventRecord(c->fork_ev, c->stream));
-    ZK_HIP(c, hipStreamWaitEvent(c->fold_stream, c->fork_ev, 0));
-    ZK_TRY(launch_multifold(c, c->fold_stream, st->cur, st->cn, k1, st->ov_w1(), st->A, st->spx(), &n_parts));
-    ZK_HIP(c, hipEventRecord(c->join_ev, c->fold_stream));
+    ZK_HIP(c, hipEventRecord(c->fork_ev.get(), c->stream));
+    ZK_HIP(c, hipStreamWaitEvent(c->fold_stream.get(), c->fork_ev.get(), 0));
+    ZK_TRY(launch_multifold(c, c->fold_stream.get(), st->cur, st->cn, k1, st->ov_w1(), st->A, st->spx(), &n_parts));
+    ZK_HIP(c, hipEventRecord(c->join_ev.get(), c->fold_stream.get()));
     st->round = k1;
     st->ov_phase = 2;
     return ZKHIP_OK;
@@ -1272,7 +1219,7 @@ extern "C" int zkhip_sc_overlap_rounds2(zkhip_sc_state* st, const uint64_t* d_ga
     // no exclusive-CU request here (cf. sumcheck_enqueue): the exchange puts this launch tens of microseconds behind the fold's
     // start, the chip is full by then and a whole free CU only appears when the fold drains
     ZK_TRY(launch_small(c, b, st->dev(), st->rp(), st->ch()));
-    ZK_HIP(c, hipStreamWaitEvent(c->stream, c->join_ev, 0));
+    ZK_HIP(c, hipStreamWaitEvent(c->stream, c->join_ev.get(), 0));
     uint32_t ny = 0;
     ZK_TRY(launch_blockfold(c, c->stream, st->A, 256, k2, st->ov_w2(), st->ov_p2(), &ny));
     if (ny > 32) return ZKHIP_ERR_SHAPE;
@@ -1379,26 +1326,17 @@ extern "C" int zkhip_sc_tail(zkhip_sc_state* st, const uint64_t* d_values, uint3
     st->round += a.log_n;
     return ZKHIP_OK;
 }
-// releases a state's buffers and the context's loan flags
-static void sc_release(zkhip_sc_state* st) {
+// ends a state: its loans go back, and its own small / stage pair goes to the context's cache or away
+static void sc_release(zkhip_sc_state* raw) {
+    std::unique_ptr<zkhip_sc_state> st(raw);
     zkhip_ctx* c = st->c;
-    if (st->A && st->owns_tables) hipFree(st->A);
-    if (st->A && !st->owns_tables) c->ws_lent = false;
-    if (st->uses_cache) {
-        c->sc_lent = false;
-    } else if (!c->sc_small) {           // keep this set for the next prove instead of freeing it
-        c->sc_small = st->small; c->sc_stage = st->stage_buf; c->sc_stage_cap = st->stage_parts_cap;
-    } else if (!c->sc_lent && st->stage_parts_cap > c->sc_stage_cap) {
-        // the cached set is too small for shards of this size (a steady stream of them would allocate and free per prove): this larger
-        // set replaces it.  (The caller has waited for the stream: finish / abort synchronise before they release.)
-        hipFree(c->sc_small);
-        if (c->sc_stage) hipFree(c->sc_stage);
-        c->sc_small = st->small; c->sc_stage = st->stage_buf; c->sc_stage_cap = st->stage_parts_cap;
-    } else {
-        hipFree(st->small);
-        if (st->stage_buf) hipFree(st->stage_buf);
+    if (st->sc_loan) return;
+    // the first finished state's set is kept for the next prove instead of being freed; and when the cached set (not in use) is too small
+    // for shards of this size (a steady stream of them would allocate and free per prove) this larger set replaces it.  (The caller has
+    // waited for the stream: finish / abort synchronise before they release.)
+    if (!c->sc_small || (!c->sc_loans.lent() && st->stage_parts_cap > c->sc_stage_cap)) {
+        c->sc_small = std::move(st->own_small); c->sc_stage = std::move(st->own_stage); c->sc_stage_cap = st->stage_parts_cap;
     }
-    delete st;
 }
 extern "C" int zkhip_sc_finish(zkhip_sc_state* st, uint64_t* h_sum, uint64_t* h_rp, uint64_t* h_ch, uint32_t* n_rounds) {
     if (!st) return ZKHIP_ERR_ARG;
@@ -1411,7 +1349,7 @@ extern "C" int zkhip_sc_finish(zkhip_sc_state* st, uint64_t* h_sum, uint64_t* h_
     uint64_t* pin = c->pinned_u64(ZK_PIN_PROOF);
     if (rc == ZKHIP_OK && hipMemcpyAsync(pin, st->small, 8 * span, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
     if (hipStreamSynchronize(c->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    if (st->ov_phase == 2 && c->fold_stream && hipStreamSynchronize(c->fold_stream) != hipSuccess) rc = ZKHIP_ERR_HIP;   // un-joined fold (see zkhip_sc_abort)
+    if (st->ov_phase == 2 && c->fold_stream.get() && hipStreamSynchronize(c->fold_stream.get()) != hipSuccess) rc = ZKHIP_ERR_HIP;   // un-joined fold (see zkhip_sc_abort)
     if (rc == ZKHIP_OK) {
         if (h_sum) std::memcpy(h_sum, pin + ((const uint64_t*)st->dev()->sum - st->small), 32);
         if (h_rp && st->round) std::memcpy(h_rp, pin + 64, 64 * (size_t)st->round);
@@ -1429,7 +1367,7 @@ extern "C" int zkhip_sc_abort(zkhip_sc_state* st) {
     // between zkhip_sc_overlap_rounds1 and _rounds2 the shard's k1-variable fold runs on the fold stream and is joined to
     // c->stream only inside _rounds2: an abort in that window must wait for it too (it reads the caller's table and writes the
     // workspace and the cached stage buffer that sc_release hands back)
-    if (c->fold_stream && hipStreamSynchronize(c->fold_stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
+    if (c->fold_stream.get() && hipStreamSynchronize(c->fold_stream.get()) != hipSuccess) rc = ZKHIP_ERR_HIP;
     sc_release(st);
     return rc;
 }
@@ -1467,7 +1405,7 @@ extern "C" int zkhip_transcript_challenge(zkhip_ctx* c, const uint8_t* h_prefix3
     for (size_t w = 0; w < words.size(); ++w)
         words[w] = ((uint32_t)msg[4 * w] << 24) | ((uint32_t)msg[4 * w + 1] << 16) | ((uint32_t)msg[4 * w + 2] << 8) | msg[4 * w + 3];
     ZK_TRY(c->reserve_ws(4 * words.size() + 64));
-    uint32_t* d_words = (uint32_t*)c->d_ws;
+    uint32_t* d_words = (uint32_t*)c->ws.ptr;
     uint32_t* d_digest = d_words + words.size();
     ZK_HIP(c, hipMemcpyAsync(d_words, words.data(), 4 * words.size(), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(zk::transcript_blocks_kernel, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)d_words, (uint32_t)n_blocks, d_digest);
