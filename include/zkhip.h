@@ -665,6 +665,53 @@ int zkhip_pointwise_mul(zkhip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b
 int zkhip_univariate_multiply(zkhip_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb,
                               uint64_t *d_out);
 
+/* ---- PLONK (plonk/src/protocol/{prover,verifier,utils,transcript}.rs over transcripts/merlin/src/lib.rs) ---------------------
+ * Layouts shared by the four calls below:
+ *   columns    : eight n-entry evaluation-form columns in the order of VerifierPreprocessedInput::vpi (verifier.rs:24-36):
+ *                q_m, q_l, q_r, q_o, q_c, sigma_1, sigma_2, sigma_3;
+ *   points     : nine G1 points in the order of PlonkProof (primitives.rs:49-65): as, bs, cs, accumulator, t_low, t_mid, t_high,
+ *                w_zeta, w_zeta_omega  (xy[9 * 12], inf[9]);
+ *   evals      : a_s, b_s, c_s, sigma1, sigma2, w_accumulator at zeta (Fr, [6 * 4]);
+ *   challenges : beta, gamma, alpha, zeta, nu, mu (Fr, [6 * 4]).
+ * n = group_order: a power of two, n >= 4, with the quotient's coset D = next_pow2(3 n + 6) <= 2^30 -> else ZKHIP_ERR_SHAPE.
+ *
+ * zkhip_plonk_key_create: CommonPreprocessedInput (compiler/primitives.rs:6-16) made resident.  h_column_ptrs: a HOST array of the eight
+ *   DEVICE columns (copied: the caller may free them).  The G1 SRS is given as points (d_points_xy) or as its zkhip_srs_precompute
+ *   table (d_table; then d_points_xy may be NULL), n_points >= n + 6 -- the longest committed polynomial, t_high, has n + 6
+ *   coefficients; fewer is the reference's index panic (univariate_kzg.rs:53) -> ZKHIP_ERR_INDEX.  The SRS buffers are NOT copied and
+ *   must outlive the key.  The handle owns the columns in evaluation and coefficient form, the tables w^i, g^i, g^-i of the coset shift
+ *   g = 7, and -- when they fit 2 GiB, i.e. up to n = 2^20 -- the coset evaluations of the columns, of L_1 and of X (ten vectors of D
+ *   elements; recomputed per proof above that), plus the work area of one proof: a key serves one zkhip_plonk_prove at a time.
+ *   Outputs: the handle and the eight commitments of vpi (h_commits_xy[8 * 12], h_commits_inf[8]).  Destroy the key before its context.
+ * zkhip_plonk_prove: PlonkProver::prove (prover.rs:39-96).  d_a, d_b, d_c, d_public: Witness (compiler/primitives.rs:23-28), n values
+ *   each.  h_blinding[11 * 4]: the scalars of generate_random_numbers in the order the reference draws them -- six in round 1
+ *   (:99-111), three in round 2 (:157-163), two in round 3 (:239-247); with them fixed the proof is a function of the inputs.
+ *   The four `/ zh_poly` quotients of third_round (:191-226) are taken as ONE exact division on the coset g <w_D>.  A witness that does
+ *   not satisfy the circuit -- a row that breaks the gate identity, a vanishing denominator of the grand product, an accumulator that
+ *   does not close, a numerator Z_H does not divide -- yields no proof: ZKHIP_ERR_ARG (the reference returns a proof that does not
+ *   verify).  Commits run three in flight (zkhip_kzg_commit_begin): the context's workspace must be free.  h_challenges may be NULL.
+ * zkhip_plonk_challenges: compute_verifier_challenges (protocol/utils.rs:56-96).  HOST ONLY, no GPU and no context.  The transcript is
+ *   the reference's byte for byte: SHA-256 over "Merlin Transcript" || "plonk_protocol"; append_message = label || len as 8 bytes LE ||
+ *   message; a scalar is its 32-byte LE canonical form, a point the UTF-8 of "(x, y)" in decimal ("infinity" for the identity);
+ *   challenge(label) finalises, RESETS the hasher and absorbs the label -- so gamma is a constant and every later challenge sees
+ *   only what was appended since the previous one.
+ * zkhip_plonk_verify: PlonkVerifier::verify (verifier.rs:62-172): *h_ok = 1 iff e(left, tau G2) == e(right, G2) as GT values.
+ *   h_vk_xy / h_vk_inf: the eight commitments of vpi; d_public: the public-input column (n values); d_g2_xy / d_g2_inf: the SRS's G2
+ *   half, n_g2 < 2 -> ZKHIP_ERR_INDEX (powers_of_tau_in_g2[1], verifier.rs:34).  A proof or key point off the curve or outside the
+ *   subgroup, or an evaluation that is not a reduced field element -> ZKHIP_ERR_ARG. */
+typedef struct zkhip_plonk_key zkhip_plonk_key;
+int zkhip_plonk_key_create(zkhip_ctx *ctx, size_t n, const uint64_t *const *h_column_ptrs, const uint64_t *d_points_xy,
+                           const void *d_table, const uint8_t *d_points_inf, size_t n_points, zkhip_plonk_key **out,
+                           uint64_t *h_commits_xy, uint8_t *h_commits_inf);
+int zkhip_plonk_key_destroy(zkhip_plonk_key *key);
+int zkhip_plonk_prove(zkhip_plonk_key *key, const uint64_t *d_a, const uint64_t *d_b, const uint64_t *d_c, const uint64_t *d_public,
+                      const uint64_t *h_blinding, uint64_t *h_points_xy, uint8_t *h_points_inf, uint64_t *h_evals,
+                      uint64_t *h_challenges);
+int zkhip_plonk_challenges(const uint64_t *h_points_xy, const uint8_t *h_points_inf, const uint64_t *h_evals, uint64_t *h_challenges);
+int zkhip_plonk_verify(zkhip_ctx *ctx, size_t n, const uint64_t *h_vk_xy, const uint8_t *h_vk_inf, const uint64_t *h_points_xy,
+                       const uint8_t *h_points_inf, const uint64_t *h_evals, const uint64_t *d_public, const uint64_t *d_g2_xy,
+                       const uint8_t *d_g2_inf, size_t n_g2, uint8_t *h_ok);
+
 #ifdef __cplusplus
 }
 #endif

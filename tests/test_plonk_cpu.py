@@ -1,0 +1,210 @@
+"""CPU: the independent PLONK model (tests/plonk_model.py) on the reference's own programs (plonk/src/protocol/verifier.rs:188-262),
+the package's host-side compiler and Merlin transcript against it, and zkhip_plonk_challenges (host-only C) against the model's
+challenges.  No GPU call is made."""
+import ctypes as C
+import hashlib
+import os
+import random
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import plonk_model as PL  # noqa: E402
+
+M, PM, R = PL.M, PL.PM, PL.R
+TAU = 6
+BLIND = [random.Random(11).randrange(R) for _ in range(11)]
+PROGRAM_1 = (["e public"], {"e": 3})
+PROGRAM_2 = (["x public", "c <== a * b", "f <== d * e", "g <== c + f", "x <== g * y"], {"x": 258, "a": 2, "b": 4, "d": 5, "e": 7, "y": 6})
+
+
+def compile_with_package(constraints, assignment, n=8):
+    import zk_cryptography_amd.plonk as zp
+    program = zp.Program([zp.AssemblyEqn.eq_to_assembly(eq) for eq in constraints], n)
+    wit = program.compute_witness_and_public_poly(dict(assignment))
+    cpi = program.common_preprocessed_input()
+    return ({f: getattr(cpi, f) for f in PL.CPI_FIELDS} | {"group_order": n},
+            {"a": wit.a, "b": wit.b, "c": wit.c, "public_poly": wit.public_poly})
+
+
+def program_1_by_hand():
+    """["e public"], e = 3, written out from compiler/{assembly,program}.rs without the package: one row  1 * e + PI = 0"""
+    n, w = 8, PL.roots_of_unity(8)
+    zeros = [0] * n
+    cells = [(1, 0), (2, 0)] + [(col, row) for row in range(1, n) for col in range(3)]          # the uses of `None`, in order
+    sig = [[w[i] for i in range(n)], zeros[:], zeros[:]]                                        # e is used once: (0, 0) maps to itself
+    for i, (col, row) in enumerate(cells):
+        ncol, nrow = cells[(i + 1) % len(cells)]
+        sig[ncol][nrow] = (col + 1) * w[row] % R
+    cpi = dict(group_order=n, q_l=[1] + zeros[1:], q_r=zeros, q_m=zeros, q_o=zeros, q_c=zeros, sigma_1=sig[0], sigma_2=sig[1], sigma_3=sig[2])
+    wit = dict(a=[3] + zeros[1:], b=zeros, c=zeros, public_poly=[R - 3] + zeros[1:])
+    return cpi, wit
+
+
+@pytest.fixture(scope="module")
+def proved():
+    out = []
+    for constraints, assignment in (PROGRAM_1, PROGRAM_2):
+        cpi, wit = compile_with_package(constraints, assignment)
+        proof, ch = PL.prove(cpi, wit, TAU, BLIND, n_srs=4 * 8 + 1, want_challenges=True)
+        out.append((cpi, wit, proof, ch, PL.vpi(cpi, TAU)))
+    return out
+
+
+def test_compiler_matches_the_hand_written_program():
+    cpi, wit = compile_with_package(*PROGRAM_1)
+    assert (cpi, wit) == program_1_by_hand()
+
+
+def test_model_proves_and_verifies_the_reference_programs(proved):       # verifier.rs:188-262: assert_eq!(is_valid, true)
+    for cpi, wit, proof, ch, v in proved:
+        assert PL.gate_identity_holds(cpi, wit)
+        assert PL.compute_verifier_challenges(proof) == ch
+        assert PL.verify(8, proof, v, wit["public_poly"]) is True
+        assert PL.verify_tau(8, proof, v, wit["public_poly"], TAU) is True
+        assert PL.fast_check(cpi, wit, TAU, BLIND, proof) == []            # the O(n) route agrees with the literal one
+
+
+def test_pairing_free_verdict_equals_the_pairing_verdict(proved):
+    """e(L, tau G2) == e(Rt, G2) <=> tau L == Rt: checked both ways on one tampered proof, then the cheap form serves the other tampers"""
+    cpi, wit, proof, ch, v = proved[1]
+    bad = PL.tamper(proof, "t_mid")
+    assert PL.verify(8, bad, v, wit["public_poly"]) is False
+    assert PL.verify_tau(8, bad, v, wit["public_poly"], TAU) is False
+
+
+@pytest.mark.parametrize("field", PL.PROOF_FIELDS)
+def test_each_field_tampered_alone_is_rejected(proved, field):
+    for cpi, wit, proof, ch, v in proved:
+        assert PL.verify_tau(8, PL.tamper(proof, field), v, wit["public_poly"], TAU) is False
+
+
+def test_short_srs_is_the_index_panic(proved):
+    cpi, wit = proved[1][0], proved[1][1]
+    with pytest.raises(IndexError):
+        PL.prove(cpi, wit, TAU, BLIND, n_srs=8 + 5)
+    PL.prove(cpi, wit, TAU, BLIND, n_srs=8 + 6)
+
+
+def test_compiler_asserts_of_the_reference():                              # program.rs:329-363
+    import zk_cryptography_amd.plonk as zp
+    program = zp.Program([zp.AssemblyEqn.eq_to_assembly(eq) for eq in ["c <== a * b", "b <== a * e"]], 8)
+    s1, s2, _ = program.make_s_polynomials()
+    w = PL.roots_of_unity(8)
+    assert zp.roots_of_unity(8) == w
+    assert s1[0] == w[1]
+    assert s2[0] == 3 * w[1] % R
+    program = zp.Program([zp.AssemblyEqn.eq_to_assembly(eq) for eq in ["e public", "c <== a * b", "e <== c * d"]], 8)
+    l, r, m, o, c = program.make_gate_polynomials()
+    assert (l[:3], r[:3], m[:3], o[:3], c[:3]) == ([1, 0, 0], [0, 0, 0], [0, R - 1, R - 1], [0, 1, 1], [0, 0, 0])
+
+
+def test_compiler_panics_come_back_as_exceptions():
+    import zk_cryptography_amd.plonk as zp
+    E = zp.AssemblyEqn.eq_to_assembly
+    with pytest.raises(ValueError, match="Max 2 variables"):
+        E("d <== a * b + c")
+    with pytest.raises(ValueError, match="Disallowed multiplication"):
+        E("d <== a * a * b")
+    with pytest.raises(ValueError, match="Unsupported op"):
+        E("a >= b")
+    with pytest.raises(ValueError, match="Invalid out variable name"):
+        E("1a <== b * c")
+    with pytest.raises(ValueError, match="unwrap"):                        # a constant term: key_option.as_ref().unwrap()
+        E("c <== a + 5")
+    with pytest.raises(NotImplementedError):                               # todo!()
+        E("c <== 5")
+    program = zp.Program([E("c <== a * b"), E("c <== a + b")], 8)
+    with pytest.raises(ValueError, match="Inconsistent assignment"):
+        program.compute_witness({"a": 2, "b": 3})
+    with pytest.raises(ValueError, match="at the top"):
+        zp.Program([E("c <== a * b"), E("c public")], 8).get_public_assignment()
+    with pytest.raises(KeyError):                                          # out.get(&in_L).unwrap()
+        program.compute_witness({"a": 2})
+
+
+@pytest.mark.parametrize("constraints,assignment", [PROGRAM_1, PROGRAM_2,
+                                                    (["y public", "t <== x * x", "u <== t * x", "-v === u + x", "y <== v * v"], {"x": 3, "y": 900})])
+def test_compiled_columns_satisfy_gates_and_permutation(constraints, assignment):
+    n = 8
+    cpi, wit = compile_with_package(constraints, assignment, n)
+    assert PL.gate_identity_holds(cpi, wit)
+    w = PL.roots_of_unity(n)
+    labels = sorted(k * w[i] % R for k in (1, 2, 3) for i in range(n))
+    assert sorted(cpi["sigma_1"] + cpi["sigma_2"] + cpi["sigma_3"]) == labels          # a permutation of the identity labels
+    # copy constraints: a cell and the cell its sigma names hold the same value
+    value = {k * w[i] % R: col[i] for k, col in ((1, wit["a"]), (2, wit["b"]), (3, wit["c"])) for i in range(n)}
+    for k, (col, sig) in enumerate(((wit["a"], cpi["sigma_1"]), (wit["b"], cpi["sigma_2"]), (wit["c"], cpi["sigma_3"]))):
+        assert all(col[i] == value[sig[i]] for i in range(n))
+    proof = PL.prove(cpi, wit, TAU, BLIND)
+    assert PL.verify_tau(n, proof, PL.vpi(cpi, TAU), wit["public_poly"], TAU) is True
+
+
+@pytest.mark.parametrize("n", [8, 16])
+def test_random_circuits_are_satisfied_by_construction(n):
+    cpi, wit = PL.random_circuit(n, random.Random(n), random.Random(100 + n))
+    assert PL.gate_identity_holds(cpi, wit)
+    acc = PL.accumulator(cpi, wit, 5, 7)
+    assert acc == PL.fast_accumulator(cpi, wit, 5, 7)
+    proof = PL.prove(cpi, wit, TAU + n, BLIND)
+    assert PL.verify_tau(n, proof, PL.vpi(cpi, TAU + n), wit["public_poly"], TAU + n) is True
+    assert PL.fast_check(cpi, wit, TAU + n, BLIND, proof) == []
+    broken = dict(wit, a=[(wit["a"][0] + 1) % R] + wit["a"][1:])
+    assert not PL.gate_identity_holds(cpi, broken)
+
+
+# ---- the package's transcript and zkhip_plonk_challenges ----------------------------------------------------------------------------
+def test_package_merlin_equals_hashlib_on_the_reference_test():           # merlin/src/lib.rs:85-94
+    import zk_cryptography_amd.plonk as zp
+    t = zp.MerlinTranscript(b"test_protocol")
+    t.append_message(b"public_input", b"hello, world")
+    t.append_scalar(b"secret_scalar", 42)
+    h = hashlib.sha256(b"Merlin Transcript" + b"test_protocol" + b"public_input" + (12).to_bytes(8, "little") + b"hello, world"
+                       + b"secret_scalar" + (32).to_bytes(8, "little") + (42).to_bytes(32, "little"))
+    c = t.challenge(b"challenge")
+    assert c == int.from_bytes(h.digest(), "big") % R and c != 0
+    assert t.challenge(b"next") == int.from_bytes(hashlib.sha256(b"challenge").digest(), "big") % R      # the hasher was reset
+    m = PL.MerlinTranscript(b"test_protocol")
+    m.append_message(b"public_input", b"hello, world")
+    m.append_scalar(b"secret_scalar", 42)
+    assert m.challenge(b"challenge") == c
+    assert zp.point_to_string(None) == PL.point_to_string(None) == "infinity"
+    assert zp.point_to_string(M.G1) == PL.point_to_string(M.G1) == "(%d, %d)" % M.G1
+
+
+def _limbs(v, words):
+    return [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(words)]
+
+
+def _c_challenges(proof):
+    from zk_cryptography_amd import _native
+    _native.build()
+    lib = C.CDLL(_native.LIB_PATH)
+    xy, inf = np.zeros((9, 12), dtype=np.uint64), np.zeros(9, dtype=np.uint8)
+    for i, f in enumerate(PL.POINT_FIELDS):
+        if proof[f] is None:
+            inf[i] = 1
+        else:
+            xy[i] = _limbs(proof[f][0] * (1 << 384) % M.P, 6) + _limbs(proof[f][1] * (1 << 384) % M.P, 6)
+    ev = np.array([_limbs(proof[f] * (1 << 256) % R, 4) for f in PL.PROOF_FIELDS[7:13]], dtype=np.uint64)
+    ch = np.zeros((6, 4), dtype=np.uint64)
+    vp = C.c_void_p
+    rc = lib.zkhip_plonk_challenges(xy.ctypes.data_as(vp), inf.ctypes.data_as(vp), ev.ctypes.data_as(vp), ch.ctypes.data_as(vp))
+    assert rc == 0
+    rinv = pow(1 << 256, -1, R)
+    return tuple(sum(int(row[k]) << (64 * k) for k in range(4)) * rinv % R for row in ch)
+
+
+def test_c_challenges_equal_the_model(proved):
+    for cpi, wit, proof, ch, v in proved:
+        assert _c_challenges(proof) == ch
+    assert ch[1] == int.from_bytes(hashlib.sha256(b"beta").digest(), "big") % R        # gamma is a constant of the protocol
+
+
+def test_c_challenges_with_an_identity_point(proved):
+    proof = dict(proved[0][2], t_high=None, w_zeta_omega_commitment=None)            # not a valid proof; the transcript must still agree
+    assert _c_challenges(proof) == PL.compute_verifier_challenges(proof)
+    small = dict(proof, as_commitment=(0, 2), a_s_poly_zeta=0)                       # a zero coordinate prints as the empty string
+    assert _c_challenges(small) == PL.compute_verifier_challenges(small)

@@ -6,6 +6,7 @@ Host-side mirror (Python over ctypes) of the reference's Rust surfaces for the h
     kzg::{MultilinearKZG, UnivariateKZG}::{commitment, open, verify}, TrustedSetup (G1 and G2) -> .kzg
     circuit::Circuit, gkr::GKRProtocol::prove -> .gkr
     polynomial::univariate::{Domain, UnivariateEval} -> .univariate
+    plonk::{compiler, protocol}, merlin::MerlinTranscript -> .plonk
 Every operation runs hand-written HIP kernels in csrc/libzkhip.so through the C ABI of
 include/zkhip.h; there is no CPU fallback (a missing library or GPU raises).
 """
@@ -21,3 +22,5 @@ from zk_cryptography_amd.composed import (ComposedMultilinear, ComposedSumcheck,
 from zk_cryptography_amd.univariate import Domain, UnivariateEval  # noqa: F401
 from zk_cryptography_amd.gkr import (Circuit, CircuitLayer, DeviceFiatShamirTranscript, FiatShamirTranscript, Gate, GKRProof, GKRProtocol,  # noqa: F401
                                      SuccintGKRProof, SuccintGKRProtocol)
+from zk_cryptography_amd.plonk import (AssemblyEqn, CommonPreprocessedInput, MerlinTranscript, PlonkProof, PlonkProver,  # noqa: F401
+                                       PlonkRoundTranscript, PlonkVerifier, Program, VerifierPreprocessedInput, Witness)

@@ -362,3 +362,6 @@ struct ProfScope {
         if (on) hipEventRecord(c->prof_events[idx].stop.get(), s);
     }
 };
+
+// cross-unit internals (C++ linkage, not part of the C ABI)
+int zk_ntt_scaled_transform(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint64_t* d_mul, uint64_t* d_dst, uint32_t log_n);   // ntt.hip

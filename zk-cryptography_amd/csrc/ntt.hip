@@ -216,6 +216,17 @@ extern "C" int zkhip_domain_transform(zkhip_ctx* c, const uint64_t* d_src, size_
     return ntt_inplace(c, d_dst, log_n, inverse, (uint64_t*)c->ws.ptr);
 }
 
+// Coset hook of the PLONK prover (plonk.hip), transforms of >= 2^12 points: the forward transform of d_src[i] * d_mul[i], i < n_src,
+// zero beyond -- the coset scaling c_i g^i and the zero padding both happen in the first pass's gather.  d_mul holds n_src entries.
+int zk_ntt_scaled_transform(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint64_t* d_mul, uint64_t* d_dst, uint32_t log_n) {
+    if (!c || !d_src || !d_mul || !d_dst) return ZKHIP_ERR_ARG;
+    if (log_n < 12 || log_n > 30 || n_src > ((size_t)1 << log_n)) return ZKHIP_ERR_SHAPE;
+    const size_t n = (size_t)1 << log_n;
+    ZK_TRY(c->activate());
+    ZK_TRY(c->reserve_ws(n * 32));
+    return ntt_big(c, d_src, n_src, d_mul, d_dst, n, log_n, 0, (uint64_t*)c->ws.ptr);
+}
+
 extern "C" int zkhip_pointwise_mul(zkhip_ctx* c, const uint64_t* d_a, const uint64_t* d_b, size_t n, uint64_t* d_out) {
     if (!c || !d_a || !d_b || !d_out) return ZKHIP_ERR_ARG;
     ZK_TRY(c->activate());

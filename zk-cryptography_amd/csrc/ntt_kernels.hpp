@@ -163,7 +163,7 @@ static __global__ __launch_bounds__(MLE_BLOCK) void ntt_pass_table_kernel(const 
     }
 }
 
-// in: n_src <= n elements, zero beyond (coeffs.resize(size, F::zero()), domain.rs:109-110); in2 (nullable, n elements): the
+// in: n_src <= n elements, zero beyond (coeffs.resize(size, F::zero()), domain.rs:109-110); in2 (nullable, n_src elements): the
 // input is the element-wise product in * in2 (UnivariateEval::multiply's evaluation-form product, evaluation.rs:79-82,
 // fused into the inverse transform's gather)
 static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_first8_kernel(const uint64_t* __restrict__ in, size_t n_src,
@@ -177,7 +177,7 @@ static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_first8_kernel(const 
         const uint32_t o = (k << (log_n - 3)) | (g << 8) | q;
         const uint32_t src = bitrev(o, log_n);
         Fr v = src < n_src ? load_fr(in, src) : Fr::zero();
-        if (in2) v = v * load_fr(in2, src);
+        if (in2 && src < n_src) v = v * load_fr(in2, src);      // in2 is read where `in` is: it may be as short (the coset hook)
         tab[k * 256 + q] = v;
     }
     __syncthreads();

@@ -1,0 +1,613 @@
+// plonk.hip -- C-ABI entry points of the PLONK prover and verifier (plonk/src/protocol/{prover,verifier,utils,transcript}.rs,
+// transcripts/merlin/src/lib.rs).  gfx950 only; no CPU fallback for the prover.  The wire, selector and permutation polynomials stay on
+// the device for the whole call: the nine commitments, six evaluations and one status word cross to the host, where the Merlin
+// transcript (SHA-256 of a few hundred bytes per round) derives the challenges between the rounds.
+#include "../../include/zkhip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "ctx.hpp"
+#include "host_fr.hpp"
+#include "host_g1.hpp"
+#include "host_util.hpp"
+#include "plonk_kernels.hpp"
+
+using namespace zk;
+
+namespace {
+
+using HFr = zkhost::Fr;
+using zkhost::fr_add;
+using zkhost::fr_mul;
+using zkhost::fr_sub;
+
+inline HFr h_load(const uint64_t* p) { HFr r; std::memcpy(r.l, p, 32); return r; }
+inline FrArg fa(const HFr& a) { FrArg r; std::memcpy(r.v, a.l, 32); return r; }
+inline bool h_is_zero(const HFr& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
+inline bool h_eq(const HFr& a, const HFr& b) { return std::memcmp(a.l, b.l, 32) == 0; }
+inline HFr h_neg(const HFr& a) { return fr_sub(zkhost::fr_zero(), a); }
+inline HFr h_pow(HFr a, uint64_t e) {
+    HFr acc = zkhost::fr_one();
+    for (; e; e >>= 1) { if (e & 1) acc = fr_mul(acc, a); a = fr_mul(a, a); }
+    return acc;
+}
+
+// ---- MerlinTranscript (transcripts/merlin/src/lib.rs:11-49) and PlonkRoundTranscript (plonk/src/protocol/transcript.rs) ----------
+// canonical integer of a Montgomery Fq element in decimal, leading zeros trimmed (ark-ff 0.4.2 Display for Fp: zero prints as "")
+std::string fq_decimal(const uint64_t* mont) {
+    zkhost::Fq a, one = zkhost::fq_zero();
+    std::memcpy(a.l, mont, 48);
+    one.l[0] = 1;
+    zkhost::Fq c = zkhost::fq_mul(a, one);
+    std::string out;
+    for (;;) {
+        bool zero = true;
+        for (int i = 0; i < 6; ++i) zero = zero && c.l[i] == 0;
+        if (zero) break;
+        unsigned __int128 rem = 0;                                 // c /= 10^19
+        const uint64_t base = 10000000000000000000ull;
+        for (int i = 5; i >= 0; --i) {
+            const unsigned __int128 cur = (rem << 64) | c.l[i];
+            c.l[i] = (uint64_t)(cur / base);
+            rem = cur % base;
+        }
+        char buf[24];
+        snprintf(buf, sizeof buf, "%019llu", (unsigned long long)(uint64_t)rem);
+        out.insert(0, buf);
+    }
+    const size_t nz = out.find_first_not_of('0');
+    return nz == std::string::npos ? std::string() : out.substr(nz);
+}
+// ark-ec 0.4.2 Display for an affine point: "(x, y)", the identity "infinity"
+std::string point_string(const uint64_t* xy, bool inf) {
+    if (inf) return "infinity";
+    return "(" + fq_decimal(xy) + ", " + fq_decimal(xy + 6) + ")";
+}
+
+struct Merlin {
+    zkhost::Sha256 hasher;
+    explicit Merlin(const char* label) {                           // :12-21
+        hasher.update((const uint8_t*)"Merlin Transcript", 17);
+        hasher.update((const uint8_t*)label, std::strlen(label));
+    }
+    void append_message(const char* label, const uint8_t* m, size_t len) {   // :23-28 label, len as 8 bytes little-endian, message
+        hasher.update((const uint8_t*)label, std::strlen(label));
+        uint8_t le[8];
+        for (int i = 0; i < 8; ++i) le[i] = (uint8_t)((uint64_t)len >> (8 * i));
+        hasher.update(le, 8);
+        hasher.update(m, len);
+    }
+    void append_scalar(const char* label, const HFr& mont) {       // :30-35 serialize_compressed: 32 bytes little-endian canonical
+        const HFr c = zkhost::fr_from_mont(mont);
+        uint8_t b[32];
+        for (int i = 0; i < 32; ++i) b[i] = (uint8_t)(c.l[i / 8] >> (8 * (i % 8)));
+        append_message(label, b, 32);
+    }
+    void append_point(const char* label, const uint64_t* xy, bool inf) {     // :37-41 the UTF-8 of to_string()
+        const std::string s = point_string(xy, inf);
+        append_message(label, (const uint8_t*)s.data(), s.size());
+    }
+    HFr challenge(const char* label) {                             // :43-49 finalize_reset: the label goes into the EMPTY hasher
+        uint8_t d[32];
+        hasher.finish(d);
+        hasher.reset();
+        hasher.update((const uint8_t*)label, std::strlen(label));
+        uint64_t t[4];
+        for (int i = 0; i < 4; ++i) {
+            uint64_t w = 0;
+            for (int j = 0; j < 8; ++j) w = (w << 8) | d[8 * (3 - i) + j];
+            t[i] = w;
+        }
+        while (zkhost::fr_geq_p(t)) zkhost::fr_sub_p(t);            // from_be_bytes_mod_order
+        HFr c, r2;
+        std::memcpy(c.l, t, 32);
+        std::memcpy(r2.l, zkhost::FR_R2, 32);
+        return fr_mul(c, r2);
+    }
+};
+
+// proof layout of the ABI: points as, bs, cs, accumulator, t_low, t_mid, t_high, w_zeta, w_zeta_omega; evaluations a, b, c, sigma1,
+// sigma2, w_accumulator; challenges beta, gamma, alpha, zeta, nu, mu
+enum { P_AS, P_BS, P_CS, P_ACC, P_TL, P_TM, P_TH, P_WZ, P_WZW, N_POINTS };
+enum { E_A, E_B, E_C, E_S1, E_S2, E_ZW, N_EVALS };
+enum { C_BETA, C_GAMMA, C_ALPHA, C_ZETA, C_NU, C_MU, N_CHALLENGES };
+
+// ---- the key --------------------------------------------------------------------------------------------------------------------
+// Coset evaluations of the eight preprocessed columns, of L_1 and of X: ten vectors of D elements.  They are kept with the key up to
+// this budget -- at n = 2^20 (D = 2^22) they take 1.25 GiB, less than the 1.6 GiB shifted-SRS table the commits of that size already
+// hold -- and recomputed per proof (ten transforms) above it.
+constexpr size_t PLONK_CACHE_BUDGET = (size_t)2 << 30;
+constexpr int N_PRE = 10;
+const uint64_t COSET_SHIFT = 7;          // arkworks' multiplicative generator of Fr; the quotient does not depend on the choice
+
+}  // namespace
+
+struct zkhip_plonk_key {
+    zkhip_ctx* ctx = nullptr;
+    size_t n = 0, D = 0, S = 0;          // rows, coset size, stride of a coefficient vector (n + 8: room for the blinding, zero-padded)
+    uint32_t log_n = 0, log_D = 0, ratio = 0;
+    const uint64_t* srs_xy = nullptr; const void* srs_table = nullptr; const uint8_t* srs_inf = nullptr; size_t n_points = 0;   // views
+    DevMem evals, coeffs, omega, gpow, ginv, pre, work;
+    HFr w_n, zh_inv[8];
+    uint64_t* col_eval(int k) const { return (uint64_t*)evals.get() + 4 * n * k; }
+    uint64_t* col_coeff(int k) const { return (uint64_t*)coeffs.get() + 4 * S * k; }
+};
+
+namespace {
+
+// work area of one proof (elements of 32 bytes)
+struct Work {
+    uint64_t *A, *B, *C, *Z, *PI, *TL, *TM, *TH, *W, *Q1, *Q2, *F, *ACC;   // S each
+    uint64_t *ev, *T;                                                       // 5 D, D
+    uint64_t *bp, *bx, *hv, *hc, *out;                                      // block products / horner scratch / 8 results
+    int* flags;
+    uint64_t* pre;                                                          // 10 D when the key holds no cache
+    size_t zero_bytes;                                                      // the leading part a proof clears
+};
+size_t work_layout(const zkhip_plonk_key& k, char* base, bool with_pre, Work* w) {
+    size_t off = 0;
+    auto take = [&](size_t elems) { uint64_t* p = (uint64_t*)(base + off); off += (elems * 32 + 255) & ~(size_t)255; return p; };
+    const size_t nb = (k.S + GP_ROWS - 1) / GP_ROWS + 1, hb = (k.S + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L) + 1;
+    Work t;
+    uint64_t** s[] = {&t.A, &t.B, &t.C, &t.Z, &t.PI, &t.TL, &t.TM, &t.TH, &t.W, &t.Q1, &t.Q2, &t.F, &t.ACC};
+    for (auto p : s) *p = take(k.S);
+    t.flags = (int*)take(1);
+    t.zero_bytes = off;
+    t.bp = take(nb); t.bx = take(nb); t.hv = take(hb); t.hc = take(hb); t.out = take(8);
+    t.ev = take(5 * k.D); t.T = take(k.D);
+    t.pre = with_pre ? take((size_t)N_PRE * k.D) : nullptr;
+    if (w) *w = t;
+    return off;
+}
+
+// forward transform onto the coset g <w_D>: the scaling c_i g^i rides in the transform's first pass
+int coset_forward(const zkhip_plonk_key& k, const uint64_t* src, size_t n_src, uint64_t* dst) {
+    zkhip_ctx* c = k.ctx;
+    if (k.log_D >= 12) return zk_ntt_scaled_transform(c, src, n_src, (const uint64_t*)k.gpow.get(), dst, k.log_D);
+    hipLaunchKernelGGL(plonk_scale_pad_kernel, dim3(mle_grid_stream(k.D)), dim3(MLE_BLOCK), 0, c->stream, src, (const uint64_t*)k.gpow.get(), n_src, k.D, dst);
+    ZK_HIP(c, hipGetLastError());
+    return zkhip_domain_transform(c, dst, k.D, dst, k.log_D, 0);
+}
+
+int powers(zkhip_ctx* c, const HFr& base, const HFr& scale, size_t count, uint64_t* out) {
+    hipLaunchKernelGGL(plonk_powers_kernel, dim3(mle_grid_stream(count)), dim3(MLE_BLOCK), 0, c->stream, fa(base), fa(scale), count, out);
+    ZK_HIP(c, hipGetLastError());
+    return ZKHIP_OK;
+}
+
+// the ten coset columns: q_m, q_l, q_r, q_o, q_c, sigma_1..3, L_1 = ifft(1, 0, ..) = (1/n, 1/n, ..), X; tmp: k.S elements
+int fill_pre(const zkhip_plonk_key& k, uint64_t* pre, uint64_t* tmp) {
+    zkhip_ctx* c = k.ctx;
+    for (int j = 0; j < 8; ++j) ZK_TRY(coset_forward(k, k.col_coeff(j), k.n, pre + 4 * k.D * j));
+    const HFr n_inv = zkhost::fr_inv(zkhost::fr_from_u64((uint64_t)k.n));
+    ZK_TRY(powers(c, zkhost::fr_one(), n_inv, k.n, tmp));
+    ZK_TRY(coset_forward(k, tmp, k.n, pre + 4 * k.D * 8));
+    const HFr one = zkhost::fr_one();
+    ZK_HIP(c, hipMemsetAsync(tmp, 0, 32, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(tmp + 4, one.l, 32, hipMemcpyHostToDevice, c->stream));   // (0, 1): the polynomial X, whose coset evaluations are the points
+    ZK_HIP(c, hipStreamSynchronize(c->stream));                    // `one` is a stack object
+    return coset_forward(k, tmp, 2, pre + 4 * k.D * 9);
+}
+
+// up to three commitments in flight, the longest first (a later commit in flight may not be larger than the first)
+int commit_group(const zkhip_plonk_key& k, const uint64_t* const* polys, const size_t* lens, int m, uint64_t* const* out_xy, uint8_t* const* out_inf) {
+    zkhip_ctx* c = k.ctx;
+    int order[3] = {0, 1, 2};
+    for (int i = 0; i < m; ++i)
+        for (int j = i + 1; j < m; ++j)
+            if (lens[order[j]] > lens[order[i]]) std::swap(order[i], order[j]);
+    uint32_t ticket[3];
+    int rc = ZKHIP_OK, begun = 0;
+    for (; begun < m && rc == ZKHIP_OK; ++begun) {
+        const int p = order[begun];
+        rc = zkhip_kzg_commit_begin(c, k.srs_table ? nullptr : k.srs_xy, k.srs_table, k.srs_inf, k.n_points, polys[p], lens[p], 0, &ticket[begun]);
+        if (rc != ZKHIP_OK) break;
+    }
+    for (int i = 0; i < begun; ++i) {
+        const int p = order[i];
+        const int r = rc == ZKHIP_OK ? zkhip_kzg_commit_end(c, ticket[i], out_xy[p], out_inf[p]) : zkhip_kzg_commit_end(c, ticket[i], nullptr, nullptr);
+        if (rc == ZKHIP_OK) rc = r;
+    }
+    return rc;
+}
+
+// p(z) of n coefficients -> out (device): the scan of zkhip_dense_evaluate
+void eval_at(zkhip_ctx* c, const Work& w, const uint64_t* coeffs, size_t n, const HFr& z, uint64_t* out) {
+    const uint32_t nb = (uint32_t)((n + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L));
+    hipLaunchKernelGGL(horner_scan_kernel<false>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), w.hv, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(horner_top_kernel, dim3(1), dim3(1024), 0, c->stream, w.hv, nb, fa(z), w.hc, out);
+}
+// (p(X) - p(z)) / (X - z): n - 1 quotient coefficients, the scan of zkhip_univariate_kzg_open; the remainder p(z) goes to rem
+void divide_by_linear(zkhip_ctx* c, const Work& w, const uint64_t* coeffs, size_t n, const HFr& z, uint64_t* quotient, uint64_t* rem) {
+    const uint32_t nb = (uint32_t)((n + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L));
+    hipLaunchKernelGGL(horner_scan_kernel<false>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), w.hv, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(horner_top_kernel, dim3(1), dim3(1024), 0, c->stream, w.hv, nb, fa(z), w.hc, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(horner_scan_kernel<true>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), nullptr, w.hc, quotient, rem);
+}
+
+int read_flags(zkhip_ctx* c, const Work& w, bool* any) {
+    int h[PLONK_FLAGS];
+    ZK_HIP(c, hipMemcpyAsync(h, w.flags, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *any = false;
+    for (int i = 0; i < PLONK_FLAGS; ++i) *any = *any || h[i] != 0;
+    return ZKHIP_OK;
+}
+
+// L_1(zeta) = (zeta^n - 1) / (n (zeta - 1)); at zeta = 1 the polynomial with all coefficients 1/n gives 1
+HFr l1_at(const HFr& zeta, const HFr& zh_zeta, uint64_t n) {
+    const HFr d = fr_sub(zeta, zkhost::fr_one());
+    if (h_is_zero(d)) return zkhost::fr_one();
+    return fr_mul(zh_zeta, zkhost::fr_inv(fr_mul(zkhost::fr_from_u64(n), d)));
+}
+
+void absorb_challenges_from_proof(const uint64_t* xy, const uint8_t* inf, const uint64_t* evals, HFr* ch) {   // protocol/utils.rs:56-96
+    Merlin t("plonk_protocol");
+    for (int p = P_AS; p <= P_CS; ++p) t.append_point("first_round", xy + 12 * p, inf[p] != 0);
+    ch[C_BETA] = t.challenge("beta");
+    ch[C_GAMMA] = t.challenge("gamma");
+    t.append_point("second_round", xy + 12 * P_ACC, inf[P_ACC] != 0);
+    ch[C_ALPHA] = t.challenge("alpha");
+    for (int p = P_TL; p <= P_TH; ++p) t.append_point("third_round", xy + 12 * p, inf[p] != 0);
+    ch[C_ZETA] = t.challenge("zeta");
+    for (int e = 0; e < N_EVALS; ++e) t.append_scalar("fourth_round", h_load(evals + 4 * e));
+    ch[C_NU] = t.challenge("nu");
+    for (int p = P_WZ; p <= P_WZW; ++p) t.append_point("fifth_round", xy + 12 * p, inf[p] != 0);
+    ch[C_MU] = t.challenge("mu");
+}
+
+// ---- host G1 for the verifier's combination ---------------------------------------------------------------------------------------
+using zkhost::Xyzz;
+Xyzz g1_generator_host() {
+    static const uint32_t gx[12] = {0xfd530c16u, 0x5cb38790u, 0x9976fff5u, 0x7817fc67u, 0x143ba1c1u, 0x154f95c7u,
+                                    0xf3d0e747u, 0xf0ae6acdu, 0x21dbf440u, 0xedce6eccu, 0x9e0bfb75u, 0x12017741u};
+    static const uint32_t gy[12] = {0x0ce72271u, 0xbaac93d5u, 0x7918fd8eu, 0x8c22631au, 0x570725ceu, 0xdd595f13u,
+                                    0x50405194u, 0x51ac5829u, 0xad0059c0u, 0x0e1c8c3fu, 0x5008a26au, 0x0bbc3efcu};
+    uint64_t xy[12];
+    for (int i = 0; i < 6; ++i) {
+        xy[i] = (uint64_t)gx[2 * i] | ((uint64_t)gx[2 * i + 1] << 32);
+        xy[6 + i] = (uint64_t)gy[2 * i] | ((uint64_t)gy[2 * i + 1] << 32);
+    }
+    return zkhost::xyzz_from_affine(xy, false);
+}
+Xyzz g1_mul_limbs(const Xyzz& p, const uint64_t* k /* canonical, 4 limbs */) {
+    Xyzz acc = zkhost::xyzz_identity();
+    for (int i = 255; i >= 0; --i) {
+        acc = zkhost::xyzz_double(acc);
+        if ((k[i / 64] >> (i % 64)) & 1) acc = zkhost::xyzz_add(acc, p);
+    }
+    return acc;
+}
+Xyzz g1_mul(const Xyzz& p, const HFr& mont) { const HFr k = zkhost::fr_from_mont(mont); return g1_mul_limbs(p, k.l); }
+// finite points only: on y^2 = x^3 + 4 and of order r
+bool g1_valid(const uint64_t* xy) {
+    zkhost::Fq x, y;
+    std::memcpy(x.l, xy, 48); std::memcpy(y.l, xy + 6, 48);
+    if (zkhost::geq_p(x.l) || zkhost::geq_p(y.l)) return false;
+    zkhost::Fq four = zkhost::fq_dbl(zkhost::fq_dbl(zkhost::fq_one()));
+    if (!zkhost::fq_eq(zkhost::fq_sqr(y), zkhost::fq_add(zkhost::fq_mul(zkhost::fq_sqr(x), x), four))) return false;
+    return zkhost::is_identity(g1_mul_limbs(zkhost::xyzz_from_affine(xy, false), zkhost::FR_P));
+}
+
+}  // namespace
+
+extern "C" int zkhip_plonk_key_destroy(zkhip_plonk_key* key) {
+    if (!key) return ZKHIP_OK;
+    if (key->ctx) {
+        (void)key->ctx->activate();
+        key->ctx->drain_streams();      // nothing of this key's may still be read by a kernel
+    }
+    delete key;
+    return ZKHIP_OK;
+}
+
+extern "C" int zkhip_plonk_key_create(zkhip_ctx* c, size_t n, const uint64_t* const* h_column_ptrs, const uint64_t* d_points_xy,
+                                      const void* d_table, const uint8_t* d_points_inf, size_t n_points, zkhip_plonk_key** out,
+                                      uint64_t* h_commits_xy, uint8_t* h_commits_inf) {
+    if (!c || !h_column_ptrs || !out || !h_commits_xy || !h_commits_inf || (!d_points_xy && !d_table)) return ZKHIP_ERR_ARG;
+    for (int j = 0; j < 8; ++j) if (!h_column_ptrs[j]) return ZKHIP_ERR_ARG;
+    *out = nullptr;
+    if (!is_pow2(n) || n < 4) return ZKHIP_ERR_SHAPE;             // Domain::new rounds up; the compiler only makes powers of two
+    size_t D = 1;
+    while (D < 3 * n + 6) D <<= 1;
+    if (log2_exact(D) > 30) return ZKHIP_ERR_SHAPE;
+    if (n_points < n + 6) return ZKHIP_ERR_INDEX;                  // powers_of_tau_in_g1[i] out of bounds (univariate_kzg.rs:53) at t_high
+    ZK_TRY(c->activate());
+    std::unique_ptr<zkhip_plonk_key> k(new (std::nothrow) zkhip_plonk_key());
+    if (!k) return ZKHIP_ERR_NOMEM;
+    k->ctx = c; k->n = n; k->D = D; k->S = n + 8;
+    k->log_n = log2_exact(n); k->log_D = log2_exact(D); k->ratio = (uint32_t)(D / n);
+    k->srs_xy = d_table ? nullptr : d_points_xy; k->srs_table = d_table; k->srs_inf = d_points_inf; k->n_points = n_points;
+    const bool cache = (size_t)N_PRE * D * 32 <= PLONK_CACHE_BUDGET;
+    const size_t work_bytes = work_layout(*k, nullptr, !cache, nullptr);
+    if (dev_alloc(k->evals, 8 * n * 32) != hipSuccess || dev_alloc(k->coeffs, 8 * k->S * 32) != hipSuccess ||
+        dev_alloc(k->omega, n * 32) != hipSuccess || dev_alloc(k->gpow, k->S * 32) != hipSuccess ||
+        dev_alloc(k->ginv, (3 * n + 8) * 32) != hipSuccess || dev_alloc(k->work, work_bytes) != hipSuccess ||
+        (cache && dev_alloc(k->pre, (size_t)N_PRE * D * 32) != hipSuccess))
+        return ZKHIP_ERR_NOMEM;
+    HFr w_D, tmp1, tmp2;
+    ZK_TRY(zkhip_domain_params((uint64_t)n, k->w_n.l, tmp1.l, tmp2.l));
+    ZK_TRY(zkhip_domain_params((uint64_t)D, w_D.l, tmp1.l, tmp2.l));
+    const HFr g = zkhost::fr_from_u64(COSET_SHIFT);
+    {   // Z_H(g w_D^j) = g^n rho^(j mod D/n) - 1, rho = w_D^n
+        const HFr gn = h_pow(g, (uint64_t)n), rho = h_pow(w_D, (uint64_t)n);
+        HFr cur = gn;
+        for (uint32_t j = 0; j < 8; ++j) {
+            k->zh_inv[j] = j < k->ratio ? zkhost::fr_inv(fr_sub(cur, zkhost::fr_one())) : zkhost::fr_zero();
+            cur = fr_mul(cur, rho);
+        }
+    }
+    ZK_HIP(c, hipMemsetAsync(k->coeffs.get(), 0, 8 * k->S * 32, c->stream));
+    for (int j = 0; j < 8; ++j) {
+        ZK_HIP(c, hipMemcpyAsync(k->col_eval(j), h_column_ptrs[j], n * 32, hipMemcpyDeviceToDevice, c->stream));
+        ZK_TRY(zkhip_domain_transform(c, k->col_eval(j), n, k->col_coeff(j), k->log_n, 1));      // to_coefficient_poly
+    }
+    ZK_TRY(powers(c, k->w_n, zkhost::fr_one(), n, (uint64_t*)k->omega.get()));
+    ZK_TRY(powers(c, g, zkhost::fr_one(), k->S, (uint64_t*)k->gpow.get()));
+    ZK_TRY(powers(c, zkhost::fr_inv(g), zkhost::fr_one(), 3 * n + 8, (uint64_t*)k->ginv.get()));
+    if (cache) {
+        Work w;
+        work_layout(*k, (char*)k->work.get(), false, &w);
+        ZK_TRY(fill_pre(*k, (uint64_t*)k->pre.get(), w.W));
+    }
+    for (int j = 0; j < 8; ++j) {                                  // VerifierPreprocessedInput::vpi (verifier.rs:24-36)
+        const int rc = d_table ? zkhip_kzg_commit_table(c, d_table, d_points_inf, n_points, k->col_coeff(j), n, 0, h_commits_xy + 12 * j, h_commits_inf + j)
+                               : zkhip_kzg_commit(c, d_points_xy, d_points_inf, n_points, k->col_coeff(j), n, 0, h_commits_xy + 12 * j, h_commits_inf + j);
+        ZK_TRY(rc);
+    }
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *out = k.release();
+    return ZKHIP_OK;
+}
+
+extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_public,
+                                 const uint64_t* h_blinding, uint64_t* h_points_xy, uint8_t* h_points_inf, uint64_t* h_evals,
+                                 uint64_t* h_challenges) {
+    if (!key || !d_a || !d_b || !d_c || !d_public || !h_blinding || !h_points_xy || !h_points_inf || !h_evals) return ZKHIP_ERR_ARG;
+    const zkhip_plonk_key& k = *key;
+    zkhip_ctx* c = k.ctx;
+    ZK_TRY(c->activate());
+    const size_t n = k.n, D = k.D;
+    Work w;
+    work_layout(k, (char*)k.work.get(), !k.pre, &w);
+    const uint64_t* pre = k.pre ? (const uint64_t*)k.pre.get() : w.pre;
+    HFr bl[11];
+    for (int i = 0; i < 11; ++i) {
+        bl[i] = h_load(h_blinding + 4 * i);
+        if (zkhost::fr_geq_p(bl[i].l)) return ZKHIP_ERR_ARG;
+    }
+    std::memset(h_points_xy, 0, 96 * N_POINTS);
+    std::memset(h_points_inf, 0, N_POINTS);
+    uint64_t* xy[N_POINTS]; uint8_t* inf[N_POINTS];
+    for (int p = 0; p < N_POINTS; ++p) { xy[p] = h_points_xy + 12 * p; inf[p] = h_points_inf + p; }
+    ZK_HIP(c, hipMemsetAsync(w.A, 0, w.zero_bytes, c->stream));
+    Merlin tr("plonk_protocol");
+    HFr ch[N_CHALLENGES];
+
+    // ---- round 1 (prover.rs:98-123): a_s = (r0 X + r1) Z_H + a, likewise b_s, c_s
+    {
+        const uint64_t* wires[3] = {d_a, d_b, d_c};
+        uint64_t* dst[3] = {w.A, w.B, w.C};
+        for (int j = 0; j < 3; ++j) {
+            ZK_TRY(zkhip_domain_transform(c, wires[j], n, dst[j], k.log_n, 1));
+            PlonkBlindArg b = {};
+            std::memcpy(b.v, bl[2 * j + 1].l, 32);                 // constant coefficient: rands[1], then rands[0] X
+            std::memcpy(b.v + 4, bl[2 * j].l, 32);
+            hipLaunchKernelGGL(plonk_blind_kernel, dim3(1), dim3(64), 0, c->stream, dst[j], n, 2u, b);
+        }
+        ZK_TRY(zkhip_domain_transform(c, d_public, n, w.PI, k.log_n, 1));
+        ZK_HIP(c, hipGetLastError());
+        const size_t lens[3] = {n + 2, n + 2, n + 2};
+        ZK_TRY(commit_group(k, dst, lens, 3, &xy[P_AS], &inf[P_AS]));
+        for (int p = P_AS; p <= P_CS; ++p) tr.append_point("first_round", xy[p], *inf[p] != 0);
+    }
+    // ---- round 2 (:125-175): the accumulator, z = (r0 + r1 X + r2 X^2) Z_H + acc
+    ch[C_BETA] = tr.challenge("beta");
+    ch[C_GAMMA] = tr.challenge("gamma");
+    {
+        PlonkCols cols;
+        for (int j = 0; j < 8; ++j) cols.q[j] = k.col_eval(j);
+        const uint32_t nb = (uint32_t)((n + GP_ROWS - 1) / GP_ROWS);
+        {
+            ProfScope ps(c, "plonk_grand_product", 32.0 * 14.0 * (double)n);
+            hipLaunchKernelGGL(plonk_gp_ratio_kernel, dim3(nb), dim3(GP_T), 0, c->stream, d_a, d_b, d_c, d_public, cols, (const uint64_t*)k.omega.get(), n,
+                               fa(ch[C_BETA]), fa(ch[C_GAMMA]), w.F, w.bp, w.flags);
+            hipLaunchKernelGGL(plonk_gp_top_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint64_t*)w.bp, nb, w.bx);
+            hipLaunchKernelGGL(plonk_gp_apply_kernel, dim3(nb), dim3(GP_T), 0, c->stream, (const uint64_t*)w.F, (const uint64_t*)w.bx, n, w.ACC, w.flags);
+        }
+        ZK_HIP(c, hipGetLastError());
+        bool bad = false;
+        ZK_TRY(read_flags(c, w, &bad));
+        if (bad) return ZKHIP_ERR_ARG;      // a row breaks the gate identity, a denominator vanishes or the accumulator does not close
+        ZK_TRY(zkhip_domain_transform(c, w.ACC, n, w.Z, k.log_n, 1));
+        PlonkBlindArg b = {};
+        for (int j = 0; j < 3; ++j) std::memcpy(b.v + 4 * j, bl[6 + j].l, 32);
+        hipLaunchKernelGGL(plonk_blind_kernel, dim3(1), dim3(64), 0, c->stream, w.Z, n, 3u, b);
+        ZK_HIP(c, hipGetLastError());
+        const uint64_t* polys[1] = {w.Z};
+        const size_t lens[1] = {n + 3};
+        ZK_TRY(commit_group(k, polys, lens, 1, &xy[P_ACC], &inf[P_ACC]));
+        tr.append_point("second_round", xy[P_ACC], *inf[P_ACC] != 0);
+    }
+    // ---- round 3 (:177-258): t = numerator / Z_H on the coset, back to coefficients, split and blinded
+    ch[C_ALPHA] = tr.challenge("alpha");
+    {
+        const uint64_t* src[5] = {w.A, w.B, w.C, w.Z, w.PI};
+        const size_t lens5[5] = {n + 2, n + 2, n + 2, n + 3, n};
+        for (int j = 0; j < 5; ++j) ZK_TRY(coset_forward(k, src[j], lens5[j], w.ev + 4 * D * j));
+        if (!k.pre) ZK_TRY(fill_pre(k, w.pre, w.W));
+        PlonkQuotArg q = {};
+        q.beta = fa(ch[C_BETA]); q.gamma = fa(ch[C_GAMMA]); q.alpha = fa(ch[C_ALPHA]); q.alpha2 = fa(fr_mul(ch[C_ALPHA], ch[C_ALPHA]));
+        for (int j = 0; j < 8; ++j) q.zh_inv[j] = fa(k.zh_inv[j]);
+        q.rot = k.ratio;
+        {
+            ProfScope ps(c, "plonk_quotient", 32.0 * 17.0 * (double)D);
+            hipLaunchKernelGGL(plonk_quotient_kernel, dim3(mle_grid_stream(D)), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)w.ev, pre, D, q, w.T);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(zkhip_domain_transform(c, w.T, D, w.T, k.log_D, 1));
+        {
+            ProfScope ps(c, "plonk_split", 32.0 * (double)(D + 6 * n));
+            hipLaunchKernelGGL(plonk_split_kernel, dim3(mle_grid_stream(D)), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)w.T, (const uint64_t*)k.ginv.get(), n, D,
+                               fa(bl[9]), fa(bl[10]), w.TL, w.TM, w.TH, w.flags);
+        }
+        ZK_HIP(c, hipGetLastError());
+        bool bad = false;
+        ZK_TRY(read_flags(c, w, &bad));
+        if (bad) return ZKHIP_ERR_ARG;      // Z_H does not divide the numerator: no proof from it
+        const uint64_t* polys[3] = {w.TL, w.TM, w.TH};
+        const size_t lens[3] = {n + 1, n + 1, n + 6};
+        ZK_TRY(commit_group(k, polys, lens, 3, &xy[P_TL], &inf[P_TL]));
+        for (int p = P_TL; p <= P_TH; ++p) tr.append_point("third_round", xy[p], *inf[p] != 0);
+    }
+    // ---- round 4 (:260-293): six evaluations (and PI(zeta) for round 5)
+    ch[C_ZETA] = tr.challenge("zeta");
+    const HFr zeta = ch[C_ZETA], zeta_w = fr_mul(zeta, k.w_n);
+    HFr ev[7];
+    {
+        ProfScope ps(c, "plonk_evaluate", 32.0 * 7.0 * (double)n);
+        eval_at(c, w, w.A, n + 2, zeta, w.out + 4 * E_A);
+        eval_at(c, w, w.B, n + 2, zeta, w.out + 4 * E_B);
+        eval_at(c, w, w.C, n + 2, zeta, w.out + 4 * E_C);
+        eval_at(c, w, k.col_coeff(5), n, zeta, w.out + 4 * E_S1);
+        eval_at(c, w, k.col_coeff(6), n, zeta, w.out + 4 * E_S2);
+        eval_at(c, w, w.Z, n + 3, zeta_w, w.out + 4 * E_ZW);       // apply_w_to_polynomial(z)(zeta) = z(w zeta)
+        eval_at(c, w, w.PI, n, zeta, w.out + 4 * 6);
+    }
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(ev, w.out, sizeof ev, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    for (int e = 0; e < N_EVALS; ++e) { std::memcpy(h_evals + 4 * e, ev[e].l, 32); tr.append_scalar("fourth_round", ev[e]); }
+    // ---- round 5 (:295-376): W_zeta = (r + nu-combination) / (X - zeta), W_zeta_omega = (z - z(w zeta)) / (X - w zeta)
+    ch[C_NU] = tr.challenge("nu");
+    {
+        const HFr beta = ch[C_BETA], gamma = ch[C_GAMMA], alpha = ch[C_ALPHA], nu = ch[C_NU];
+        const HFr az = ev[E_A], bz = ev[E_B], cz = ev[E_C], s1z = ev[E_S1], s2z = ev[E_S2], zwz = ev[E_ZW], piz = ev[6];
+        const HFr a2 = fr_mul(alpha, alpha), zn = h_pow(zeta, (uint64_t)n), zh = fr_sub(zn, zkhost::fr_one());
+        const HFr l1z = l1_at(zeta, zh, (uint64_t)n);
+        const HFr bzeta = fr_mul(beta, zeta);
+        const HFr p1 = fr_mul(fr_mul(fr_add(fr_add(az, bzeta), gamma), fr_add(fr_add(bz, fr_add(bzeta, bzeta)), gamma)),
+                              fr_add(fr_add(cz, fr_add(bzeta, fr_add(bzeta, bzeta))), gamma));
+        const HFr p2 = fr_mul(fr_mul(fr_add(fr_add(az, fr_mul(beta, s1z)), gamma), fr_add(fr_add(bz, fr_mul(beta, s2z)), gamma)), zwz);
+        HFr nup[6];
+        nup[0] = zkhost::fr_one();
+        for (int j = 1; j < 6; ++j) nup[j] = fr_mul(nup[j - 1], nu);
+        PlonkLinArg L = {};
+        const uint64_t* ptr[PLONK_LIN_TERMS] = {k.col_coeff(0), k.col_coeff(1), k.col_coeff(2), k.col_coeff(3), k.col_coeff(4), w.Z, k.col_coeff(7),
+                                                w.TL, w.TM, w.TH, w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6)};
+        const HFr s[PLONK_LIN_TERMS] = {fr_mul(az, bz), az, bz, cz, zkhost::fr_one(), fr_add(fr_mul(alpha, p1), fr_mul(a2, l1z)),
+                                        h_neg(fr_mul(fr_mul(alpha, beta), p2)), h_neg(zh), h_neg(fr_mul(zh, zn)), h_neg(fr_mul(zh, fr_mul(zn, zn))),
+                                        nup[1], nup[2], nup[3], nup[4], nup[5]};
+        for (int j = 0; j < PLONK_LIN_TERMS; ++j) { L.p[j] = ptr[j]; L.s[j] = fa(s[j]); }
+        HFr c0 = fr_sub(piz, fr_mul(fr_mul(alpha, fr_add(cz, gamma)), p2));
+        c0 = fr_sub(c0, fr_mul(a2, l1z));
+        const HFr opened[5] = {az, bz, cz, s1z, s2z};
+        for (int j = 0; j < 5; ++j) c0 = fr_sub(c0, fr_mul(nup[j + 1], opened[j]));
+        L.c0 = fa(c0);
+        {
+            ProfScope ps(c, "plonk_linearise", 32.0 * 16.0 * (double)n);
+            hipLaunchKernelGGL(plonk_linearise_kernel, dim3(mle_grid_stream(n + 6)), dim3(MLE_BLOCK), 0, c->stream, L, n + 6, w.W);
+        }
+        {
+            ProfScope ps(c, "plonk_divide", 96.0 * 2.0 * (double)n);
+            divide_by_linear(c, w, w.W, n + 6, zeta, w.Q1, w.out);
+            divide_by_linear(c, w, w.Z, n + 3, zeta_w, w.Q2, w.out + 4);
+        }
+        ZK_HIP(c, hipGetLastError());
+        const uint64_t* polys[2] = {w.Q1, w.Q2};
+        const size_t lens[2] = {n + 5, n + 2};
+        ZK_TRY(commit_group(k, polys, lens, 2, &xy[P_WZ], &inf[P_WZ]));
+        for (int p = P_WZ; p <= P_WZW; ++p) tr.append_point("fifth_round", xy[p], *inf[p] != 0);
+    }
+    ch[C_MU] = tr.challenge("mu");
+    if (h_challenges) std::memcpy(h_challenges, ch, sizeof ch);
+    return ZKHIP_OK;
+}
+
+// compute_verifier_challenges (protocol/utils.rs:56-96): host only, no GPU
+extern "C" int zkhip_plonk_challenges(const uint64_t* h_points_xy, const uint8_t* h_points_inf, const uint64_t* h_evals, uint64_t* h_challenges) {
+    if (!h_points_xy || !h_points_inf || !h_evals || !h_challenges) return ZKHIP_ERR_ARG;
+    for (int e = 0; e < N_EVALS; ++e) if (zkhost::fr_geq_p(h_evals + 4 * e)) return ZKHIP_ERR_ARG;
+    HFr ch[N_CHALLENGES];
+    absorb_challenges_from_proof(h_points_xy, h_points_inf, h_evals, ch);
+    std::memcpy(h_challenges, ch, sizeof ch);
+    return ZKHIP_OK;
+}
+
+// PlonkVerifier::verify (verifier.rs:62-172)
+extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_xy, const uint8_t* h_vk_inf, const uint64_t* h_points_xy,
+                                  const uint8_t* h_points_inf, const uint64_t* h_evals, const uint64_t* d_public, const uint64_t* d_g2_xy,
+                                  const uint8_t* d_g2_inf, size_t n_g2, uint8_t* h_ok) {
+    if (!c || !h_vk_xy || !h_vk_inf || !h_points_xy || !h_points_inf || !h_evals || !d_public || !d_g2_xy || !d_g2_inf || !h_ok) return ZKHIP_ERR_ARG;
+    *h_ok = 0;
+    if (!is_pow2(n) || n < 4 || log2_exact(n) > 28) return ZKHIP_ERR_SHAPE;
+    if (n_g2 < 2) return ZKHIP_ERR_INDEX;                          // powers_of_tau_in_g2[1] (verifier.rs:34)
+    for (int e = 0; e < N_EVALS; ++e) if (zkhost::fr_geq_p(h_evals + 4 * e)) return ZKHIP_ERR_ARG;
+    for (int p = 0; p < N_POINTS; ++p) if (!h_points_inf[p] && !g1_valid(h_points_xy + 12 * p)) return ZKHIP_ERR_ARG;
+    for (int p = 0; p < 8; ++p) if (!h_vk_inf[p] && !g1_valid(h_vk_xy + 12 * p)) return ZKHIP_ERR_ARG;
+    ZK_TRY(c->activate());
+    HFr ch[N_CHALLENGES];
+    absorb_challenges_from_proof(h_points_xy, h_points_inf, h_evals, ch);
+    const HFr beta = ch[C_BETA], gamma = ch[C_GAMMA], alpha = ch[C_ALPHA], zeta = ch[C_ZETA], nu = ch[C_NU], mu = ch[C_MU];
+    // PI(zeta): to_coefficient_poly().evaluate(zeta) on the device
+    DevMem tmp;
+    const size_t prep_bytes = zkhip_g2_prepared_bytes(2);
+    const size_t o_pi = 0, o_g1 = (n * 32 + 255) & ~(size_t)255, o_inf = o_g1 + 256, o_gt = o_inf + 256, o_prep = o_gt + 2 * 576 + 128;
+    if (dev_alloc(tmp, o_prep + prep_bytes) != hipSuccess) return ZKHIP_ERR_NOMEM;
+    char* base = (char*)tmp.get();
+    HFr piz, wn, t1, t2;
+    ZK_TRY(zkhip_domain_params((uint64_t)n, wn.l, t1.l, t2.l));
+    ZK_TRY(zkhip_domain_transform(c, d_public, n, (uint64_t*)(base + o_pi), log2_exact(n), 1));
+    ZK_TRY(zkhip_dense_evaluate(c, (const uint64_t*)(base + o_pi), n, zeta.l, piz.l));
+    HFr e[N_EVALS];
+    for (int j = 0; j < N_EVALS; ++j) e[j] = h_load(h_evals + 4 * j);
+    const HFr az = e[E_A], bz = e[E_B], cz = e[E_C], s1z = e[E_S1], s2z = e[E_S2], zwz = e[E_ZW];
+    const HFr a2 = fr_mul(alpha, alpha), zn = h_pow(zeta, (uint64_t)n), zh = fr_sub(zn, zkhost::fr_one());
+    const HFr l1z = l1_at(zeta, zh, (uint64_t)n);
+    const HFr fa1 = fr_add(fr_add(az, fr_mul(s1z, beta)), gamma), fb1 = fr_add(fr_add(bz, fr_mul(s2z, beta)), gamma);
+    const HFr r0 = fr_sub(fr_sub(piz, fr_mul(l1z, a2)), fr_mul(alpha, fr_mul(fr_mul(fa1, fb1), fr_mul(fr_add(cz, gamma), zwz))));   // :82-88
+    const HFr bzeta = fr_mul(beta, zeta);
+    const HFr k_acc = fr_add(fr_add(fr_mul(fr_mul(fr_mul(fr_add(fr_add(az, bzeta), gamma), fr_add(fr_add(bz, fr_add(bzeta, bzeta)), gamma)),
+                                                  fr_add(fr_add(cz, fr_add(bzeta, fr_add(bzeta, bzeta))), gamma)), alpha), fr_mul(l1z, a2)), mu);
+    const HFr k_s3 = fr_mul(fr_mul(fr_mul(fa1, fb1), fr_mul(alpha, beta)), zwz);
+    HFr nup[6];
+    nup[0] = zkhost::fr_one();
+    for (int j = 1; j < 6; ++j) nup[j] = fr_mul(nup[j - 1], nu);
+    auto pt = [&](const uint64_t* xy, const uint8_t* inf, int i) { return zkhost::xyzz_from_affine(xy + 12 * i, inf[i] != 0); };
+    auto P = [&](int i) { return pt(h_points_xy, h_points_inf, i); };
+    auto V = [&](int i) { return pt(h_vk_xy, h_vk_inf, i); };       // q_m, q_l, q_r, q_o, q_c, sigma_1, sigma_2, sigma_3
+    using zkhost::xyzz_add;
+    Xyzz t_comb = xyzz_add(xyzz_add(P(P_TL), g1_mul(P(P_TM), zn)), g1_mul(P(P_TH), fr_mul(zn, zn)));
+    Xyzz d1 = xyzz_add(xyzz_add(xyzz_add(g1_mul(V(0), fr_mul(az, bz)), g1_mul(V(1), az)), xyzz_add(g1_mul(V(2), bz), g1_mul(V(3), cz))), V(4));   // :101-105
+    d1 = xyzz_add(d1, g1_mul(P(P_ACC), k_acc));                                                                                                 // :106-114
+    d1 = xyzz_add(d1, g1_mul(V(7), h_neg(k_s3)));                                                                                               // :115-122
+    d1 = xyzz_add(d1, g1_mul(t_comb, h_neg(zh)));                                                                                               // :123-126
+    Xyzz f1 = xyzz_add(d1, xyzz_add(xyzz_add(g1_mul(P(P_AS), nup[1]), g1_mul(P(P_BS), nup[2])),
+                                    xyzz_add(g1_mul(P(P_CS), nup[3]), xyzz_add(g1_mul(V(5), nup[4]), g1_mul(V(6), nup[5])))));                    // :134-139
+    HFr es = fr_sub(fr_mul(mu, zwz), r0);
+    const HFr opened[5] = {az, bz, cz, s1z, s2z};
+    for (int j = 0; j < 5; ++j) es = fr_add(es, fr_mul(nup[j + 1], opened[j]));
+    const Xyzz e1_neg = g1_mul(g1_generator_host(), h_neg(es));                                                                                // :141-150
+    const Xyzz left = xyzz_add(P(P_WZ), g1_mul(P(P_WZW), mu));                                                                                 // :157-160
+    const Xyzz right = xyzz_add(xyzz_add(g1_mul(P(P_WZ), zeta), g1_mul(P(P_WZW), fr_mul(fr_mul(wn, mu), zeta))), xyzz_add(f1, e1_neg));         // :162-169
+    // e(right, G2) and e(left, tau G2): prepared entry 0 is the generator, entry 1 the SRS's powers_of_tau_in_g2[1]
+    uint64_t g1[24];
+    uint8_t g1_inf[2];
+    g1_inf[0] = zkhost::xyzz_to_affine(right, g1) ? 0 : 1;
+    g1_inf[1] = zkhost::xyzz_to_affine(left, g1 + 12) ? 0 : 1;
+    ZK_HIP(c, hipMemcpyAsync(base + o_g1, g1, sizeof g1, hipMemcpyHostToDevice, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(base + o_inf, g1_inf, 2, hipMemcpyHostToDevice, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    ZK_TRY(zkhip_kzg_prepare(c, d_g2_xy + 24, d_g2_inf + 1, 1, base + o_prep));
+    ZK_TRY(zkhip_pairing_prepared(c, (const uint64_t*)(base + o_g1), (const uint8_t*)(base + o_inf), base + o_prep, 2, (uint64_t*)(base + o_gt)));
+    uint64_t gt[144];
+    ZK_HIP(c, hipMemcpyAsync(gt, base + o_gt, sizeof gt, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *h_ok = std::memcmp(gt, gt + 72, 576) == 0 ? 1 : 0;            // GT has one encoding: left == right (:171)
+    return ZKHIP_OK;
+}

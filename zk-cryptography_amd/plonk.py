@@ -1,0 +1,544 @@
+"""plonk::{compiler, protocol} and merlin::MerlinTranscript: the PLONK prover and verifier on the GPU.
+
+Mirrors plonk/src/protocol/{prover,verifier,utils,transcript,primitives}.rs, plonk/src/compiler/{assembly,program,utils,primitives}.rs
+and transcripts/merlin/src/lib.rs.  The five rounds of `PlonkProver::prove` and `PlonkVerifier::verify` run in libzkhip
+(zkhip_plonk_prove / zkhip_plonk_verify: transforms, the grand product, the quotient on a coset, the linearisation, nine commitments
+and two pairings on the device; the Merlin transcript on the host between the rounds).  The small compiler in front of them works on
+python ints on the host, as it does on field elements in the reference: its panics come back as exceptions.
+
+Field elements of this module are python ints (canonical, < r); G1 points are `G1Affine`.  The 11 random scalars the reference draws
+(`generate_random_numbers`: six in round 1, three in round 2, two in round 3) may be passed as `blinding`; the default draws them
+from `secrets`.
+"""
+import ctypes as C
+import hashlib
+import re
+import secrets
+import weakref
+
+import numpy as np
+
+from zk_cryptography_amd import _native as N
+from zk_cryptography_amd.field import Fr, R_MOD
+from zk_cryptography_amd.kzg import G1Affine, G2Affine
+
+_vp = C.c_void_p
+PROOF_POINTS = ["as_commitment", "bs_commitment", "cs_commitment", "accumulator_commitment", "t_low", "t_mid", "t_high",
+                "w_zeta_commitment", "w_zeta_omega_commitment"]
+PROOF_SCALARS = ["a_s_poly_zeta", "b_s_poly_zeta", "c_s_poly_zeta", "sigma1_poly_zeta", "sigma2_poly_zeta", "w_accumulator_poly_zeta"]
+CHALLENGES = ["beta", "gamma", "alpha", "zeta", "nu", "mu"]
+_COLUMNS = ["q_m", "q_l", "q_r", "q_o", "q_c", "sigma_1", "sigma_2", "sigma_3"]      # the order of VerifierPreprocessedInput::vpi
+
+
+# ---- transcripts/merlin/src/lib.rs ----------------------------------------------------------------------------------------
+def _fp_string(v):
+    """ark-ff 0.4.2 Display for Fp: decimal with leading zeros trimmed (zero prints as the empty string)"""
+    return str(int(v)).lstrip("0")
+
+
+def point_to_string(point):
+    """ark-ec 0.4.2 Display of a G1 point: "(x, y)" of the affine coordinates, "infinity" for the identity"""
+    if point is None or getattr(point, "infinity", False):
+        return "infinity"
+    x, y = point.coords() if isinstance(point, G1Affine) else point
+    return "(%s, %s)" % (_fp_string(x), _fp_string(y))
+
+
+class MerlinTranscript:
+    """merlin::MerlinTranscript (lib.rs:6-49), quirks included: `challenge` finalises, RESETS the hasher to empty and absorbs the label."""
+
+    def __init__(self, label=b"default"):
+        self.hasher = hashlib.sha256()
+        self.hasher.update(b"Merlin Transcript")
+        self.hasher.update(bytes(label))
+
+    def append_message(self, label, message):
+        self.hasher.update(bytes(label))
+        self.hasher.update(len(message).to_bytes(8, "little"))
+        self.hasher.update(bytes(message))
+
+    def append_scalar(self, label, scalar):
+        self.append_message(label, (int(scalar) % R_MOD).to_bytes(32, "little"))      # serialize_compressed
+
+    def append_point(self, label, point):
+        self.append_message(label, point_to_string(point).encode())
+
+    def challenge(self, label):
+        digest = self.hasher.digest()
+        self.hasher = hashlib.sha256()
+        self.hasher.update(bytes(label))
+        return int.from_bytes(digest, "big") % R_MOD                                    # from_be_bytes_mod_order
+
+    def challenge_n(self, label, n):
+        return [self.challenge(label) for _ in range(n)]
+
+
+class PlonkRoundTranscript:
+    """plonk/src/protocol/transcript.rs"""
+
+    def __init__(self):
+        self.transcript = MerlinTranscript(b"plonk_protocol")
+
+    def first_round(self, a_s, b_s, c_s):
+        for p in (a_s, b_s, c_s):
+            self.transcript.append_point(b"first_round", p)
+
+    def second_round(self, accumulator_commitment):
+        self.transcript.append_point(b"second_round", accumulator_commitment)
+
+    def third_round(self, t_low, t_mid, t_high):
+        for p in (t_low, t_mid, t_high):
+            self.transcript.append_point(b"third_round", p)
+
+    def fourth_round(self, *scalars):
+        for s in scalars:
+            self.transcript.append_scalar(b"fourth_round", s)
+
+    def fifth_round(self, w_zeta_commitment, w_zeta_omega_commitment):
+        for p in (w_zeta_commitment, w_zeta_omega_commitment):
+            self.transcript.append_point(b"fifth_round", p)
+
+    def challenge_round(self, label):
+        return self.transcript.challenge(label)
+
+
+# ---- plonk/src/compiler ---------------------------------------------------------------------------------------------------------
+def root_of_unity(group_order):
+    """F::get_root_of_unity(group_order) (compiler/utils.rs:38-40)"""
+    g = np.zeros(4, dtype=np.uint64)
+    gi, ni = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    N.check(N.lib().zkhip_domain_params(C.c_uint64(group_order), g.ctypes.data_as(_vp), gi.ctypes.data_as(_vp), ni.ctypes.data_as(_vp)),
+            "root_of_unity")
+    return Fr.to_ints(g)[0]
+
+
+def roots_of_unity(group_order):                    # compiler/utils.rs:42-49
+    w, out = root_of_unity(group_order), [1]
+    for _ in range(1, group_order):
+        out.append(out[-1] * w % R_MOD)
+    return out
+
+
+def get_product_key(key1, key2):                    # compiler/utils.rs:76-98
+    if key1 is not None and key2 is not None:
+        members = sorted(key1.split("*") + key2.split("*"))
+        return "*".join(m for m in members if m)
+    return key1 if key1 is not None else key2
+
+
+def is_valid_variable_name(name):                   # compiler/utils.rs:100-104
+    return bool(name) and all(ch.isalnum() for ch in name) and not name[0].isnumeric()
+
+
+def merge_maps(map1, map2):
+    merged = {}
+    for m in (map1, map2):
+        for k, v in m.items():
+            merged[k] = (merged.get(k, 0) + v) % R_MOD
+    return merged
+
+
+def multiply_maps(map1, map2):
+    result = {}
+    for k1, v1 in map1.items():
+        for k2, v2 in map2.items():
+            k = get_product_key(k1, k2)
+            result[k] = (result.get(k, 0) + v1 * v2) % R_MOD
+    return result
+
+
+def evaluate(exprs, first_is_negative=False):       # compiler/utils.rs:106-168
+    exprs = list(exprs)
+    for op in ("+", "-", "*"):
+        if op in exprs:
+            idx = exprs.index(op)
+            left = evaluate(exprs[:idx], first_is_negative)
+            if op == "*":
+                return multiply_maps(left, evaluate(exprs[idx + 1:], first_is_negative))
+            return merge_maps(left, evaluate(exprs[idx + 1:], op == "-"))
+    if len(exprs) > 1:
+        raise ValueError("No ops, expected sub-expr to be a unit: %r" % exprs[1])
+    tok = exprs[0]                                  # an empty side is the reference's index panic: IndexError
+    if tok.startswith("-"):
+        return evaluate([tok[1:]], not first_is_negative)
+    if re.fullmatch(r"\+?[0-9]+", tok) and int(tok) < (1 << 127):
+        return {None: (-int(tok)) % R_MOD if first_is_negative else int(tok) % R_MOD}
+    if is_valid_variable_name(tok):
+        return {tok: R_MOD - 1 if first_is_negative else 1}
+    raise ValueError("ok wtf is %s" % tok)
+
+
+class GateWire:
+    def __init__(self, left_wire, right_wire, output_wire):
+        self.left_wire, self.right_wire, self.output_wire = left_wire, right_wire, output_wire
+
+    def to_vec(self):
+        return [self.left_wire, self.right_wire, self.output_wire]
+
+
+class Gate:
+    def __init__(self, l, r, m, o, c):
+        self.l, self.r, self.m, self.o, self.c = l, r, m, o, c
+
+
+class AssemblyEqn:
+    """compiler/assembly.rs: one constraint as wires + coefficient map (keys: a variable, a product key, None for the constant)"""
+
+    def __init__(self, wires, coeffs):
+        self.wires, self.coeffs = wires, coeffs
+
+    def _neg_coeff(self, key):
+        return (-self.coeffs[key]) % R_MOD if key in self.coeffs else 0
+
+    def left(self):
+        return self._neg_coeff(self.wires.left_wire)
+
+    def right(self):
+        return self._neg_coeff(self.wires.right_wire) if self.wires.right_wire != self.wires.left_wire else 0
+
+    def constant(self):
+        return self._neg_coeff(None)
+
+    def output(self):
+        return self.coeffs.get("$output_coeff", 1)
+
+    def mul(self):
+        if None not in self.wires.to_vec():
+            return self._neg_coeff(get_product_key(self.wires.left_wire, self.wires.right_wire))
+        return 0
+
+    def gate(self):
+        return Gate(self.left(), self.right(), self.mul(), self.output(), self.constant())
+
+    @staticmethod
+    def eq_to_assembly(eq):                         # assembly.rs:79-169
+        tokens = eq.strip().split(" ")
+        if tokens[1] in ("<==", "==="):
+            out = tokens[0]
+            coeffs = evaluate(tokens[2:])
+            if out[0] == "-":
+                out = out[1:]
+                coeffs["$output_coeff"] = R_MOD - 1
+            if not is_valid_variable_name(out):
+                raise ValueError("Invalid out variable name: %s" % out)
+            variables = []
+            for t in tokens[2:]:
+                var = t.lstrip("-")
+                if is_valid_variable_name(var) and var not in variables:
+                    variables.append(var)
+            allowed = list(variables) + ["", "$output_coeff"]
+            if not variables:
+                raise NotImplementedError("not yet implemented")                       # todo!()
+            if len(variables) == 1:
+                variables.append(variables[0])
+            if len(variables) > 2:
+                raise ValueError("Max 2 variables, found %d" % len(variables))
+            allowed.append(get_product_key(variables[0], variables[1]))
+            for key in coeffs:
+                if key is None:                     # key_option.as_ref().unwrap(): a constant term panics in the reference
+                    raise ValueError("called `Option::unwrap()` on a `None` value")
+                if key not in allowed:
+                    raise ValueError("Disallowed multiplication")
+            return AssemblyEqn(GateWire(variables[0], variables[1], out), coeffs)
+        if tokens[1] == "public":
+            return AssemblyEqn(GateWire(tokens[0], None, None), {tokens[0]: R_MOD - 1, "$output_coeff": 0, "$public": 1})
+        raise ValueError("Unsupported op: %s" % tokens[1])
+
+
+class CommonPreprocessedInput:
+    """compiler/primitives.rs:6-16: eight columns in evaluation form over the domain of `group_order` (lists of ints)"""
+
+    def __init__(self, group_order, q_l, q_r, q_m, q_o, q_c, sigma_1, sigma_2, sigma_3):
+        self.group_order = group_order
+        self.q_l, self.q_r, self.q_m, self.q_o, self.q_c = q_l, q_r, q_m, q_o, q_c
+        self.sigma_1, self.sigma_2, self.sigma_3 = sigma_1, sigma_2, sigma_3
+        self._keys = {}
+
+
+class Witness:
+    """compiler/primitives.rs:23-28"""
+
+    def __init__(self, a, b, c, public_poly):
+        self.a, self.b, self.c, self.public_poly = a, b, c, public_poly
+
+
+class Program:
+    """compiler/program.rs"""
+
+    def __init__(self, constraints, group_order):
+        self.constraints, self.group_order = list(constraints), group_order
+
+    def common_preprocessed_input(self):
+        q_l, q_r, q_m, q_o, q_c = self.make_gate_polynomials()
+        s1, s2, s3 = self.make_s_polynomials()
+        return CommonPreprocessedInput(self.group_order, q_l, q_r, q_m, q_o, q_c, s1, s2, s3)
+
+    def make_gate_polynomials(self):                # :32-65 (l, r, m, o, c)
+        n = self.group_order
+        l, r, m, o, c = ([0] * n for _ in range(5))
+        for i, constraint in enumerate(self.constraints):
+            g = constraint.gate()
+            l[i], r[i], m[i], o[i], c[i] = g.l, g.r, g.m, g.o, g.c                    # more constraints than rows: IndexError, as there
+        return l, r, m, o, c
+
+    def make_s_polynomials(self):                   # :67-132
+        n = self.group_order
+        uses = {}
+        for row, constraint in enumerate(self.constraints):
+            for column, variable in enumerate(constraint.wires.to_vec()):
+                uses.setdefault(variable, []).append((column, row))
+        for row in range(len(self.constraints), n):
+            for column in range(3):
+                uses.setdefault(None, []).append((column, row))
+        w = roots_of_unity(n)
+        s = [list(w), [x * 2 % R_MOD for x in w], [0] * n]
+        for cells in uses.values():
+            for i, (column, row) in enumerate(cells):
+                ncol, nrow = cells[(i + 1) % len(cells)]
+                s[ncol][nrow] = w[row] * (column + 1) % R_MOD                           # Cell::label
+        return s[0], s[1], s[2]
+
+    def coeffs(self):
+        return [dict(c.coeffs) for c in self.constraints]
+
+    def wires(self):
+        return [c.wires for c in self.constraints]
+
+    def get_public_assignment(self):                # :150-173
+        out, no_more_allowed = [], False
+        for coeff in self.coeffs():
+            if "$public" in coeff:
+                if no_more_allowed:
+                    raise ValueError("Public var declarations must be at the top")
+                out.append("".join(k for k in coeff if not k.startswith("$")))
+            else:
+                no_more_allowed = True
+        return out
+
+    def compute_witness(self, starting_assignments):        # :175-218
+        out = {k: v % R_MOD for k, v in starting_assignments.items()}
+        out[None] = 0
+        for constraint in self.constraints:
+            wires, coeffs = constraint.wires, constraint.coeffs
+            in_l, in_r, output = wires.left_wire, wires.right_wire, wires.output_wire
+            out_coeff = coeffs.get("$output_coeff", 1)
+            if output is not None and out_coeff in (1, R_MOD - 1):
+                new_value = (coeffs.get("", 0) + out[in_l] * coeffs.get(in_l, 0)
+                             + out[in_r] * coeffs.get(in_r, 0) * (1 if in_r != in_l else 0)
+                             + out[in_l] * out[in_r] * coeffs.get(get_product_key(in_l, in_r), 0)) * out_coeff % R_MOD
+                if output in out:
+                    if out[output] != new_value:
+                        raise ValueError("Inconsistent assignment for variable %r" % output)
+                else:
+                    out[output] = new_value
+        return out
+
+    def compute_witness_and_public_poly(self, starting_assignments):     # :220-266
+        n = self.group_order
+        out = self.compute_witness(starting_assignments)
+        public = [(-out[x]) % R_MOD for x in self.get_public_assignment()]
+        public += [0] * (n - len(public))
+        a, b, c = [0] * n, [0] * n, [0] * n
+        for i, constraint in enumerate(self.constraints):
+            wl, wr, wo = constraint.wires.to_vec()
+            a[i] = out[wl] if wl is not None else 0
+            b[i] = out[wr] if wr is not None else 0
+            c[i] = out[wo] if wo is not None else 0
+        return Witness(a, b, c, public)
+
+
+# ---- plonk/src/protocol ---------------------------------------------------------------------------------------------------------
+def _column(values):
+    """a column as a device tensor of Montgomery limbs: a list of python ints, uint64 [n, 4] limbs or an int64 CUDA tensor"""
+    import torch
+    if isinstance(values, torch.Tensor):
+        return values.contiguous() if values.is_cuda else values.cuda().contiguous()
+    if isinstance(values, np.ndarray) and values.ndim == 2:
+        return torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint64).view(np.int64)).cuda()
+    return torch.from_numpy(Fr.from_ints(list(values)).view(np.int64)).cuda()
+
+
+def _points_arrays(points):
+    xy = np.zeros((len(points), 12), dtype=np.uint64)
+    inf = np.zeros(len(points), dtype=np.uint8)
+    for i, p in enumerate(points):
+        xy[i], inf[i] = p.xy, 1 if p.infinity else 0
+    return xy, inf
+
+
+class _KeyRef:
+    """what Context.destroy() closes before the context goes (a zkhip_plonk_key refers to its zkhip_ctx); weak, so that a key nobody
+    uses any more is freed with its CommonPreprocessedInput, not with the context"""
+
+    def __init__(self, key):
+        self._key = weakref.ref(key)
+
+    def close(self):
+        key = self._key()
+        if key is not None:
+            key.close()
+
+
+class _Key:
+    """zkhip_plonk_key: the preprocessed input resident on the device, with the eight commitments of vpi"""
+
+    def __init__(self, cpi, srs):
+        n = cpi.group_order
+        self.n, self.srs = n, srs
+        self.columns = [_column(getattr(cpi, f)) for f in _COLUMNS]
+        for t in self.columns:
+            if t.shape[0] != n:
+                raise AssertionError("a preprocessed column does not have group_order entries")
+        self.ctx = N.Context.get(self.columns[0].device.index)
+        table = srs.table_for(n + 6)
+        ptrs = (C.c_void_p * 8)(*[t.data_ptr() for t in self.columns])
+        xy, inf = np.zeros((8, 12), dtype=np.uint64), np.zeros(8, dtype=np.uint8)
+        self.handle = C.c_void_p()
+        self._keep = (table, srs.powers_of_tau_in_g1, srs.inf)
+        st = N.lib().zkhip_plonk_key_create(self.ctx.handle, C.c_size_t(n), ptrs, N.ptr(srs.powers_of_tau_in_g1),
+                                            N.ptr(table) if table is not None else None, N.ptr(srs.inf), C.c_size_t(len(srs)),
+                                            C.byref(self.handle), xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp))
+        N.check(st, "plonk key (group_order a power of two >= 4; the SRS needs group_order + 6 G1 points)")
+        self.commitments = [G1Affine(xy[i], inf[i]) for i in range(8)]
+        self._ref = _KeyRef(self)
+        self.ctx._circuits.append(self._ref)
+
+    def close(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h and self.ctx.handle:
+            N.lib().zkhip_plonk_key_destroy(h)
+        ref = getattr(self, "_ref", None)
+        if ref is not None and ref in self.ctx._circuits:
+            self.ctx._circuits.remove(ref)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+def _key_for(cpi, srs):
+    key = cpi._keys.get(id(srs))
+    if key is None or key.srs is not srs or not key.handle or not key.ctx.handle:
+        key = cpi._keys[id(srs)] = _Key(cpi, srs)
+    return key
+
+
+class VerifierPreprocessedInput:
+    """protocol/primitives.rs:74-84"""
+
+    def __init__(self, qm, ql, qr, qo, qc, sigma1, sigma2, sigma3, x_2):
+        self.qm_commitment, self.ql_commitment, self.qr_commitment, self.qo_commitment, self.qc_commitment = qm, ql, qr, qo, qc
+        self.sigma1_commitment, self.sigma2_commitment, self.sigma3_commitment, self.x_2 = sigma1, sigma2, sigma3, x_2
+
+    @staticmethod
+    def vpi(srs, cpi):                              # verifier.rs:24-36
+        if srs.powers_of_tau_in_g2 is None or len(srs.powers_of_tau_in_g2) < 2:
+            raise IndexError("powers_of_tau_in_g2[1]: build the SRS with generate_srs(..., g2=True)")
+        x_2 = srs.g2_points()[1]
+        return VerifierPreprocessedInput(*_key_for(cpi, srs).commitments, x_2)
+
+    def _commitments(self):
+        return [self.qm_commitment, self.ql_commitment, self.qr_commitment, self.qo_commitment, self.qc_commitment,
+                self.sigma1_commitment, self.sigma2_commitment, self.sigma3_commitment]
+
+
+class PlonkProof:
+    """protocol/primitives.rs:49-65: nine G1Affine points and six field elements (python ints)"""
+
+    def __init__(self, **fields):
+        for f in PROOF_POINTS + PROOF_SCALARS:
+            setattr(self, f, fields[f])
+
+    def _arrays(self):
+        xy, inf = _points_arrays([getattr(self, f) for f in PROOF_POINTS])
+        return xy, inf, Fr.from_ints([getattr(self, f) for f in PROOF_SCALARS])
+
+
+def compute_verifier_challenges(proof):
+    """protocol/utils.rs:56-96 through zkhip_plonk_challenges (host only) -> (beta, gamma, alpha, zeta, nu, mu)"""
+    xy, inf, ev = proof._arrays()
+    ch = np.zeros((6, 4), dtype=np.uint64)
+    N.check(N.lib().zkhip_plonk_challenges(xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp), ev.ctypes.data_as(_vp), ch.ctypes.data_as(_vp)),
+            "plonk challenges")
+    return tuple(Fr.to_ints(ch))
+
+
+class PlonkProver:
+    """protocol/prover.rs: PlonkProver::new(preprocessed_input, srs, transcript).prove(&witness)"""
+
+    def __init__(self, preprocessed_input, srs, transcript=None):
+        self.preprocessed_input, self.srs = preprocessed_input, srs
+        self.transcript = transcript if transcript is not None else PlonkRoundTranscript()
+        self.random_number = dict.fromkeys(CHALLENGES, 0)
+
+    def prove(self, witness, blinding=None):
+        """-> PlonkProof.  `blinding`: the 11 scalars of generate_random_numbers in the order the reference draws them (default:
+        fresh ones from `secrets`).  A witness that does not satisfy the circuit raises (ZKHIP_ERR_ARG): no proof is made from it."""
+        if blinding is None:
+            blinding = [secrets.randbelow(R_MOD) for _ in range(11)]
+        if len(blinding) != 11:
+            raise AssertionError("blinding: 11 scalars (6 + 3 + 2)")
+        key = _key_for(self.preprocessed_input, self.srs)
+        cols = [_column(v) for v in (witness.a, witness.b, witness.c, witness.public_poly)]
+        for t in cols:
+            if t.shape[0] != key.n:
+                raise AssertionError("a witness column does not have group_order entries")
+        bl = Fr.from_ints([int(b) for b in blinding])
+        xy, inf = np.zeros((9, 12), dtype=np.uint64), np.zeros(9, dtype=np.uint8)
+        ev, ch = np.zeros((6, 4), dtype=np.uint64), np.zeros((6, 4), dtype=np.uint64)
+        key.ctx.sync_stream()
+        st = N.lib().zkhip_plonk_prove(key.handle, N.ptr(cols[0]), N.ptr(cols[1]), N.ptr(cols[2]), N.ptr(cols[3]), bl.ctypes.data_as(_vp),
+                                       xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp), ev.ctypes.data_as(_vp), ch.ctypes.data_as(_vp))
+        N.check(st, "plonk prove (ZKHIP_ERR_ARG: the witness does not satisfy the circuit)")
+        fields = {f: G1Affine(xy[i], inf[i]) for i, f in enumerate(PROOF_POINTS)}
+        fields.update(zip(PROOF_SCALARS, Fr.to_ints(ev)))
+        self.random_number = dict(zip(CHALLENGES, Fr.to_ints(ch)))
+        # the caller's transcript ends where the reference's does: everything absorbed, mu drawn
+        proof = PlonkProof(**fields)
+        _replay(self.transcript, proof)
+        return proof
+
+
+def _replay(t, proof):
+    t.first_round(proof.as_commitment, proof.bs_commitment, proof.cs_commitment)
+    t.challenge_round(b"beta")
+    t.challenge_round(b"gamma")
+    t.second_round(proof.accumulator_commitment)
+    t.challenge_round(b"alpha")
+    t.third_round(proof.t_low, proof.t_mid, proof.t_high)
+    t.challenge_round(b"zeta")
+    t.fourth_round(*[getattr(proof, f) for f in PROOF_SCALARS])
+    t.challenge_round(b"nu")
+    t.fifth_round(proof.w_zeta_commitment, proof.w_zeta_omega_commitment)
+    return t.challenge_round(b"mu")
+
+
+class PlonkVerifier:
+    """protocol/verifier.rs:39-172"""
+
+    def __init__(self, group_order, proof, srs, verifier_preprocessed_input):
+        self.group_order, self.proof, self.srs = group_order, proof, srs
+        self.verifier_preprocessed_input = verifier_preprocessed_input
+
+    def verify(self, public_input_poly):
+        """-> bool.  A point off the curve or outside the subgroup raises ValueError (ZKHIP_ERR_ARG)."""
+        srs = self.srs
+        if srs.powers_of_tau_in_g2 is None:
+            raise ValueError("this TrustedSetup has no G2 half: build it with generate_srs(..., g2=True)")
+        xy, inf, ev = self.proof._arrays()
+        vxy, vinf = _points_arrays(self.verifier_preprocessed_input._commitments())
+        pub = _column(public_input_poly)
+        if pub.shape[0] != self.group_order:
+            raise AssertionError("the public-input column does not have group_order entries")
+        ok = C.c_uint8(0)
+        ctx = N.Context.get(pub.device.index)
+        st = N.lib().zkhip_plonk_verify(ctx.handle, C.c_size_t(self.group_order), vxy.ctypes.data_as(_vp), vinf.ctypes.data_as(_vp),
+                                        xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp), ev.ctypes.data_as(_vp), N.ptr(pub),
+                                        N.ptr(srs.powers_of_tau_in_g2), N.ptr(srs.g2_inf), C.c_size_t(len(srs.powers_of_tau_in_g2)),
+                                        C.byref(ok))
+        if st == N.ERR_ARG:
+            raise ValueError("plonk verify: a point is off its curve or outside the prime-order subgroup")
+        N.check(st, "plonk verify")
+        return bool(ok.value)
