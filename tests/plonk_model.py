@@ -188,11 +188,49 @@ def apply_w(poly, w):                               # protocol/utils.rs:26-39
     return Poly([c * pow(w, i, R) for i, c in enumerate(poly.c)])
 
 
+def g1_mul(pt, k):
+    """(k mod r) * pt, equal to M.g1_mul on every input (tests/test_plonk_cpu.py), in Jacobian coordinates: one inversion per product
+    where the affine ladder spends one per step.  A verdict of this model is some twenty of these; a test asks for sixteen verdicts."""
+    P = M.P
+    k %= R
+    if pt is None or k == 0:
+        return None
+    x2, y2 = pt
+    X, Y, Z = x2, y2, 1
+    for bit in bin(k)[3:]:
+        if Z:                                                                 # double (a = 0)
+            A, B = X * X % P, Y * Y % P
+            C = B * B % P
+            D = 2 * ((X + B) * (X + B) - A - C) % P
+            E = 3 * A % P
+            X3 = (E * E - 2 * D) % P
+            X, Y, Z = X3, (E * (D - X3) - 8 * C) % P, 2 * Y * Z % P
+        if bit == "1":                                                        # add the affine point
+            if not Z:
+                X, Y, Z = x2, y2, 1
+                continue
+            ZZ = Z * Z % P
+            H, r = (x2 * ZZ - X) % P, (y2 * Z % P * ZZ - Y) % P
+            if H == 0:
+                if r:
+                    X, Y, Z = 1, 1, 0
+                    continue
+                return M.g1_mul(pt, k)                                        # the running point equals pt: not within the ladder of k < r
+            HH = H * H % P
+            HHH, V = H * HH % P, X * HH % P
+            X3 = (r * r - HHH - 2 * V) % P
+            X, Y, Z = X3, (r * (V - X3) - Y * HHH) % P, Z * H % P
+    if not Z:
+        return None
+    zi = pow(Z, P - 2, P)
+    return X * zi % P * zi % P, Y * zi % P * zi % P * zi % P
+
+
 def commit_tau(poly, tau, n_srs=None):
     """UnivariateKZG::commitment against tau^i G: p(tau) G (an SRS shorter than the polynomial is the reference's index panic)"""
     if n_srs is not None and len(poly.c) > n_srs:
         raise IndexError("powers_of_tau_in_g1[%d]" % n_srs)
-    return M.g1_mul(M.G1, poly.evaluate(tau))
+    return g1_mul(M.G1, poly.evaluate(tau))
 
 
 def vpi(cpi, tau):                                  # verifier.rs:24-36
@@ -283,7 +321,7 @@ def prove(cpi, wit, tau, blinding, n_srs=None, want_challenges=False):
 def _msm(pairs):
     acc = None
     for pt, k in pairs:
-        acc = M.g1_add(acc, M.g1_mul(pt, k))
+        acc = M.g1_add(acc, g1_mul(pt, k))
     return acc
 
 
@@ -306,7 +344,7 @@ def verifier_points(n, proof, v, public_poly):
                (t_comb, -zh_zeta)])
     f1 = _msm([(d1, 1), (proof["as_commitment"], nu), (proof["bs_commitment"], pow(nu, 2, R)), (proof["cs_commitment"], pow(nu, 3, R)),
                (v["sigma_1"], pow(nu, 4, R)), (v["sigma_2"], pow(nu, 5, R))])
-    e1 = M.g1_mul(M.G1, nu * az + pow(nu, 2, R) * bz + pow(nu, 3, R) * cz + pow(nu, 4, R) * s1z + pow(nu, 5, R) * s2z + mu * zwz - r0)
+    e1 = g1_mul(M.G1, nu * az + pow(nu, 2, R) * bz + pow(nu, 3, R) * cz + pow(nu, 4, R) * s1z + pow(nu, 5, R) * s2z + mu * zwz - r0)
     wz, wzw = proof["w_zeta_commitment"], proof["w_zeta_omega_commitment"]
     left = _msm([(wz, 1), (wzw, mu)])
     right = _msm([(wz, zeta), (wzw, w * mu % R * zeta), (f1, 1), (e1, -1)])
@@ -321,7 +359,7 @@ def verify(n, proof, v, public_poly):
 def verify_tau(n, proof, v, public_poly, tau):
     """the same verdict without a pairing when tau is known: e(L, tau G2) == e(Rt, G2)  <=>  tau L == Rt (G1, G2 of prime order)"""
     left, right = verifier_points(n, proof, v, public_poly)
-    return M.g1_mul(left, tau) == right if left is not None else right is None
+    return g1_mul(left, tau) == right if left is not None else right is None
 
 
 def tamper(proof, field):
@@ -427,7 +465,7 @@ def fast_check(cpi, wit, tau, blinding, proof):
     beta, gamma, alpha, zeta, nu, mu = compute_verifier_challenges(proof)
     dom = FastDomain(n)
     w = dom.w[1]
-    G = lambda k: M.g1_mul(M.G1, k)
+    G = lambda k: g1_mul(M.G1, k)
     acc = fast_accumulator(cpi, wit, beta, gamma)
     cols = dict(a=wit["a"], b=wit["b"], c=wit["c"], pi=wit["public_poly"], acc=acc, **{f: cpi[f] for f in CPI_FIELDS})
 
@@ -467,8 +505,8 @@ def fast_check(cpi, wit, tau, blinding, proof):
                + nu * (T["a"] - az) + pow(nu, 2, R) * (T["b"] - bz) + pow(nu, 3, R) * (T["c"] - cz)
                + pow(nu, 4, R) * (T["sigma_1"] - s1z) + pow(nu, 5, R) * (T["sigma_2"] - s2z)) % R
     t_zeta = _msm([(proof["t_low"], 1), (proof["t_mid"], pow(zeta, n, R)), (proof["t_high"], pow(zeta, 2 * n, R))])
-    if M.g1_mul(proof["w_zeta_commitment"], (tau - zeta) % R) != M.g1_add(G(r_known), M.g1_mul(t_zeta, (-Z["zh"]) % R)):
+    if g1_mul(proof["w_zeta_commitment"], (tau - zeta) % R) != M.g1_add(G(r_known), g1_mul(t_zeta, (-Z["zh"]) % R)):
         bad.append("w_zeta_commitment")
-    if M.g1_mul(proof["w_zeta_omega_commitment"], (tau - zeta * w) % R) != G((T["z"] - zwz) % R):
+    if g1_mul(proof["w_zeta_omega_commitment"], (tau - zeta * w) % R) != G((T["z"] - zwz) % R):
         bad.append("w_zeta_omega_commitment")
     return bad

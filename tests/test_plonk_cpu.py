@@ -208,3 +208,15 @@ def test_c_challenges_with_an_identity_point(proved):
     assert _c_challenges(proof) == PL.compute_verifier_challenges(proof)
     small = dict(proof, as_commitment=(0, 2), a_s_poly_zeta=0)                       # a zero coordinate prints as the empty string
     assert _c_challenges(small) == PL.compute_verifier_challenges(small)
+
+
+def test_model_scalar_multiplication_equals_the_affine_ladder():
+    """plonk_model.g1_mul (Jacobian, one inversion) against the golden model's affine double-and-add: scalars at the edges of [0, r),
+    beyond r, random ones; the generator, another point and the identity"""
+    rng = random.Random(17)
+    other = M.g1_mul(M.G1, 0xABCDEF)
+    for pt, scalars in ((M.G1, [0, 1, 2, 3, R - 2, R - 1, R, R + 1, (1 << 255) - 1, rng.randrange(R)]),
+                        (other, [1, 2, R - 1, rng.randrange(R), rng.randrange(R)]), (None, [0, 5])):
+        for k in scalars:
+            got = PL.g1_mul(pt, k)
+            assert got == M.g1_mul(pt, k) and M.on_curve(got), k

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -122,6 +123,15 @@ enum { C_BETA, C_GAMMA, C_ALPHA, C_ZETA, C_NU, C_MU, N_CHALLENGES };
 // this budget -- at n = 2^20 (D = 2^22) they take 1.25 GiB, less than the 1.6 GiB shifted-SRS table the commits of that size already
 // hold -- and recomputed per proof (ten transforms) above it.
 constexpr size_t PLONK_CACHE_BUDGET = (size_t)2 << 30;
+// diagnostic aid (tests/test_gpu_plonk.py): ZKHIP_PLONK_CACHE_BUDGET=<bytes> replaces the budget, 0 makes every key an uncached one.
+// Read at each key's creation, not once per process: a key keeps the choice it was made with.
+size_t plonk_cache_budget() {
+    const char* e = std::getenv("ZKHIP_PLONK_CACHE_BUDGET");
+    if (!e || !*e) return PLONK_CACHE_BUDGET;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    return end && *end == '\0' ? (size_t)v : PLONK_CACHE_BUDGET;
+}
 constexpr int N_PRE = 10;
 const uint64_t COSET_SHIFT = 7;          // arkworks' multiplicative generator of Fr; the quotient does not depend on the choice
 
@@ -323,7 +333,7 @@ extern "C" int zkhip_plonk_key_create(zkhip_ctx* c, size_t n, const uint64_t* co
     k->ctx = c; k->n = n; k->D = D; k->S = n + 8;
     k->log_n = log2_exact(n); k->log_D = log2_exact(D); k->ratio = (uint32_t)(D / n);
     k->srs_xy = d_table ? nullptr : d_points_xy; k->srs_table = d_table; k->srs_inf = d_points_inf; k->n_points = n_points;
-    const bool cache = (size_t)N_PRE * D * 32 <= PLONK_CACHE_BUDGET;
+    const bool cache = (size_t)N_PRE * D * 32 <= plonk_cache_budget();
     const size_t work_bytes = work_layout(*k, nullptr, !cache, nullptr);
     if (dev_alloc(k->evals, 8 * n * 32) != hipSuccess || dev_alloc(k->coeffs, 8 * k->S * 32) != hipSuccess ||
         dev_alloc(k->omega, n * 32) != hipSuccess || dev_alloc(k->gpow, k->S * 32) != hipSuccess ||
