@@ -196,3 +196,77 @@ def test_five_table_rounds_on_the_matrix_cores_at_every_size(grid):
                           "-k", "(test_composed_prove_random and 5-) or test_multi_composed_random or test_hip_path_reproduces_golden or test_sum_check_proof"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1200)
     assert out.returncode == 0, out.stdout.decode()[-3000:]
+
+
+# ---- the two byte-GEMM kernels at their per-workgroup limit ---------------------------------------------------------------------------
+# composed_round_dot_kernel and composed_cross2_mfma_kernel feed bytes as u - 128 to int8 MFMAs and rebuild the unsigned sums
+# sum ua ub = G + 128 UA + 128 UB - 16384 J in 32 bits, for at most 65536 indices per workgroup.  The production grids give a workgroup
+# 4096 indices and random bytes, so a true sum never has its top bit set.  Here one workgroup takes all 65536 and the operand bytes are 0xFF:
+# M = ((r >> 192) << 192) - 1 has 24 low bytes of 0xFF as a STORED value, every byte-product sum of the 24 x 24 low positions is
+# 65536 x 255^2 = 4 261 478 400 > 2^31, and with all-zero tables every fed byte is -128: G = +2^30 and the true sums are 0.
+_LIMIT_CHILD = """
+import sys; sys.path.insert(0, %(root)r)
+import numpy as np
+import zk_cryptography_amd as zk
+from oracle import oracle as ora
+R = zk.Fr.MODULUS
+M = ((R >> 192) << 192) - 1
+ONE = (1 << 256) %% R                               # the stored form of 1
+n = 1 << 18
+def const(v, count=n):                              # `count` entries with the STORED value v: raw limbs, canonical
+    assert 0 <= v < R
+    return np.tile(np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint64), (count, 1))
+def quarters(*parts):
+    return np.concatenate(parts)
+rnd = lambda seed: ora.random_fr(n // 4, seed)
+tables = %(tables)s
+t = np.stack(tables)
+assert t.shape == (%(k)d, n, 4) and t.dtype == np.uint64
+assert M.to_bytes(32, "little")[:24] == bytes([255]) * 24 and 65536 * 255 * 255 > 1 << 31
+proof, ch = zk.ComposedSumcheck(zk.ComposedMultilinear(list(t))).prove()
+rp, och = ora.composed_prove(t)
+assert np.array_equal(proof.round_polys, rp) and np.array_equal(ch, och)
+print("limit ok")
+"""
+
+
+def _limit_child(tables, k, env):
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = _LIMIT_CHILD % dict(root=root, tables=tables, k=k)
+    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "limit ok" in res.stdout, res.stdout[-2000:] + res.stderr[-2000:]
+
+
+ROUND_DOT_LIMIT_TABLES = {
+    # Q_t = M on every plane (table 0 = M, tables 1-3 = the stored 1), l = d = M (table 4: M below, 2M mod r above)
+    "M": "[const(M), const(ONE), const(ONE), const(ONE), quarters(const(M, n // 2), const(2 * M % R, n // 2))]",
+    "zero": "[const(0)] * 5",
+}
+
+
+@pytest.mark.parametrize("grid", ["2", "1"])
+@pytest.mark.parametrize("fill", ["M", "zero"])
+def test_round_dot_at_the_workgroup_limit(fill, grid):
+    """K = 5, 2^18 entries, ZKHIP_ROUND_DOT_MIN_LOG=8.  ZKHIP_ROUND_GRID=2: launch_round() gives the first round (work = 2^17 output pairs)
+    two workgroups of per_wg = 65536 staged indices each = CDT_MAX_PER_WG, composed_round_dot_kernel's limit; the later rounds halve it.
+    ZKHIP_ROUND_GRID=1: per_wg = 131072 > CDT_MAX_PER_WG, so the first round falls back to the vector form (composed_round_kernel<5>) and
+    the second (2^16 pairs, one workgroup of 65536) is the matrix-core one.  Fresh process: the overrides are read once.  The oracle's proof,
+    bit for bit."""
+    _limit_child(ROUND_DOT_LIMIT_TABLES[fill], 5, dict(ZKHIP_ROUND_DOT_MIN_LOG="8", ZKHIP_ROUND_GRID=grid))
+
+
+CROSS2_LIMIT_TABLES = {
+    "M": "[const(M), const(M)]",
+    "zero": "[const(0), const(0)]",
+    # the four blocks of each table differ, and so do the sixteen block pairs
+    "quarters": "[quarters(const(M, n // 4), const(0, n // 4), rnd(7001), const(M, n // 4)), quarters(rnd(7002), const(M, n // 4), const(0, n // 4), const(M - 1, n // 4))]",
+}
+
+
+@pytest.mark.parametrize("fill", ["M", "zero", "quarters"])
+def test_cross2_mfma_at_the_workgroup_limit(fill):
+    """Two tables of 2^18 entries, ZKHIP_STAGE=1 (the stage form from 2^15 entries on) and ZKHIP_CROSS_GRID=1: stage_sums() launches
+    composed_cross2_mfma_kernel for the first stage with m = 2^16 indices per block and grid = max(min(1, m / 128), ceil(m / 65536)) = 1 --
+    ONE workgroup of 65536 indices, the kernel's limit (the default is 512 workgroups of 128).  The oracle's proof, bit for bit."""
+    _limit_child(CROSS2_LIMIT_TABLES[fill], 2, dict(ZKHIP_STAGE="1", ZKHIP_CROSS_GRID="1"))

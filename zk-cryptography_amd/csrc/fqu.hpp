@@ -4,13 +4,15 @@
 // plain multiply or a carry add (profiles/r01/ubench_alu_gfx950.txt), so what a saturated product pays for its
 // 288 carry adds is pure overhead: with 28-bit limbs a whole column of limb products (<= 28 of them, < 2^58
 // each) fits one 64-bit accumulator and the product is 406 mads and nothing else.  R is 11 bits above p, which
-// also makes lazy reduction free: values up to ~64 p are legal multiplier inputs and the product is always < 2p,
+// also makes lazy reduction free: the product (a b + m p) / R is < 2p whenever value(a) value(b) < R p = 2520 p^2
+// (both values up to 50 p, or one up to 64 p against one up to 39 p; the group law stays below 18 p x 18 p),
 // so additions are 14 independent adds and subtractions add a precomputed multiple of p instead of branching.
 //
 // Conventions
 //   value  : the integer sum l[i] 2^(28 i), congruent to x * 2^392 (mod p); NOT necessarily < p.
 //   limbs  : "weak" = limbs 0..12 < 2^28 + 2^4 (what sub/weak_norm return), "normalised" = limbs 0..12 < 2^28
-//            (what mul returns).  Multiplier inputs may carry limbs up to 2^29.5.
+//            (what mul returns).  Multiplier inputs may carry limbs up to 2^29.5 and values below 64 p (a column of
+//            14 such limb products and 14 reduction terms stays below 2^63).
 // Points enter from / leave to the arkworks layout (12 x 32-bit saturated limbs, R = 2^384) through
 // from_ark / to_ark; parity with the reference is checked on the converted, canonical values.
 #pragma once
@@ -78,8 +80,10 @@ __device__ __forceinline__ FqU fqu_add(const FqU& a, const FqU& b) {   // lazy: 
 }
 __device__ __forceinline__ FqU fqu_dbl(const FqU& a) { return fqu_add(a, a); }
 
-// a - b + K p, K in {4, 8, 16}: the redundant limbs of K p dominate any weakly normalised subtrahend, so no limb goes
-// negative; requires value(b) < (K - 1) p.  Result weakly normalised, value < value(a) + K p.
+// a - b + K p, K in {4, 8, 16}: limbs 0..12 of the redundant K p are >= 2^29 - 2 (tools/gen_fqu_consts.py asserts it), so they
+// dominate a weakly normalised subtrahend AND the fqu_dbl(..) of a normalised one (limbs <= 2^29 - 2: what g1u_double, g1u_madd
+// and g1u_add pass) and no limb goes negative; requires value(b) < (K - 1) p and limbs of a up to 2^29.5.  Result weakly
+// normalised, value = value(a) + K p - value(b) exactly.
 template <int K>
 __device__ __forceinline__ FqU fqu_sub(const FqU& a, const FqU& b) {
     FqU r;
@@ -92,8 +96,9 @@ __device__ __forceinline__ FqU fqu_sub(const FqU& a, const FqU& b) {
 }
 __device__ __forceinline__ FqU fqu_neg4(const FqU& b) { return fqu_sub<4>(FqU::zero(), b); }   // value(b) < 3p
 
-// Montgomery product a b 2^-392: one 64-bit accumulator per column, 406 mads.  Inputs: limbs < 2^29.5, values
-// < 64 p.  Output normalised, value < 2p.
+// Montgomery product a b 2^-392: one 64-bit accumulator per column, 406 mads.  Inputs: limbs <= 2^29.5, values
+// < 64 p.  Output normalised, value < value(a) value(b) / 2^392 + p: < 2p when value(a) value(b) < 2^392 p = 2520 p^2
+// (64 p x 64 p gives up to 2.63 p; tests/test_gpu_arith.py::test_fqu_mul_contract_edge).
 __device__ __forceinline__ FqU fqu_mul_inline(const FqU& a, const FqU& b) {
     constexpr int N = FqU::N;
     uint32_t m[N];
