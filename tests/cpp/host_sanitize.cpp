@@ -1,6 +1,7 @@
 // The HOST-only product code of libzkhip that does real arithmetic -- csrc/host_g1.hpp (the MSM's epilogue: XYZZ group law, the
 // weighted double-and-add sweep, affine conversion), csrc/host_fr.hpp (Fr, the interpolation matrices, SHA-256, the Fiat-Shamir
-// transcript), csrc/msm_geometry.hpp (the digit windows / bucket sets of a pass), csrc/host_util.hpp (the thread pool) -- compiled with
+// transcript), csrc/msm_geometry.hpp (the digit windows / bucket sets of a pass), csrc/host_util.hpp (the thread pool), csrc/tunables.hpp
+// (the environment switches' parser) -- compiled with
 // g++ -fsanitize=address,undefined (sanitizers on the CPU build only) and checked against the CPU oracle.  Run twice by
 // tests/test_host_sanitizers_cpu.py: the outputs must be identical (determinism).  Exit code 0 = everything matched.
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include "../../zk-cryptography_amd/csrc/host_g1.hpp"
 #include "../../zk-cryptography_amd/csrc/host_util.hpp"
 #include "../../zk-cryptography_amd/csrc/msm_geometry.hpp"
+#include "../../zk-cryptography_amd/csrc/tunables.hpp"
 extern "C" {
 #include "../../oracle/zkoracle.h"
 }
@@ -238,6 +240,26 @@ static void test_loan() {
     EXPECT(desk.out == 0);
 }
 
+// every switch under the odd strings of tests/test_tunables_cpu.py and a few longer ones: a value is the default or lies in the range
+static void test_tunables() {
+    using namespace zk::env;
+    const char* odd[] = {"", "0", "1", "abc", "-1", "01", "10", " 7", "+3x", "200", "-2147483649", "2147483648", "99999999999999999999999",
+                         "-99999999999999999999999", "18446744073709551616", "1e9", "0x10", "\t\n"};
+    for (const Switch& s : ALL) {
+        for (const char* v : odd) {
+            setenv(s.name, v, 1);
+            if (s.kind == TEXT) { EXPECT(text(s) && std::strcmp(text(s), v) == 0); continue; }
+            const long long x = read(s);
+            if (s.kind == FLAG) EXPECT(x == 0 || x == 1);
+            if (s.kind == INT) EXPECT(x == s.def || (x >= s.lo && x <= s.hi));
+            mix(&x, sizeof x);
+        }
+        unsetenv(s.name);
+        if (s.kind == TEXT) EXPECT(text(s) == nullptr);
+        else EXPECT(read(s) == s.def);
+    }
+}
+
 int main() {
     test_loan();
     test_fr();
@@ -245,6 +267,7 @@ int main() {
     test_g1();
     test_geometry();
     test_pool();
+    test_tunables();
     std::printf("digest %016llx\n%s\n", (unsigned long long)g_digest, g_failed ? "FAILED" : "ok");
     return g_failed ? 1 : 0;
 }

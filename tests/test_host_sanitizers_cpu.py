@@ -1,5 +1,5 @@
 """SURVEY 5's "ASan-enabled host build + determinism check": the HOST-only product code that does real arithmetic (csrc/host_g1.hpp,
-csrc/host_fr.hpp, csrc/msm_geometry.hpp, csrc/host_util.hpp) built with g++ -fsanitize=address,undefined and run against the CPU oracle
+csrc/host_fr.hpp, csrc/msm_geometry.hpp, csrc/host_util.hpp, csrc/tunables.hpp) built with g++ -fsanitize=address,undefined and run against the CPU oracle
 (tests/cpp/host_sanitize.cpp).  Any sanitizer report, mismatch or difference between two runs fails.  (GPU sanitizers are not available on
 this pool; the device code is covered by the parity suite.)"""
 import os

@@ -17,6 +17,7 @@
 #include "composed_dot.hpp"
 #include "composed_pipe.hpp"
 #include "host_fr.hpp"
+#include "tunables.hpp"
 
 using namespace zk;
 
@@ -46,14 +47,9 @@ static void launch_round(zkhip_ctx* c, bool fold, const TablePtrs& tp, size_t n,
         // (K = 3, built and measured the same way: 7 -> 3 products in the first round, but its rounds at 2^20 are 35-55 us long and the staging,
         // the barriers and the closing reduction cost more than the products saved: 56 -> 67 us.  Not instantiated.)
         // ZKHIP_ROUND_DOT=0 keeps the vector form (A/B runs), ZKHIP_ROUND_DOT_MIN_LOG=<l> moves both thresholds (tests: the small sizes too).
-        static const int dot_min_log = [] {
-            const char* on = std::getenv("ZKHIP_ROUND_DOT");
-            if (on && std::atoi(on) == 0) return 64;
-            const char* e = std::getenv("ZKHIP_ROUND_DOT_MIN_LOG");
-            return e ? -std::max(8, std::atoi(e)) : 18;
-        }();
+        static const long long dot_min_log = zk::env::read(zk::env::ROUND_DOT) ? zk::env::read(zk::env::ROUND_DOT_MIN_LOG) : 64;   // (64 = never)
         const size_t work = fold ? n / 4 : n / 2;
-        const int min_log = dot_min_log < 0 ? -dot_min_log : dot_min_log + (fold ? 1 : 0);
+        const long long min_log = dot_min_log != zk::env::UNSET ? dot_min_log : fold ? 19 : 18;
         const size_t per_wg = (work + (size_t)grid * CDT_ROWS - 1) / ((size_t)grid * CDT_ROWS) * CDT_ROWS;
         if (min_log < 64 && work >= ((size_t)1 << min_log) && per_wg <= CDT_MAX_PER_WG) {
             if (fold)
@@ -279,16 +275,15 @@ struct ComposedRun {
         // one record per workgroup, and the closing kernel -- one workgroup, on the critical path -- adds them up: a claim of ONE term
         // launches at most 512 workgroups (K = 2 at 2^22: 0.626 / 0.621 / 0.614-0.621 / 0.619 ms at 2048 / 1024 / 512 / 256; the GKR layers,
         // two terms per claim, measured no better with fewer).  ZKHIP_ROUND_GRID overrides (diagnostics).
-        static const int grid_env = [] { const char* e = std::getenv("ZKHIP_ROUND_GRID"); return e ? std::atoi(e) : 0; }();
+        static const int grid_env = (int)zk::env::read(zk::env::ROUND_GRID);
         const int grid_cap = grid_env > 0 ? grid_env : n_terms == 1 ? 512 : (int)MLE_MAX_GRID;
         // small folding rounds with a term of three and more tables: K + 1 lanes per output pair (composed_round_tsplit_kernel), ONE pass
         // per workgroup -- the grid is sized for the widest such term and every term of the round uses it (the records of a round
-        // are per workgroup).  ZKHIP_ROUND_TSPLIT=0: off (A/B runs).
-        static const bool tsplit_on = [] { const char* e = std::getenv("ZKHIP_ROUND_TSPLIT"); return !e || std::atoi(e) != 0; }();
+        // are per workgroup).
         uint32_t k_wide = 0;
         bool any_lin = false;
         for (uint32_t p = 0; p < n_terms; ++p) { k_wide = std::max(k_wide, term_sizes[p]); any_lin = any_lin || lin_cur[p] != nullptr; }
-        const bool tsplit = tsplit_on && fold && k_wide >= 3 && !any_lin && work >= 1 && work <= CMP_TSPLIT_MAX;
+        const bool tsplit = fold && k_wide >= 3 && !any_lin && work >= 1 && work <= CMP_TSPLIT_MAX;
         const size_t tsplit_per_wg = (size_t)(MLE_BLOCK / 64) * (64 / (k_wide + 1));
         const int grid = tsplit ? (int)std::min<size_t>(MLE_MAX_GRID, (work + tsplit_per_wg - 1) / tsplit_per_wg)
                          : split ? (int)((4 * work + MLE_BLOCK - 1) / MLE_BLOCK)
@@ -379,11 +374,11 @@ struct ComposedRun {
         return true;
     }
     bool stage_ok() const {
-        static const int mode = [] { const char* e = std::getenv("ZKHIP_STAGE"); return e ? std::atoi(e) : -1; }();
+        static const int mode = (int)zk::env::read(zk::env::STAGE);
         if (mode == 0) return false;
         if (mode == 1) return stage_possible((size_t)1 << 15);
-        static const int log1 = [] { const char* e = std::getenv("ZKHIP_STAGE_MIN_LOG_ONE"); const int v = e ? std::atoi(e) : 0; return v >= 12 && v <= 30 ? v : 18; }();     // tuning aids (tools/sweep_stage.sh)
-        static const int logm = [] { const char* e = std::getenv("ZKHIP_STAGE_MIN_LOG_MANY"); const int v = e ? std::atoi(e) : 0; return v >= 12 && v <= 30 ? v : 18; }();
+        static const int log1 = (int)zk::env::read(zk::env::STAGE_MIN_LOG_ONE);     // tuning aids (tools/sweep_stage.sh)
+        static const int logm = (int)zk::env::read(zk::env::STAGE_MIN_LOG_MANY);
         return stage_possible(n_terms >= 2 ? (size_t)1 << logm : (size_t)1 << log1);
     }
     MultiTablePtrs stage_tables() const {
@@ -402,11 +397,11 @@ struct ComposedRun {
     int stage_sums(int* n_records) {
         const size_t m = cn / 4;
         ProfScope ps(c, "composed_cross2", 0.0);
-        static const bool no_mfma = [] { const char* e = std::getenv("ZKHIP_CROSS_VALU"); return e && std::atoi(e) != 0; }();   // diagnostics: A/B
+        static const bool no_mfma = zk::env::read(zk::env::CROSS_VALU) != 0;   // diagnostics: A/B
         if (!no_mfma && m >= 1024 && m <= (size_t)256 * 65536) {
             // byte outer products on the matrix cores: >= 128 indices and <= 65536 per workgroup (int32 accumulators)
             // up to four workgroups per CU (42 KiB of LDS each), as many records as the scratch holds
-            static const size_t cap_env = [] { const char* e = std::getenv("ZKHIP_CROSS_GRID"); return e ? (size_t)std::atoi(e) : (size_t)0; }();   // diagnostics
+            static const size_t cap_env = (size_t)zk::env::read(zk::env::CROSS_GRID);   // diagnostics
             const size_t cap = std::min<size_t>(cap_env ? cap_env : 512, (size_t)(8 * ZK_MAX_PARTIALS) / ((size_t)CST_VALS * n_terms));
             const int grid = (int)std::max<size_t>(std::min<size_t>(cap, m / 128), (m + 65535) / 65536);
             hipLaunchKernelGGL(composed_cross2_mfma_kernel, dim3(grid, n_terms), dim3(256), 0, c->stream, stage_tables(), cn, n_terms, d_partials);
@@ -470,7 +465,7 @@ struct ComposedRun {
         if (pipe_on() && pipe_eligible(meta)) {
             ZK_TRY(c->allow_big_lds((const void*)composed_tail_pipe_kernel, (size_t)CMP_TAIL_ENTRIES * 32));
             hipLaunchKernelGGL(composed_tail_pipe_kernel, dim3(1 + extra_wg()), dim3(PIPE_BLOCK), (size_t)total_all * m * 32, c->stream, tt, total_all, m,
-                               fold ? 1u : 0u, fold ? prev_challenge() : nullptr, close_args(), n_rounds - round, (const uint64_t*)nullptr, 0u, pipe_max_q());
+                               fold ? 1u : 0u, fold ? prev_challenge() : nullptr, close_args(), n_rounds - round, (const uint64_t*)nullptr, 0u, PIPE_MAX_Q);
         } else {
             ZK_TRY(c->allow_big_lds((const void*)composed_tail_kernel, (size_t)CMP_TAIL_ENTRIES * 32));
             hipLaunchKernelGGL(composed_tail_kernel, dim3(1 + extra_wg()), dim3(CMP_TAIL_BLOCK), (size_t)total_all * m * 32, c->stream, tt, total_all, m,
@@ -479,24 +474,13 @@ struct ComposedRun {
         round = n_rounds;
         return ZKHIP_OK;
     }
-    static uint32_t pipe_max_q() {     // forms are computed ahead for tables of <= 4 max_q entries (ZKHIP_PIPE_MAX_Q: tuning)
-        static const uint32_t v = [] { const char* e = std::getenv("ZKHIP_PIPE_MAX_Q"); return e ? (uint32_t)std::atoi(e) : PIPE_MAX_Q; }();
-        return v;
-    }
-    static size_t pipe_tail_max() {    // tables of at most this many entries go to the single-workgroup tail behind pipelined rounds (ZKHIP_PIPE_TAIL: tuning)
-        static const size_t v = [] { const char* e = std::getenv("ZKHIP_PIPE_TAIL"); return e ? (size_t)std::atoi(e) : (size_t)512; }();
-        return v;
-    }
-    static bool pipe_on() {
-        static const bool on = [] { const char* e = std::getenv("ZKHIP_PIPE"); return !e || std::atoi(e) != 0; }();
-        return on;
-    }
+    static constexpr size_t PIPE_TAIL_MAX = 512;                 // tables of at most this many entries go to the single-workgroup tail behind pipelined rounds
+    static bool pipe_on() { static const bool on = zk::env::read(zk::env::PIPE) != 0; return on; }
     // ---- the rounds between the streaming sizes and the LDS tail, one launch per round and one round ahead (composed_pipe.hpp) ----
     // Entered with tables of cn entries (a fold at the last challenge pending or not) that do not fit the tail yet.
     static constexpr size_t PIPE_MID_MAX = (size_t)1 << 17;      // entries per table: above, the streaming forms (stages, wide rounds) are faster
     bool pipe_mid_ok() const {
-        static const bool mid_on = [] { const char* e = std::getenv("ZKHIP_PIPE_MID"); return !e || std::atoi(e) != 0; }();
-        return pipe_on() && mid_on && pipe_eligible(meta) && after() > tail_len && after() <= PIPE_MID_MAX && after() >= 4 * PIPE_TILE && n_rounds - round >= 2;
+        return pipe_on() && pipe_eligible(meta) && after() > tail_len && after() <= PIPE_MID_MAX && after() >= 4 * PIPE_TILE && n_rounds - round >= 2;
     }
     MultiTablePtrs pipe_tables(bool with_out) const {
         MultiTablePtrs mp = {};
@@ -532,12 +516,12 @@ struct ComposedRun {
     uint32_t pipe_steady_rounds() const {
         size_t cn_ = cn;
         uint32_t round_ = round, k = 0;
-        while ((cn_ > tail_len || cn_ > pipe_tail_max()) && cn_ >= 8 * PIPE_TILE && n_rounds - round_ >= 2) { cn_ /= 2; ++round_; ++k; }
+        while ((cn_ > tail_len || cn_ > PIPE_TAIL_MAX) && cn_ >= 8 * PIPE_TILE && n_rounds - round_ >= 2) { cn_ /= 2; ++round_; ++k; }
         return k;
     }
     static size_t pipe_wgs() {         // workgroups that take tiles, at most (ZKHIP_PIPE_WGS: tuning)
-        static const size_t v = [] { const char* e = std::getenv("ZKHIP_PIPE_WGS"); const int x = e ? std::atoi(e) : 0; return x >= 1 && x <= (int)PIPE_MAX_WGS ? (size_t)x : (size_t)256; }();
-        return v;
+        static_assert(zk::env::PIPE_WGS.hi == (long long)PIPE_MAX_WGS, "the records of a pipelined round are sized for PIPE_MAX_WGS workgroups");
+        static const size_t v = (size_t)zk::env::read(zk::env::PIPE_WGS); return v;
     }
     // one steady round's bookkeeping (what a launch of composed_pipe_round_kernel with fold = 1 leaves behind)
     void pipe_advance() {
@@ -574,7 +558,7 @@ struct ComposedRun {
         ZK_TRY(c->allow_big_lds((const void*)composed_tail_pipe_kernel, (size_t)CMP_TAIL_ENTRIES * 32));
         ProfScope ps(c, "composed_tail", 0.0);
         hipLaunchKernelGGL(composed_tail_pipe_kernel, dim3(1 + extra_wg()), dim3(PIPE_BLOCK), (size_t)total_all * cn * 32, c->stream, current_tables(), total_all,
-                           (uint32_t)cn, 0u, (const uint64_t*)nullptr, close_args(), n_rounds - round, (const uint64_t*)d_pipe_rec[pipe_parity], pipe_records, pipe_max_q());
+                           (uint32_t)cn, 0u, (const uint64_t*)nullptr, close_args(), n_rounds - round, (const uint64_t*)d_pipe_rec[pipe_parity], pipe_records, PIPE_MAX_Q);
         pipe_records = 0;
         round = n_rounds;
         return ZKHIP_OK;

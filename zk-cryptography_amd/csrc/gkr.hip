@@ -21,6 +21,7 @@
 #include "mle_kernels.hpp"
 #include "outer_transcript.hpp"
 #include "shard.hpp"
+#include "tunables.hpp"
 
 // ---- a layer's sumcheck in time linear in its width -------------------------------------------------------------
 // The reference proves, per layer,   sum_{b,c} add~(b,c) (V(b) + V(c)) + mul~(b,c) V(b) V(c)   with the multi-composed
@@ -514,7 +515,7 @@ int layer_enqueue_device(zkhip_ctx* c, const LayerDev& ld, uint32_t l, const uin
         if (!replayable) launch_gate_weights(c, n_gates, n_gate_vars, pb, pc, av, bv, false, sc.eqh, sc.wg);
         else if (n_gates > 2) return ZKHIP_ERR_SHAPE;       // (one gate variable: the caller uploaded at most two weights)
     }
-    static const bool fuse_small = [] { const char* e = std::getenv("ZKHIP_GKR_FUSE_SMALL"); return !e || std::atoi(e) != 0; }();
+    static const bool fuse_small = zk::env::read(zk::env::GKR_FUSE_SMALL) != 0;
     const bool small = fuse_small && w_len <= GKR_SMALL_ROWS;
     auto rows1_args = [&](const LayerDev& L, const uint64_t* V, size_t rows, bool two) {       // the first rows of layer L (every gate once: the weights are formed there)
         GateRowsArgs ra = {};
@@ -548,12 +549,14 @@ int layer_enqueue_device(zkhip_ctx* c, const LayerDev& ld, uint32_t l, const uin
     }
     // ---- rounds over c, b at u = the challenges just recorded (in the arena)
     if (small) {                                           // eq(u), w_b and the second rows: one workgroup, one launch
+        ProfScope ps(c, "gkr_small_mid", 0.0);
         GateRowsArgs ra = {};
         ra.row_off = ld.csr1; ra.ids = ld.csr1 + w_len + 1; ra.gate_type = ld.type; ra.other_in = ld.in0; ra.wg = sc.wg; ra.factor = sc.equ;
         ra.n_rows = (uint32_t)w_len; ra.phase = 2u; ra.add_out = sc.aa; ra.mul_out = sc.am; ra.v = d_w; ra.vu_ptr = sc.evals; ra.t1 = sc.t1; ra.t2 = sc.t2;
         ra.row_stride = 1u;
         hipLaunchKernelGGL(gkr_small_mid_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)ar_ch, s, sc.equ, d_w, sc.evals, ra);
     } else {
+        ProfScope ps(c, "gkr_mid", 0.0);
         launch_eq_table(c, ar_ch, s, sc.eqh, sc.equ, d_w, sc.dot_partials, sc.evals);
         hipLaunchKernelGGL(gkr_gate_rows_kernel, dim3(gw), dim3(MLE_BLOCK), 0, c->stream, ld.csr1, ld.csr1 + w_len + 1, ld.type, ld.in0, sc.wg, sc.equ,
                            (uint32_t)w_len, 2u, sc.aa, (uint64_t*)nullptr, sc.am, d_w, (const uint64_t*)sc.evals, sc.t1, sc.t2);
@@ -571,11 +574,13 @@ int layer_enqueue_device(zkhip_ctx* c, const LayerDev& ld, uint32_t l, const uin
     if (small) {                                           // ... and the next layer's first rows, if that layer is small too
         const bool with_rows = next && w_len_next <= GKR_SMALL_ROWS && !next->bad_label && w_len_next == next->w_len && w_len_next == 2 * w_len &&
                                next->n_gates <= ((size_t)1 << (l + 1));      // (what the next call checks before it would launch them itself)
+        ProfScope ps(c, "gkr_small_end", 0.0);
         const GateRowsArgs ra = with_rows ? rows1_args(*next, d_w_next, w_len_next, true) : GateRowsArgs();
         hipLaunchKernelGGL(gkr_small_end_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)(ar_ch + 4 * (size_t)s), s, sc.eqc, d_w, sc.evals + 4,
                            fin, with_rows ? 1u : 0u, ra);
         *next_rows1_done = with_rows;
     } else {
+        ProfScope ps(c, "gkr_end", 0.0);
         launch_eq_table(c, ar_ch + 4 * (size_t)s, s, sc.eqh, sc.eqc, d_w, sc.dot_partials, sc.evals + 4);
         hipLaunchKernelGGL(gkr_layer_finish_kernel, dim3(1), dim3(64), 0, c->stream, fin);
     }
@@ -690,9 +695,8 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
     // A lane of zkhip_gkr_prove_batch REPLAYS the proof's launch chain as a HIP graph (one hipGraphLaunch instead of 130-400 launches of
     // 3-5 us of host time each: with eight chains side by side the process's launch rate was the bound, tools/perf_gkr_batch.py).  A graph
     // holds addresses: the layer values are first copied to a buffer of the lane's own, so that every proof of the circuit on this lane is
-    // the same chain on the same memory.  (ZKHIP_GKR_GRAPH=0: plain launches.)
-    static const bool graph_env = [] { const char* e = std::getenv("ZKHIP_GKR_GRAPH"); return !e || std::atoi(e) != 0; }();
-    const bool lane = c->gkr_lane && graph_env && !c->profiling;
+    // the same chain on the same memory.  (A profiled context takes plain launches.)
+    const bool lane = c->gkr_lane && !c->profiling;
     std::vector<const uint64_t*> staged;
     if (lane) {
         size_t total = 0;
@@ -765,11 +769,7 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
     // The outer transcript on the device (default): every layer is enqueued behind the one before, alpha / beta / the claims travel
     // through device memory, the proof is read back ONCE.  ZKHIP_GKR_HOST_TRANSCRIPT=1 keeps the host transcript (one synchronisation
     // per layer; same proof, for A/B runs); the pipelined closing kernels are what feed the device transcript, so ZKHIP_PIPE=0 does too.
-    static const bool host_transcript = [] {
-        const char* e = std::getenv("ZKHIP_GKR_HOST_TRANSCRIPT");
-        const char* p = std::getenv("ZKHIP_PIPE");
-        return (e && std::atoi(e) != 0) || (p && std::atoi(p) == 0);
-    }();
+    static const bool host_transcript = zk::env::read(zk::env::GKR_HOST_TRANSCRIPT) != 0 || zk::env::read(zk::env::PIPE) == 0;
     if (!host_transcript) {
         const uint32_t stride = 2 * n_layers;
         // device block behind the layer scratch: outer state | next | sums (n_layers + 1) | w_b | w_c | arena
@@ -935,9 +935,8 @@ extern "C" int zkhip_gkr_prove_batch(zkhip_circuit* cir, uint32_t n_proofs, uint
         // what the priorities order is only who goes first.
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return ZKHIP_ERR_HIP;
-        static const bool spread = [] { const char* e = std::getenv("ZKHIP_GKR_LANE_PRIO"); return !e || std::atoi(e) != 0; }();
         const int span = least - greatest + 1;                    // (numerically lower = higher priority)
-        const int prio = spread && span > 1 ? greatest + (int)(c->gkr_lanes.size() % (size_t)span) : 0;
+        const int prio = span > 1 ? greatest + (int)(c->gkr_lanes.size() % (size_t)span) : 0;
         if (zk::ensure_stream(lc->owned_stream, &prio) != hipSuccess) return ZKHIP_ERR_HIP;
         lc->stream = lc->owned_stream.get();
         lc->gkr_lane = true;

@@ -18,6 +18,7 @@
 #include "mle_kernels.hpp"
 #include "msm_kernels.hpp"
 #include "srs_kernels.hpp"
+#include "tunables.hpp"
 
 using namespace zk;
 
@@ -28,7 +29,7 @@ using namespace zk;
 // and the bucket sets behind them.
 //   one problem:   uniform windows of c bits, c = 16 from 2^13 points on (one lane per bucket: the accumulate pass wants many short
 //                  lists, so the window is as wide as the sort allows as soon as the bucket reduction is not the larger cost; measured
-//                  with tools/perf_msm.py, ZKHIP_MSM_C sweep: below 2^13 every c ends at the ~1 ms latency floor of the reduction
+//                  with tools/perf_msm.py while the width was a run-time choice: below 2^13 every c ends at the ~1 ms latency floor of the reduction
 //                  passes).  16 x 16 = 256: the top window has 15 significant bits, half full, never sparse.
 //   shifted table: at 2^20 points thirteen digit windows of 20 / 19 bits on ONE bucket set of 2^19 buckets; widths by SRS size (msm_table_widths).
 //   several:       every problem gets a width of its OWN, log2(n_j) - delta bits (lists of 2^delta .. 2^(delta+1) points: the accumulate pass
@@ -644,10 +645,7 @@ static int msm_commit_small(zkhip_ctx* c, const uint32_t* d_table, size_t stride
     const MsmSmallProblem one = {n, stride, 0, 0, msm_table_widths(stride)};
     return msm_small_batch(c, d_table, d_inf, d_scalars, &one, 1, h_out_xy, h_out_inf);
 }
-static bool msm_small_on() {
-    static const bool on = [] { const char* e = std::getenv("ZKHIP_MSM_SMALL"); return !e || std::atoi(e) != 0; }();
-    return on;
-}
+static bool msm_small_on() { static const bool on = env::read(env::MSM_SMALL) != 0; return on; }
 
 extern "C" int zkhip_kzg_commit_table(zkhip_ctx* c, const void* d_table_with_header, const uint8_t* d_points_inf, size_t n_points,
                                       const uint64_t* d_scalars, size_t n_scalars, int require_equal_len, uint64_t* h_out_xy,
@@ -797,19 +795,11 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     // batches of one width each (14 / 12 / 10 bits) beside each other, fronts lined up: 6.7 ms -- their sparse top windows needed the
     // heavy-bucket passes (0.6 ms) and the three reductions ended 0.9 ms after the last accumulate pass.  ZKHIP_OPEN_PIPELINES=1 runs the
     // rounds above 2^14 as pipelines again for an A/B.)
-    const bool pipelines = [] { const char* e = std::getenv("ZKHIP_OPEN_PIPELINES"); return e && e[0] == '1'; }();
-    size_t OPEN_BATCH_MAX = pipelines ? (size_t)1 << 14 : OPEN_BATCH_MAX_DEFAULT;
-    if (const char* e = std::getenv("ZKHIP_OPEN_BATCH_LOG")) {   // tuning aid (tools/perf_open.py)
-        const int v = std::atoi(e);
-        if (v >= 8 && v <= 20) OPEN_BATCH_MAX = (size_t)1 << v;
-    }
-    if (OPEN_BATCH_MAX != OPEN_BATCH_MAX_DEFAULT) d_level_tables = nullptr;    // the tables are laid out for the default batch
+    static const bool pipelines = env::read(env::OPEN_PIPELINES) != 0;
+    const size_t OPEN_BATCH_MAX = pipelines ? (size_t)1 << 14 : OPEN_BATCH_MAX_DEFAULT;
+    if (pipelines) d_level_tables = nullptr;    // the tables are laid out for the default batch
     // result slot / stream of the single commits (they rotate over the slots); the batch has the last slot
-    int NSLOT = pipelines ? 5 : 2;
-    if (const char* e = std::getenv("ZKHIP_OPEN_SLOTS")) {   // tuning aid (tools/perf_open.py): fewer single commits beside each other
-        const int v = std::atoi(e);
-        if (v >= 1 && v <= NSLOT) NSLOT = v;
-    }
+    const int NSLOT = pipelines ? 5 : 2;
     const int sl_batch = zkhip_ctx::MSM_SLOTS - 1;
     const uint64_t* cur = d_evals;
     size_t cn = n, lvl_off = 0;
@@ -819,7 +809,7 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     struct Large { uint32_t round; size_t off, h; };
     std::vector<Large> large;
     // (a small opening against its tables -- the short path below -- takes all its rounds in ONE launch: a dozen 5 us launches otherwise)
-    const bool small_open = d_level_tables && n <= MSM_SMALL_MAX && OPEN_BATCH_MAX == OPEN_BATCH_MAX_DEFAULT && msm_small_on() && n_vars <= (uint32_t)ZK_MAX_ROUNDS;
+    const bool small_open = d_level_tables && n <= MSM_SMALL_MAX && !pipelines && msm_small_on() && n_vars <= (uint32_t)ZK_MAX_ROUNDS;
     if (small_open) {
         PtsArg zp = {};
         std::memcpy(zp.v, h_points, 32 * (size_t)n_vars);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "tunables.hpp"
 
 #ifdef __HIPCC__
 #define ZK_HD __host__ __device__ __forceinline__
@@ -112,13 +113,8 @@ inline MsmLevelWidths msm_level_table_widths(size_t nj, size_t batch_total) {
     // tuning aid: widest window log2(n_j) - delta.  Read ONCE per process: the layout of a table (W, hi, n_hi) is a function of the sizes
     // and of this value, and the table carries no header -- a value that changed between the build of a table and its use would
     // silently address it wrongly.  (Tables are not portable between processes that run with different values.)
-    static const int env_delta = [] {
-        const char* e = std::getenv("ZKHIP_LEVEL_TABLE_DELTA");
-        if (!e) return 99;
-        const int v = std::atoi(e);
-        return v >= -3 && v <= 4 ? v : 99;
-    }();
-    if (env_delta != 99) delta = env_delta;
+    static const long long env_delta = env::read(env::LEVEL_TABLE_DELTA);
+    if (env_delta != env::UNSET) delta = (int)env_delta;
     const uint32_t c = (uint32_t)std::min(20, std::max(8, lg - delta));
     MsmLevelWidths lw;
     lw.W = (256 + c - 1) / c;
@@ -136,11 +132,8 @@ inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_s
     // widths log2(n_j) - delta, delta = the smallest from 1 on whose partitions fit the sort (MultilinearKZG::open: 3-4 at 2^20, where the
     // pass is throughput bound and the width hardly matters -- 4.92 / 4.97 / 5.36 ms at delta 4 / 3 / 5 -- and 1 below 2^19, where the accumulate
     // pass is as long as its longest lists: 2^16 1.66 / 1.74 / 1.96 / 2.77 ms at delta 1 / 2 / 3 / 4)
-    int delta = 1;
-    if (const char* e = std::getenv("ZKHIP_MSM_BATCH_DELTA")) {   // tuning aid (tools/perf_open.py): width = log2(n_j) - delta
-        const int v = std::atoi(e);
-        if (v >= 0 && v <= 8) delta = v;
-    }
+    static const int first_delta = (int)env::read(env::MSM_BATCH_DELTA);   // tuning aid (tools/sweep_open.sh), read once: msm.hip keeps geometries by shape
+    int delta = first_delta;
     int rc = ZKHIP_ERR_SHAPE;
     // narrower windows until the sort's partitions suffice (at 8 bits -- the floor -- 64 problems have 2048)
     for (; delta <= 24 && rc == ZKHIP_ERR_SHAPE; ++delta) rc = msm_build_geometry_at(pr, shared, table_stride, delta, g);
@@ -210,11 +203,7 @@ inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t tabl
         } else {
             uint32_t w, hi, n_hi;
             if (pr.n == 1) {
-                uint32_t c = lg >= 13 ? 16 : lg >= 10 ? 12 : 8;
-                if (const char* e = std::getenv("ZKHIP_MSM_C")) {   // tuning aid (tools/perf_msm.py); any 4 <= c <= 16 is correct
-                    const int v = std::atoi(e);
-                    if (v >= 4 && v <= 16) c = (uint32_t)v;
-                }
+                const uint32_t c = lg >= 13 ? 16 : lg >= 10 ? 12 : 8;     // (any 4 <= c <= 16 is correct)
                 w = (256 + c - 1) / c; hi = c; n_hi = w;
             } else {
                 const uint32_t c = (uint32_t)std::min(16, std::max(8, (int)lg - delta));   // >= 8 bits: at most 32 windows per problem, 2048 for 64 problems

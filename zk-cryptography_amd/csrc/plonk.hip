@@ -17,6 +17,7 @@
 #include "host_g1.hpp"
 #include "host_util.hpp"
 #include "plonk_kernels.hpp"
+#include "tunables.hpp"
 
 using namespace zk;
 
@@ -122,16 +123,10 @@ enum { C_BETA, C_GAMMA, C_ALPHA, C_ZETA, C_NU, C_MU, N_CHALLENGES };
 // Coset evaluations of the eight preprocessed columns, of L_1 and of X: ten vectors of D elements.  They are kept with the key up to
 // this budget -- at n = 2^20 (D = 2^22) they take 1.25 GiB, less than the 1.6 GiB shifted-SRS table the commits of that size already
 // hold -- and recomputed per proof (ten transforms) above it.
-constexpr size_t PLONK_CACHE_BUDGET = (size_t)2 << 30;
+static_assert(zk::env::PLONK_CACHE_BUDGET.def == 2LL << 30, "the budget the lines above speak of");
 // diagnostic aid (tests/test_gpu_plonk.py): ZKHIP_PLONK_CACHE_BUDGET=<bytes> replaces the budget, 0 makes every key an uncached one.
 // Read at each key's creation, not once per process: a key keeps the choice it was made with.
-size_t plonk_cache_budget() {
-    const char* e = std::getenv("ZKHIP_PLONK_CACHE_BUDGET");
-    if (!e || !*e) return PLONK_CACHE_BUDGET;
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(e, &end, 10);
-    return end && *end == '\0' ? (size_t)v : PLONK_CACHE_BUDGET;
-}
+size_t plonk_cache_budget() { return (size_t)zk::env::read(zk::env::PLONK_CACHE_BUDGET); }
 constexpr int N_PRE = 10;
 const uint64_t COSET_SHIFT = 7;          // arkworks' multiplicative generator of Fr; the quotient does not depend on the choice
 

@@ -15,6 +15,7 @@
 #include "ctx.hpp"
 #include "host_util.hpp"
 #include "shard.hpp"
+#include "tunables.hpp"
 
 // ---------------------------------------------------------------------------------------
 // RCCL, resolved at run time: libzkhip.so does not link it (a host that brings its own transport never loads it)
@@ -34,7 +35,7 @@ constexpr int RCCL_UINT8 = 1;                          // ncclUint8
 Rccl& rccl() {
     static Rccl r = [] {
         Rccl q;
-        const char* env = std::getenv("ZKHIP_RCCL_LIB");
+        const char* env = zk::env::text(zk::env::RCCL_LIB);
         // a process that already holds an RCCL (PyTorch ships one) gets that one back by its soname
         const char* names[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
         for (const char* n : names) {

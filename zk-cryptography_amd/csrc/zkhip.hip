@@ -18,6 +18,7 @@
 #include "sumcheck_kernels.hpp"
 #include "multifold_kernels.hpp"
 #include "mfma_fold.hpp"
+#include "tunables.hpp"
 
 using namespace zk;
 
@@ -180,10 +181,8 @@ static int launch_fold(zkhip_ctx* c, const uint64_t* d_in, size_t n, const uint6
     else {
         // at most THREE workgroups per CU (a 40 KiB LDS request the kernel never touches; section 7 of profiles/r06/NOTES.md found the sums pass
         // no slower with a quarter of the loads in flight): 0.1427 -> 0.1372 ms at 2^24, 0.70 -> 0.73 of HBM; two per CU 0.161, four 0.137, no cap 0.143.
-        // ZKHIP_FOLD_LDS=<bytes> overrides (diagnostics; 0 = no cap).
-        static const long fold_lds = [] { const char* e = getenv("ZKHIP_FOLD_LDS"); return e ? std::min(std::max(atol(e), 0L), 158L * 1024) : 40960L; }();
-        if (fold_lds > 64 * 1024) ZK_TRY(c->allow_big_lds((const void*)fold_kernel<false>, 158 * 1024));
-        hipLaunchKernelGGL(fold_kernel<false>, dim3(grid), dim3(MLE_BLOCK), (size_t)fold_lds, c->stream, d_in, d_out, n_out, log_half,
+        constexpr size_t FOLD_LDS = 40960;
+        hipLaunchKernelGGL(fold_kernel<false>, dim3(grid), dim3(MLE_BLOCK), FOLD_LDS, c->stream, d_in, d_out, n_out, log_half,
                            d_r, rv, d_partials);
     }
     if (np) *np = (uint32_t)grid;
@@ -213,12 +212,12 @@ static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cu
     // the term order (tile T starts at term r * T mod 2^k; the default 1 -- 3 and 5 measured the same, 0 = every wave at term 0: 108 vs 112 us
     // before the aligned planes); ZKHIP_MF_OCC=n caps the workgroups per CU through the LDS request (all 1024 workgroups are resident at once as it is, 4 per CU; capped at 2 per CU
     // or with 36-78 KiB requested per workgroup the pass takes the same 83-85 us, alone and beside the proofs in flight: round 6)
-    static const int mf_cfg = [] { const char* e = getenv("ZKHIP_MF"); return e ? atoi(e) : 1; }();
+    static const int mf_cfg = (int)zk::env::read(zk::env::MF);
     if (m >= 8192 && k >= 4 && mf_cfg != 0) {   // streaming shape, limb products on the matrix cores (mfma_fold.hpp)
         out_per_wg = 64;
         ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
-        const unsigned tiles = (unsigned)(m / 64), rot = (unsigned)(mf_cfg % 10);
-        static const int mf_occ = [] { const char* e = getenv("ZKHIP_MF_OCC"); return e ? atoi(e) : 0; }();
+        const unsigned tiles = (unsigned)(m / 64), rot = (unsigned)mf_cfg;
+        static const int mf_occ = (int)zk::env::read(zk::env::MF_OCC);
         size_t q_bytes = mfm_lds_bytes(std::min<uint32_t>(1u << k, (uint32_t)MFM_CHUNK));
         if (mf_occ > 0) q_bytes = std::max(q_bytes, (size_t)(((158 * 1024 / mf_occ) - 1024) & ~255));
         if (q_bytes > 64 * 1024) ZK_TRY(c->allow_big_lds((const void*)multifold_mfma_kernel<4, 4>, 158 * 1024));   // (the kernel has ~0.6 KiB of static LDS on top)
@@ -229,6 +228,7 @@ static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cu
         // 6-variable fold of the overlapped plan 12 % slower than the 8-variable one
         const uint32_t waves = k >= 8 ? 4 : k == 7 ? 2 : 1;
         ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
+        ProfScope form(c, "multifold_valu", 0.0, stream);   // (a second record of the same launch: which form it was)
         hipLaunchKernelGGL((multifold_kernel<64, 4, true>), dim3((unsigned)(m / 64)), dim3(64 * waves), ((size_t)32 << k) + 32 * (size_t)(waves - 1) * 64,
                            stream, cur, m, k, d_w, dst, pdst);
     } else {                  // few outputs left: 16 per workgroup, up to 64 lanes share one output
@@ -328,10 +328,8 @@ extern "C" int zkhip_mle_evaluation(zkhip_ctx* c, const uint64_t* d_evals, size_
     if (n_pts != log2_exact(n)) return ZKHIP_ERR_SHAPE;                // assert_eq! evaluation_form.rs:163-167
     ZK_TRY(c->activate());
     uint64_t* d_res = c->small_u64(ZK_SMALL_RES);
-    // ZKHIP_EVAL_ONE_PASS=0 (diagnostics): the chain of k-variable folds that partial_evaluations takes
-    static const bool one_pass = [] { const char* e = getenv("ZKHIP_EVAL_ONE_PASS"); return !e || atoi(e) != 0; }();
     const uint32_t log_n = log2_exact(n);
-    if (one_pass && log_n >= 17) {
+    if (log_n >= 17) {
         // Every point is known before the first launch, so the evaluation is ONE pass over the table: with k1 leading variables per
         // output, p(r) = sum_j eq_j(r[k1..]) * (sum_b eq_b(r[..k1]) * T[b * m + j]) -- the k1-variable fold on the matrix cores
         // whose tiles weight their 64 outputs with the eq table of the remaining points and keep only that sum (32 n bytes read,
@@ -536,8 +534,7 @@ static inline uint32_t stage_k(size_t cur_n) {
 // kernel takes (10), so that the fold starts as early as possible: 2^24 = 6 rounds | fold (100 us) next to 10 rounds | 8
 // rounds.  Same values as the round-by-round loop, bit for bit.
 static inline uint32_t overlapped_min_log() {       // (ZKHIP_OVERLAP_MIN_LOG: tuning aid, read once)
-    static const uint32_t v = [] { const char* e = std::getenv("ZKHIP_OVERLAP_MIN_LOG"); const int x = e ? std::atoi(e) : 0; return x >= 19 && x <= 25 ? (uint32_t)x : 24u; }();
-    return v;
+    static const uint32_t v = (uint32_t)zk::env::read(zk::env::OVERLAP_MIN_LOG); return v;
 }
 static inline bool overlapped_plan(size_t n) { return is_pow2(n) && n >= ((size_t)1 << overlapped_min_log()) && n <= ((size_t)1 << 24); }
 // A rank's SHARD takes the overlapped stage over the whole range it was built for: there it is also the form with the fewest exchanges
@@ -604,8 +601,7 @@ static int launch_fine_sums(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uin
         // 123 us), and every other kernel's loads queue behind them: the first rounds and small folds of the proofs in flight beside
         // it took 50-150 us instead of 10-40, 0.212 against 0.201 ms per proof (profiles/r06/NOTES.md section 7).
         // ZKHIP_FINE_LDS=<bytes> overrides (diagnostics; 0 = no cap).
-        static const long fine_lds = [] { const char* e = getenv("ZKHIP_FINE_LDS"); return e ? atol(e) : 79872L; }();
-        const size_t lds = (size_t)std::min<long>(std::max<long>(fine_lds, 0), 158 * 1024);
+        static const size_t lds = (size_t)zk::env::read(zk::env::FINE_LDS);
         if (lds > 64 * 1024) ZK_TRY(c->allow_big_lds((const void*)fine_sums_kernel, 158 * 1024));
         hipLaunchKernelGGL(fine_sums_kernel, dim3((unsigned)((n_chunks + 7) / 8)), dim3(MLE_BLOCK), lds, stream, d_evals, n_chunks, first);
     }
