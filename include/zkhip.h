@@ -658,7 +658,9 @@ int zkhip_domain_params(uint64_t size, uint64_t *h_generator, uint64_t *h_genera
 int zkhip_ntt(zkhip_ctx *ctx, uint64_t *d_data, uint32_t log_n, int inverse);
 /* Domain::fft / ifft as the reference calls them (domain.rs:108-118: clone the input, resize it to the domain size with
  * zeros, transform): d_src holds n_src <= 2^log_n values and is not modified, d_dst receives the 2^log_n results.  The zero
- * padding happens inside the first pass (no staging copy). */
+ * padding happens inside the first pass (no staging copy).
+ * Aliasing, the same at every size: d_dst == d_src transforms in place and requires n_src == 2^log_n; d_dst == d_src with a shorter
+ * input returns ZKHIP_ERR_ARG and touches nothing.  Buffers that overlap in any other way are not supported. */
 int zkhip_domain_transform(zkhip_ctx *ctx, const uint64_t *d_src, size_t n_src, uint64_t *d_dst, uint32_t log_n, int inverse);
 int zkhip_pointwise_mul(zkhip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out);
 /* UnivariateEval::multiply (evaluation.rs:59-86): d_out[na + nb - 1] = coefficients of a * b via three transforms. */

@@ -153,3 +153,48 @@ int ora_dense_divide(fr_t *q, size_t *nq, fr_t *r, size_t *nr, const fr_t *a, si
     *nr = lr;
     return 0;
 }
+
+/* ---- test-only array helpers for a closed form of the transform (tests/ntt_model.py, tests/test_gpu_ntt.py) ------------
+ * For x[j] = a^j, j < n, and w an n-th root of unity:  sum_j (a w^i)^j = (a^n - 1) / (a w^i - 1).  Indices are handled in
+ * chunks that each start from one ora_fr_pow_u64, so the chunks are independent. */
+#define ORA_GEO_CHUNK ((size_t)4096)
+
+/* out[j] = a^j, j < n */
+void ora_fr_powers(fr_t *out, const fr_t *a, size_t n) {
+    const long chunks = (long)((n + ORA_GEO_CHUNK - 1) / ORA_GEO_CHUNK);
+#pragma omp parallel for schedule(static)
+    for (long c = 0; c < chunks; ++c) {
+        size_t lo = (size_t)c * ORA_GEO_CHUNK, hi = lo + ORA_GEO_CHUNK < n ? lo + ORA_GEO_CHUNK : n;
+        fr_t p;
+        ora_fr_pow_u64(&p, a, (uint64_t)lo);
+        for (size_t j = lo; j < hi; ++j) { out[j] = p; ora_fr_mul(&p, &p, a); }
+    }
+}
+
+/* The number of i < n with  scale * out[i] * (a w^i - 1) != a^n - 1;  *first_bad (nullable) receives the smallest such i, or n.
+ * Forward transform of the powers of a: w = omega, scale = 1; inverse: w = omega^-1, scale = n. */
+size_t ora_ntt_geometric_mismatches(const fr_t *out, size_t n, const fr_t *a, const fr_t *w, const fr_t *scale, size_t *first_bad) {
+    fr_t one, rhs;
+    ora_fr_one(&one);
+    ora_fr_pow_u64(&rhs, a, (uint64_t)n);
+    ora_fr_sub(&rhs, &rhs, &one);
+    const long chunks = (long)((n + ORA_GEO_CHUNK - 1) / ORA_GEO_CHUNK);
+    size_t bad = 0, first = n;
+#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(min : first)
+    for (long c = 0; c < chunks; ++c) {
+        size_t lo = (size_t)c * ORA_GEO_CHUNK, hi = lo + ORA_GEO_CHUNK < n ? lo + ORA_GEO_CHUNK : n;
+        fr_t aw;
+        ora_fr_pow_u64(&aw, w, (uint64_t)lo);
+        ora_fr_mul(&aw, &aw, a);                                  /* a w^lo */
+        for (size_t i = lo; i < hi; ++i) {
+            fr_t d, lhs;
+            ora_fr_sub(&d, &aw, &one);
+            ora_fr_mul(&lhs, &out[i], &d);
+            ora_fr_mul(&lhs, &lhs, scale);
+            if (!ora_fr_eq(&lhs, &rhs)) { ++bad; if (i < first) first = i; }
+            ora_fr_mul(&aw, &aw, w);
+        }
+    }
+    if (first_bad) *first_bad = first;
+    return bad;
+}

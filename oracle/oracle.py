@@ -41,6 +41,7 @@ def lib():
         _lib = C.CDLL(_LIB)
         _lib.ora_sparse_to_bytes.restype = C.c_size_t
         _lib.ora_dense_mul.restype = C.c_size_t
+        _lib.ora_ntt_geometric_mismatches.restype = C.c_size_t
     return _lib
 
 
@@ -652,6 +653,29 @@ def univariate_multiply(a, b):
     o = np.empty((a.shape[0] + b.shape[0] - 1, 4), dtype=np.uint64)
     assert lib().ora_univariate_multiply(_p(o), _p(a), C.c_size_t(a.shape[0]), _p(b), C.c_size_t(b.shape[0])) == 0
     return o
+
+
+def fr_powers(a, n):
+    """[a^0, a^1, .., a^(n-1)] for one Montgomery element a"""
+    a = _fr(a).reshape(4)
+    o = np.empty((n, 4), dtype=np.uint64)
+    lib().ora_fr_powers(_p(o), _p(a), C.c_size_t(n))
+    return o
+
+
+def ntt_geometric_mismatches(out, a, inverse):
+    """(count, first index) of the outputs that are not the size-len(out) transform of the powers of a, by the closed form
+    scale * out[i] * (a w^i - 1) == a^n - 1 on every index (w = omega, scale = 1; inverse: omega^-1 and n).  first index = n when the
+    count is 0.  a^n == 1 would make the identity hold for any out[i] at a w^i == 1: the caller picks a with a^n != 1."""
+    out, a = _fr(out).reshape(-1, 4), _fr(a).reshape(4)
+    n = out.shape[0]
+    w = fr_get_root_of_unity(n)
+    scale = fr_from_ints([n if inverse else 1])[0]
+    if inverse:
+        w = fr_inv(w)
+    first = C.c_size_t(0)
+    bad = lib().ora_ntt_geometric_mismatches(_p(out), C.c_size_t(n), _p(a), _p(w), _p(scale), C.byref(first))
+    return int(bad), int(first.value)
 
 
 def dense_mul(a, b):

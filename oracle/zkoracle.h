@@ -184,6 +184,10 @@ int  ora_domain_fft(fr_t *out, const fr_t *coeffs, size_t n_coeffs, size_t domai
 int  ora_domain_ifft(fr_t *out, const fr_t *evals, size_t n_evals, size_t domain_size);
 /* UnivariateEval::multiply: out has na+nb-1 coefficients */
 int  ora_univariate_multiply(fr_t *out, const fr_t *a, size_t na, const fr_t *b, size_t nb);
+/* test-only: out[j] = a^j; and the count of i < n with scale * out[i] * (a w^i - 1) != a^n - 1, the closed form of the transform of
+ * the powers of a (forward: w = omega, scale = 1; inverse: w = omega^-1, scale = n).  *first_bad (nullable): smallest such i, or n */
+void ora_fr_powers(fr_t *out, const fr_t *a, size_t n);
+size_t ora_ntt_geometric_mismatches(const fr_t *out, size_t n, const fr_t *a, const fr_t *w, const fr_t *scale, size_t *first_bad);
 /* DenseUnivariatePolynomial Mul (schoolbook, dense_univariate.rs:210-233) ; returns out length */
 size_t ora_dense_mul(fr_t *out, const fr_t *a, size_t na, const fr_t *b, size_t nb);
 void ora_dense_evaluate(fr_t *o, const fr_t *coeffs, size_t n, const fr_t *x);

@@ -65,6 +65,47 @@ def test_arith_driver_builds_and_links():
     assert L.arith_driver_mfma_fold_wsum(bogus, 256, 4, bogus, bogus, 0, bogus, bogus, 9, None) != 0
 
 
+def test_ntt_driver_builds_and_links():
+    """tests/cpp/ntt_driver.hip (the launchers of tests/test_gpu_ntt_kernels.py): compiled for gfx950, loadable, every launcher exported,
+    and every launcher turns away on the host whatever would index out of bounds or shift by a negative amount (no GPU is touched on
+    that path)"""
+    import sys
+    sys.path.insert(0, HERE)
+    import ntt_driver as DRV
+    assert os.path.exists(DRV.build())
+    L = DRV.lib()
+    for name in DRV.LAUNCHERS:
+        assert hasattr(L, "ntt_driver_" + name), name
+    assert L.ntt_driver_tile_log() == 11 and L.ntt_driver_first_pass_stages() == 8
+    p = 4096                                           # never dereferenced: every call below is refused before any launch
+    # null pointers
+    assert L.ntt_driver_twiddle(None, 3, p, None) != 0 and L.ntt_driver_twiddle(p, 3, None, None) != 0
+    assert L.ntt_driver_first_table(None, 12, p, None) != 0 and L.ntt_driver_first_table(p, 12, None, None) != 0
+    assert L.ntt_driver_pass_table(None, 12, 8, 4, p, 0, p, None) != 0 and L.ntt_driver_pass_table(p, 12, 8, 4, p, 0, None, None) != 0
+    assert L.ntt_driver_pass_table(p, 12, 8, 4, None, 1, p, None) != 0
+    assert L.ntt_driver_first8(None, 1, None, p, 12, p, None) != 0 and L.ntt_driver_first8(p, 1, None, None, 12, p, None) != 0
+    assert L.ntt_driver_first8(p, 1, None, p, 12, None, None) != 0
+    assert L.ntt_driver_pass(None, p, 12, 8, 4, p, p, 0, 1, None) != 0 and L.ntt_driver_pass(p, None, 12, 8, 4, p, p, 0, 1, None) != 0
+    assert L.ntt_driver_pass(p, p, 12, 8, 4, None, p, 0, 1, None) != 0 and L.ntt_driver_pass(p, p, 12, 8, 4, p, None, 1, 1, None) != 0
+    assert L.ntt_driver_first_stages(None, p, 3, p, None) != 0 and L.ntt_driver_first_stages(p, None, 3, p, None) != 0
+    assert L.ntt_driver_first_stages(p, 2 * p, 3, None, None) != 0 and L.ntt_driver_first_stages(p, p, 3, p, None) != 0
+    assert L.ntt_driver_mid_stages(None, 11, 10, 1, p, None) != 0 and L.ntt_driver_mid_stages(p, 11, 10, 1, None, None) != 0
+    # sizes: log_n < 11 on the >= 2^12-point kernels, and sizes beyond what the driver serves
+    assert L.ntt_driver_first8(p, 1, None, p, 10, p, None) != 0 and L.ntt_driver_first8(p, 1, None, p, 27, p, None) != 0
+    assert L.ntt_driver_pass(p, p, 10, 8, 2, p, p, 0, 1, None) != 0 and L.ntt_driver_pass_table(p, 10, 8, 2, p, 0, p, None) != 0
+    assert L.ntt_driver_first_table(p, 7, p, None) != 0 and L.ntt_driver_twiddle(p, 26, p, None) != 0
+    assert L.ntt_driver_first_stages(p, 2 * p, 27, p, None) != 0 and L.ntt_driver_mid_stages(p, 9, 8, 1, p, None) != 0
+    # T outside 1..7, s0 < 11 - T, s0 + T > log_n
+    for s0, T in ((8, 0), (8, 8), (3, 7), (9, 1), (7, 3), (8, 5), (12, 1), (0xFFFFFFFF, 7), (0xFFFFFFFE, 7)):
+        assert L.ntt_driver_pass(p, p, 12, s0, T, p, p, 0, 1, None) != 0, (s0, T)
+        assert L.ntt_driver_pass_table(p, 12, s0, T, p, 0, p, None) != 0, (s0, T)
+    # n_src > n, n_dst > n
+    assert L.ntt_driver_first8(p, 4097, None, p, 12, p, None) != 0 and L.ntt_driver_pass(p, p, 12, 8, 4, p, p, 0, 4097, None) != 0
+    # mid_stages: T outside 1..6, s0 < 10 - T, s0 + T > log_n
+    for s0, T in ((10, 0), (4, 7), (10, 7), (8, 1), (3, 6), (10, 2), (11, 1), (0xFFFFFFFF, 6)):
+        assert L.ntt_driver_mid_stages(p, 11, s0, T, p, None) != 0, (s0, T)
+
+
 def test_fqu_consts_regenerate_identically():
     """tools/gen_fqu_consts.py asserts what fqu_sub's callers need of the redundant K p constants (every limb but the top >= 2^29 - 2)
     and still prints csrc/fqu_consts.hpp byte for byte"""

@@ -199,20 +199,22 @@ extern "C" int zkhip_ntt(zkhip_ctx* c, uint64_t* d_data, uint32_t log_n, int inv
 }
 
 // Domain::fft / ifft as the reference calls them (domain.rs:108-118: clone, resize to the domain size with zeros, transform):
-// d_src holds n_src <= 2^log_n values, d_dst receives the 2^log_n results; d_src is not modified (d_dst == d_src is allowed
-// when n_src == 2^log_n).
+// d_src holds n_src <= 2^log_n values, d_dst receives the 2^log_n results; d_src is not modified.  The one aliasing rule, at every
+// size: d_dst == d_src transforms in place and needs n_src == 2^log_n, anything shorter is ZKHIP_ERR_ARG (a buffer of n_src < n elements
+// cannot take n results); buffers that overlap in any other way are not supported.
 extern "C" int zkhip_domain_transform(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, uint64_t* d_dst, uint32_t log_n, int inverse) {
     if (!c || !d_dst || (n_src && !d_src)) return ZKHIP_ERR_ARG;
     if (log_n > 30) return ZKHIP_ERR_SHAPE;
     const size_t n = (size_t)1 << log_n;
     if (n_src > n) return ZKHIP_ERR_SHAPE;
+    if (d_dst == d_src && n_src != n) return ZKHIP_ERR_ARG;
     ZK_TRY(c->activate());
     ZK_TRY(c->reserve_ws(n * 32));
     if (log_n >= 12) return ntt_big(c, d_src, n_src, nullptr, d_dst, n, log_n, inverse, (uint64_t*)c->ws.ptr);
     if (d_dst != d_src) {
         if (n_src < n) ZK_HIP(c, hipMemsetAsync(d_dst + 4 * n_src, 0, (n - n_src) * 32, c->stream));
         if (n_src) ZK_HIP(c, hipMemcpyAsync(d_dst, d_src, n_src * 32, hipMemcpyDeviceToDevice, c->stream));
-    } else if (n_src != n) return ZKHIP_ERR_ARG;
+    }
     return ntt_inplace(c, d_dst, log_n, inverse, (uint64_t*)c->ws.ptr);
 }
 

@@ -9,7 +9,7 @@
 // Passes over HBM (n x 32 bytes read + written each):
 //   1. bit-reversal gather fused with the first NTT_TILE_LOG stages: a tile of 2^NTT_TILE_LOG consecutive
 //      outputs of those stages depends only on the same consecutive (bit-reversed) inputs, so they run in LDS;
-//   2. one pass per remaining stage (butterflies at distance >= the tile).
+//   2. passes of several stages each over the remaining ones (butterflies at distance >= the tile).
 // Twiddles come from a table W[i] = w^i, i < n/2, built once per (size, direction) and kept in HBM.
 #pragma once
 #include "mle_kernels.hpp"
@@ -59,23 +59,6 @@ static __global__ __launch_bounds__(MLE_BLOCK) void ntt_first_stages_kernel(cons
         __syncthreads();
     }
     for (uint32_t q = threadIdx.x; q < tile; q += MLE_BLOCK) store_fr(out, base + q, tab[q]);
-}
-
-// one in-place stage with butterfly distance m = 2^s (s >= NTT_TILE_LOG)
-static __global__ __launch_bounds__(MLE_BLOCK) void ntt_stage_kernel(uint64_t* __restrict__ data, uint32_t log_n, uint32_t s,
-                                                              const uint64_t* __restrict__ tw) {
-    const size_t half = (size_t)1 << (log_n - 1);
-    const size_t m = (size_t)1 << s;
-    const size_t tw_stride = (size_t)1 << (log_n - s - 1);
-    const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t b = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; b < half; b += stride) {
-        const size_t j = b & (m - 1);
-        const size_t i0 = ((b >> s) << (s + 1)) | j;
-        Fr t = load_fr(data, i0 + m) * load_fr(tw, j * tw_stride);
-        Fr u = load_fr(data, i0);
-        store_fr(data, i0 + m, u - t);
-        store_fr(data, i0, u + t);
-    }
 }
 
 // T consecutive stages s0 .. s0+T-1 (butterfly distances 2^s0 ..) in one pass.  Index i = hi | mid | lo with `mid` the T
@@ -227,22 +210,23 @@ static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_pass_kernel(const ui
         const uint32_t mid = q >> cols_log, c = q & (cols - 1);
         tab[q] = load_fr(src, base + ((size_t)mid << s0) + c);
     }
-    // this lane's two butterflies per stage: b = threadIdx.x and threadIdx.x + 512 -> (c, q = b >> cols_log)
-    const uint32_t c = threadIdx.x & (cols - 1);
+    // this lane's two butterflies per stage: b = threadIdx.x and threadIdx.x + 512 -> (c = b & (cols - 1), q = b >> cols_log).
+    // The two share their column except at T = 1, where a row of 1024 columns is wider than the workgroup.
+    const uint32_t c0 = threadIdx.x & (cols - 1), c1 = (threadIdx.x + NTT_BIG_BLOCK) & (cols - 1);
     const uint32_t q0 = threadIdx.x >> cols_log, q1 = (threadIdx.x + NTT_BIG_BLOCK) >> cols_log;
-    auto tw_index = [&](uint32_t t, uint32_t q) -> size_t {
+    auto tw_index = [&](uint32_t t, uint32_t q, uint32_t c) -> size_t {
         const uint32_t ml = q & ((1u << t) - 1);
         return ((((size_t)1 << t) - 1) << s0) + ((size_t)ml << s0) + lo0 + c;
     };
-    Fr w0 = load_fr(tw, tw_index(0, q0)), w1 = load_fr(tw, tw_index(0, q1));
+    Fr w0 = load_fr(tw, tw_index(0, q0, c0)), w1 = load_fr(tw, tw_index(0, q1, c1));
     __syncthreads();
     for (uint32_t t = 0; t < T; ++t) {
         const Fr wa = w0, wb = w1;
-        if (t + 1 < T) { w0 = load_fr(tw, tw_index(t + 1, q0)); w1 = load_fr(tw, tw_index(t + 1, q1)); }
+        if (t + 1 < T) { w0 = load_fr(tw, tw_index(t + 1, q0, c0)); w1 = load_fr(tw, tw_index(t + 1, q1, c1)); }
         const bool last = LAST_SCALED && t + 1 == T;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const uint32_t q = h ? q1 : q0;
+            const uint32_t q = h ? q1 : q0, c = h ? c1 : c0;
             const uint32_t mid0 = ((q >> t) << (t + 1)) | (q & ((1u << t) - 1));
             const uint32_t i0 = (mid0 << cols_log) | c, i1 = i0 + (cols << t);
             const Fr tt = tab[i1] * (h ? wb : wa);
