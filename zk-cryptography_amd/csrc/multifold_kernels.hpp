@@ -565,35 +565,77 @@ static __global__ __launch_bounds__(MLE_BLOCK) void slice_sums_kernel(const uint
 // ---- k-variable fold of a SMALL table (<= 2^18 entries), spread over the chip -----------------------------------------
 // partial[y*m + c] = sum over the term range y of w[b] * in[b*m + c], as CANONICAL integers (the serial kernel's form; the
 // conversion is linear, so partial tables still add up).  multifold_kernel<16> gives such a table to m/16 workgroups (16 at
-// m = 256: ~16 us of one-wave-per-SIMD latency); here a workgroup of 1024 lanes takes OW outputs x (1024/OW) term slices
-// of <= 4 terms each, sums the slices in LDS, and the term ranges go to blockIdx.y: 2^18 entries are 64 workgroups of
-// 4 products per lane.  The serial kernel adds the gridDim.y (<= 8) partial tables (SmallArgs::stride).
-constexpr int BF_BLOCK = 1024;
-static __global__ __launch_bounds__(BF_BLOCK) void blockfold_kernel(const uint64_t* __restrict__ in, uint32_t m, uint32_t log_ow,
+// m = 256: ~16 us of one-wave-per-SIMD latency).  Here a workgroup is 256 lanes, ONE wave per SIMD: the products are
+// chains of multiply-adds with 64-way instruction parallelism, so a wave alone on its SIMD issues back to back, and the
+// grid is sized to reach all 256 CUs (with 1024 lanes -- four waves per SIMD -- on 32 or 64 CUs its instruction count alone
+// accounts for the 11-14 us it took; the count and what is measured: profiles/blockfold/NOTES.md).  A workgroup takes 8 consecutive outputs x up to
+// 32 term slices of <= 4 terms each; a wave is 8 outputs x 8 slices, summed by three shuffle levels, and the four waves
+// combine through LDS behind ONE barrier.  The term ranges go to blockIdx.y; the serial kernel adds the gridDim.y (<= 8)
+// partial tables (SmallArgs::stride).
+constexpr int BF_BLOCK = 256;
+constexpr int BF_LOG_OW = 3;                               // outputs per workgroup: 8 (one 256-byte run per slice and term)
+constexpr int BF_SLICES = BF_BLOCK >> BF_LOG_OW;           // term slices per workgroup: 32
+constexpr int BF_MAX_PER = 4;                              // terms per lane: WideAcc's capacity as pinned in tests/test_gpu_arith.py
+constexpr int BF_MAX_NY = 8;                               // partial tables: the serial kernel's strided prologue keeps 8 loads in flight
+constexpr int BF_TARGET_WGS = 256;                         // workgroups to aim for when the terms allow it: one per CU
+
+// The grid and the split of the 2^k terms for a fold to m outputs: m / 8 workgroups x ny term ranges; in a range, `sl` (<= 32)
+// slices of `per` (<= 4) consecutive terms, so sl * per * ny = 2^k.  ny is what fills the chip (BF_TARGET_WGS) or what
+// per <= 4 forces, whichever is larger, and at most 8: ny * m <= 2048 for m <= 1024, the room of the prover's first partial
+// tables.  A table too small for that leaves slices idle (sl < 32) rather than CUs.  The one rule for the library, the
+// sharded stage's buffer sizes and the test driver.
+struct BlockfoldShape { uint32_t log_ow, sl, per, ny; };
+__host__ __device__ constexpr bool blockfold_shape(uint32_t m, uint32_t k, BlockfoldShape* sh) {
+    if (m == 0 || (m & (m - 1)) != 0 || (m >> BF_LOG_OW) == 0) return false;       // a power of two, at least one workgroup's outputs
+    if (k == 0 || k > 10) return false;                                              // 2^10 terms = 32 slices x 4 terms x 8 ranges
+    const uint32_t terms = 1u << k, wgx = m >> BF_LOG_OW;
+    const uint32_t fill = wgx >= (uint32_t)BF_TARGET_WGS ? 1u : (uint32_t)BF_TARGET_WGS / wgx;
+    const uint32_t forced = (terms + BF_SLICES * BF_MAX_PER - 1) / (BF_SLICES * BF_MAX_PER);
+    uint32_t ny = fill > forced ? fill : forced;
+    if (ny > (uint32_t)BF_MAX_NY) ny = BF_MAX_NY;
+    if (ny > terms) ny = terms;
+    const uint32_t range = terms / ny;                                               // terms of one workgroup
+    sh->log_ow = BF_LOG_OW;
+    sh->sl = range < (uint32_t)BF_SLICES ? range : (uint32_t)BF_SLICES;
+    sh->per = range / sh->sl;
+    sh->ny = ny;
+    return true;
+}
+
+// grid (m >> BF_LOG_OW, ny), BF_BLOCK lanes; sl, per, ny from blockfold_shape
+static __global__ __launch_bounds__(BF_BLOCK) void blockfold_kernel(const uint64_t* __restrict__ in, uint32_t m, uint32_t sl_cnt,
                                                                     uint32_t per, const uint64_t* __restrict__ weights,
                                                                     uint64_t* __restrict__ partial) {
-    __shared__ Fr part[BF_BLOCK];
-    const uint32_t ow = 1u << log_ow, sl_cnt = BF_BLOCK >> log_ow;
-    const uint32_t o = threadIdx.x & (ow - 1), sl = threadIdx.x >> log_ow;
-    const uint32_t c = blockIdx.x * ow + o;
+    constexpr uint32_t OW = 1u << BF_LOG_OW, WAVES = BF_BLOCK / 64;
+    __shared__ Fr part[(WAVES - 1) * OW];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t o = lane & (OW - 1), sl = wave * (64 / OW) + (lane >> BF_LOG_OW);
+    const uint32_t c = blockIdx.x * OW + o;
     const uint32_t b0 = (blockIdx.y * sl_cnt + sl) * per;
-    WideAcc acc;
-    acc.clear();
-    for (uint32_t u = 0; u < per; u += 2) {
-        Fr v0 = load_fr(in, (size_t)(b0 + u) * m + c), w0 = load_fr(weights, b0 + u);
-        Fr v1 = v0, w1 = w0;
-        const bool two = u + 1 < per;
-        if (two) { v1 = load_fr(in, (size_t)(b0 + u + 1) * m + c); w1 = load_fr(weights, b0 + u + 1); }
-        acc.mac(w0, v0);
-        if (two) acc.mac(w1, v1);
+    Fr r = Fr::zero();
+    if (sl < sl_cnt) {                                   // a whole number of waves idles, except where sl_cnt < 8
+        Fr v[BF_MAX_PER], w[BF_MAX_PER];                 // every load in flight before the first product
+#pragma unroll
+        for (int u = 0; u < BF_MAX_PER; ++u) {
+            if ((uint32_t)u < per) { v[u] = load_fr(in, (size_t)(b0 + u) * m + c); w[u] = load_fr(weights, b0 + u); }
+        }
+        WideAcc acc;
+        acc.clear();
+#pragma unroll
+        for (int u = 0; u < BF_MAX_PER; ++u) {
+            if ((uint32_t)u < per) acc.mac(w[u], v[u]);
+        }
+        r = wide_reduce(acc.lo, acc.hi);
     }
-    part[threadIdx.x] = wide_reduce(acc.lo, acc.hi);
+#pragma unroll
+    for (int d = 32; d >= (int)OW; d >>= 1) r = r + shfl_down_fr(r, d);      // lanes < 8: the wave's eight slices added up
+    if (wave != 0 && lane < OW) part[(wave - 1) * OW + lane] = r;
     __syncthreads();
-    for (uint32_t half = sl_cnt >> 1; half >= 1; half >>= 1) {       // tree over the slices
-        if (sl < half) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + (half << log_ow)];
-        __syncthreads();
+    if (wave == 0 && lane < OW) {
+#pragma unroll
+        for (uint32_t w2 = 1; w2 < WAVES; ++w2) r = r + part[(w2 - 1) * OW + lane];
+        store_fr(partial, (size_t)blockIdx.y * m + c, fr_from_mont_outlined(r));
     }
-    if (sl == 0) store_fr(partial, (size_t)blockIdx.y * m + c, fr_from_mont_outlined(part[o]));
 }
 
 }  // namespace zk

@@ -561,28 +561,28 @@ static int launch_small(zkhip_ctx* c, const SmallArgs& a, SumcheckDev* st, uint6
     return ZKHIP_OK;
 }
 
-// k-variable fold of a small table spread over the chip: partial tables P[y][m], y < *n_slices (blockfold_kernel)
-struct BlockfoldShape { uint32_t log_ow, per, ny; };
-// OW outputs x (1024 / OW) term slices per workgroup; at least one term per slice; ny partial tables come out
-static inline bool blockfold_shape(uint32_t m, uint32_t k, BlockfoldShape* sh) {
-    const uint32_t log_m = log2_exact(m);
-    sh->log_ow = std::max<uint32_t>(std::min<uint32_t>(log_m, 5), k < 10 ? 10 - k : 0);
-    if (sh->log_ow > log_m) return false;
-    const uint32_t sl_cnt = (uint32_t)BF_BLOCK >> sh->log_ow;
-    const uint32_t terms = 1u << k;
-    sh->per = std::min<uint32_t>(4, terms / sl_cnt);
-    sh->ny = terms / (sh->per * sl_cnt);
+// the first fold of the overlapped plan (k <= 6 variables, 2^19 .. 2^24 entries) leaves its partial tables in 2 x 1024 entries (d_p1
+// below, the sharded stage's d_mid), the second one (m = 256, k <= 10) in 32 x 256
+constexpr bool blockfold_fits(uint32_t m, uint32_t k_max, uint32_t room) {
+    for (uint32_t k = 1; k <= k_max; ++k) {
+        BlockfoldShape sh = {};
+        if (!blockfold_shape(m, k, &sh) || sh.ny * m > room || sh.sl * sh.per * sh.ny != (1u << k)) return false;
+    }
     return true;
 }
+static_assert(blockfold_fits(256, 6, 2048) && blockfold_fits(512, 6, 2048) && blockfold_fits(1024, 6, 2048) && blockfold_fits(256, 10, 32 * 256),
+              "blockfold_shape: more partial tables than the prover's buffers hold");
+// k-variable fold of a small table spread over the chip: partial tables P[y][m], y < *n_slices (blockfold_kernel; its grid and
+// the split of the terms come from blockfold_shape, multifold_kernels.hpp)
 static int launch_blockfold(zkhip_ctx* c, hipStream_t stream, const uint64_t* in, uint32_t m, uint32_t k, const uint64_t* d_w,
                             uint64_t* d_partial, uint32_t* n_slices) {
     BlockfoldShape sh;
     if (!blockfold_shape(m, k, &sh)) return ZKHIP_ERR_SHAPE;
-    const uint32_t log_ow = sh.log_ow, per = sh.per, ny = sh.ny, terms = 1u << k;
+    const uint32_t terms = 1u << k;
     ProfScope ps(c, "blockfold", 32.0 * (double)m * terms, stream);
-    hipLaunchKernelGGL(blockfold_kernel, dim3(m >> log_ow, ny), dim3(BF_BLOCK), 0, stream, in, m, log_ow, per, d_w, d_partial);
+    hipLaunchKernelGGL(blockfold_kernel, dim3(m >> sh.log_ow, sh.ny), dim3(BF_BLOCK), 0, stream, in, m, sh.sl, sh.per, d_w, d_partial);
     ZK_HIP(c, hipGetLastError());
-    *n_slices = ny;
+    *n_slices = sh.ny;
     return ZKHIP_OK;
 }
 // fine block sums: d_fine[2^lb] = sums of the 2^lb equal consecutive blocks of the table (each >= FINE_CHUNK entries);
