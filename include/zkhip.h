@@ -590,6 +590,18 @@ int zkhip_kzg_open_tables(zkhip_ctx *ctx, const uint64_t *d_evals, size_t n, con
                           const uint64_t *d_points_xy, const uint8_t *d_points_inf, size_t n_points,
                           const uint64_t *d_folded_xy, const uint8_t *d_folded_inf, const void *d_level_tables,
                           uint64_t *h_evaluation, uint64_t *h_proofs_xy, uint8_t *h_proofs_inf);
+/* `batch` openings against ONE SRS in one call: opening b is the table h_eval_ptrs[b] (a HOST array of `batch` device pointers to n
+ * entries each; a pointer may repeat: one polynomial at several points) at the points h_points[b][n_vars][4].  The SRS arguments and
+ * the shape and argument checks are those of zkhip_kzg_open_tables, applied once, with its status codes; a refused call launches
+ * nothing and leaves the outputs untouched; batch == 0 returns ZKHIP_OK and touches nothing.  Outputs (host): h_evaluations[batch][4],
+ * h_proofs_xy[batch][n_vars][12], h_proofs_inf[batch][n_vars] -- opening b bit for bit what zkhip_kzg_open_tables returns for
+ * (h_eval_ptrs[b], h_points + 4 n_vars b).  With level tables and n <= 2^12 (the short path of zkhip_kzg_open_tables) the whole batch is
+ * three launches, one copy and one synchronisation per chunk of 64 openings; every other size and configuration runs the openings one
+ * after another. */
+int zkhip_kzg_open_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_eval_ptrs, size_t n, const uint64_t *h_points,
+                         size_t n_eval_points, const uint64_t *d_points_xy, const uint8_t *d_points_inf, size_t n_points,
+                         const uint64_t *d_folded_xy, const uint8_t *d_folded_inf, const void *d_level_tables,
+                         uint64_t *h_evaluations, uint64_t *h_proofs_xy, uint8_t *h_proofs_inf);
 /* UnivariateKZGInterface::open (kzg/src/univariate_kzg.rs:60-81): evaluation = poly(z) (dense_univariate.rs:184-196),
  * proof = commitment to the quotient of (poly - z) / (x - z) (divide_with_q_and_r, dense_univariate.rs:88-124) against
  * the first n_coeffs - 1 SRS points.  Evaluation and quotient come from one Horner suffix scan on the device.

@@ -250,6 +250,39 @@ static __global__ __launch_bounds__(MLE_BLOCK) void open_steps_small_kernel(cons
         cn = h;
     }
 }
+// The same for a BATCH of small openings (zkhip_kzg_open_batch): workgroup b walks the rounds of opening b -- its table in[b] (tables may
+// repeat: they are only read), its points pts[b * n_rounds ..] from device memory (1.5 KB per opening does not fit the kernel arguments
+// B times), its own quotients [b * q_stride ..] in level order and its own ping / pong scratch.  The last round (one pair, thread 0)
+// also leaves its remainder -- the evaluation -- in evals[b], so that it travels with the commit's terms in one copy.
+static __global__ __launch_bounds__(MLE_BLOCK) void open_steps_small_batch_kernel(const uint64_t* const* __restrict__ in, uint32_t n,
+                                                                           const uint64_t* __restrict__ pts, uint32_t n_rounds,
+                                                                           uint64_t* __restrict__ quotients, size_t q_stride, uint64_t* ping,
+                                                                           size_t ping_stride, uint64_t* pong, size_t pong_stride,
+                                                                           uint64_t* __restrict__ evals) {
+    const uint32_t b = blockIdx.x;
+    const uint64_t* cur = in[b];
+    quotients += 4 * (size_t)b * q_stride;
+    ping += 4 * (size_t)b * ping_stride;
+    pong += 4 * (size_t)b * pong_stride;
+    uint32_t cn = n, off = 0;
+    for (uint32_t i = 0; i < n_rounds; ++i) {
+        const Fr z = load_fr(pts, (size_t)b * n_rounds + i);
+        uint64_t* rem = (i & 1) ? pong : ping;
+        const uint32_t h = cn >> 1;
+        for (uint32_t j = threadIdx.x; j < h; j += MLE_BLOCK) {
+            const Fr lo = load_fr(cur, j), hi = load_fr(cur, (size_t)j + h);
+            const Fr d = hi - lo;
+            const Fr r = lo + z * d;
+            store_fr(quotients, (size_t)off + j, d);
+            store_fr(rem, j, r);
+            if (i + 1 == n_rounds) store_fr(evals, b, r);
+        }
+        __syncthreads();
+        off += h;
+        cur = rem;
+        cn = h;
+    }
+}
 
 // ---- Horner suffix scan: UnivariateKZG::open ---------------------------------------------------------------
 // V_i = sum_{j >= i} c_j z^(j-i)  (V_i = c_i + z V_{i+1}, V_n = 0).  V_0 = p(z) is DenseUnivariatePolynomial::evaluate

@@ -749,11 +749,11 @@ extern "C" int zkhip_kzg_open(zkhip_ctx* c, const uint64_t* d_evals, size_t n, c
     return zkhip_kzg_open_tables(c, d_evals, n, h_points, n_eval_points, d_points_xy, d_points_inf, n_points, d_folded_xy, d_folded_inf, nullptr,
                                  h_evaluation, h_proofs_xy, h_proofs_inf);
 }
-extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uint64_t* h_points, size_t n_eval_points,
-                                     const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points,
-                                     const uint64_t* d_folded_xy, const uint8_t* d_folded_inf, const void* d_level_tables_with_header,
-                                     uint64_t* h_evaluation, uint64_t* h_proofs_xy, uint8_t* h_proofs_inf) {
-    if (!c || !d_evals || !h_points || !d_points_xy || !h_evaluation || !h_proofs_xy || !h_proofs_inf) return ZKHIP_ERR_ARG;
+static bool open_pipelines_on() { static const bool on = env::read(env::OPEN_PIPELINES) != 0; return on; }
+// the shape and argument checks of an opening, shared by zkhip_kzg_open_tables and zkhip_kzg_open_batch (applied once per call, before
+// anything is launched); *d_level_tables <- the tables behind their checked header, or nullptr
+static int kzg_open_check(zkhip_ctx* c, size_t n, size_t n_eval_points, size_t n_points, const uint64_t* d_folded_xy, const uint8_t* d_folded_inf,
+                          const void* d_level_tables_with_header, uint32_t* n_vars_out, const void** d_level_tables) {
     if (d_level_tables_with_header && !d_folded_inf) return ZKHIP_ERR_ARG;      // the tables belong to cached folded levels
     if (!is_pow2(n)) return ZKHIP_ERR_SHAPE;
     const uint32_t n_vars = log2_exact(n);
@@ -763,12 +763,19 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     if (n >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;
     if ((d_folded_xy == nullptr) != (d_folded_inf == nullptr)) return ZKHIP_ERR_ARG;
     ZK_TRY(c->activate());
-    const void* d_level_tables = nullptr;
+    *d_level_tables = nullptr;
     if (d_level_tables_with_header) {
         int trc = ZKHIP_OK;
-        d_level_tables = table_check(c, d_level_tables_with_header, ZK_TABLE_LEVELS, n_points, &trc);   // the level tables of an SRS of THIS size, with the widths used below?
-        if (!d_level_tables) return trc;
+        *d_level_tables = table_check(c, d_level_tables_with_header, ZK_TABLE_LEVELS, n_points, &trc);   // the level tables of an SRS of THIS size, with the widths used below?
+        if (!*d_level_tables) return trc;
     }
+    *n_vars_out = n_vars;
+    return ZKHIP_OK;
+}
+// one opening behind kzg_open_check (d_level_tables: behind the header)
+static int kzg_open_one(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t n_vars, const uint64_t* h_points,
+                        const uint64_t* d_points_xy, const uint8_t* d_points_inf, const uint64_t* d_folded_xy, const uint8_t* d_folded_inf,
+                        const void* d_level_tables, uint64_t* h_evaluation, uint64_t* h_proofs_xy, uint8_t* h_proofs_inf) {
     // aux layout: quotients of all rounds (n - 1, laid out like the folded SRS) | remainder ping (n/2) | pong (n/4) |
     // [folded SRS xy, inf]
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -795,7 +802,7 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     // batches of one width each (14 / 12 / 10 bits) beside each other, fronts lined up: 6.7 ms -- their sparse top windows needed the
     // heavy-bucket passes (0.6 ms) and the three reductions ended 0.9 ms after the last accumulate pass.  ZKHIP_OPEN_PIPELINES=1 runs the
     // rounds above 2^14 as pipelines again for an A/B.)
-    static const bool pipelines = env::read(env::OPEN_PIPELINES) != 0;
+    const bool pipelines = open_pipelines_on();
     const size_t OPEN_BATCH_MAX = pipelines ? (size_t)1 << 14 : OPEN_BATCH_MAX_DEFAULT;
     if (pipelines) d_level_tables = nullptr;    // the tables are laid out for the default batch
     // result slot / stream of the single commits (they rotate over the slots); the batch has the last slot
@@ -934,6 +941,159 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
     ZK_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(h_evaluation, c->pinned_u64(ZK_PIN_RES), 32);
     return ZKHIP_OK;
+}
+
+extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uint64_t* h_points, size_t n_eval_points,
+                                     const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points,
+                                     const uint64_t* d_folded_xy, const uint8_t* d_folded_inf, const void* d_level_tables_with_header,
+                                     uint64_t* h_evaluation, uint64_t* h_proofs_xy, uint8_t* h_proofs_inf) {
+    if (!c || !d_evals || !h_points || !d_points_xy || !h_evaluation || !h_proofs_xy || !h_proofs_inf) return ZKHIP_ERR_ARG;
+    uint32_t n_vars = 0;
+    const void* d_level_tables = nullptr;
+    ZK_TRY(kzg_open_check(c, n, n_eval_points, n_points, d_folded_xy, d_folded_inf, d_level_tables_with_header, &n_vars, &d_level_tables));
+    return kzg_open_one(c, d_evals, n, n_vars, h_points, d_points_xy, d_points_inf, d_folded_xy, d_folded_inf, d_level_tables, h_evaluation,
+                        h_proofs_xy, h_proofs_inf);
+}
+
+// ---------------------------------------------------------------------------------------
+// MultilinearKZG::open of a BATCH of (polynomial, point) pairs against one SRS
+// ---------------------------------------------------------------------------------------
+// A small opening (the short path above) is latency: one single-workgroup quotient launch and two launches of a few dozen waves, a copy,
+// a synchronisation and a serial host fold, on an empty chip.  Round i of EVERY opening of one SRS commits against the same level table
+// with the same widths, so B openings are n_vars table regions read by B scalar vectors each: three launches (quotients, plane sums,
+// reduction) with the batch index as a grid dimension, one copy of the terms and the B evaluations, one synchronisation, and the host
+// fold of B n_vars problems on the context's host threads.  The group elements are those of the single call, so are the affine proofs.
+// A batch is cut into chunks of at most OPEN_BATCH_CHUNK openings: at 2^12 entries a chunk holds 14 MiB of quotients and remainders
+// (224 KiB each), <= 3 MiB of terms in device and pinned memory (n_vars x <= 14 planes x 192 B each) and its partial sums -- the buffers
+// stay of the size a few dozen single openings' worth, whatever B a caller passes; 64 openings are >= 512 (opening, round) problems
+// of <= 14 planes each, several waves for every SIMD of the chip, so a larger chunk has nothing left to fill.
+constexpr uint32_t OPEN_BATCH_CHUNK = 64;
+constexpr size_t OPEN_BATCH_LANE_PAIRS = 32;      // most (point, window) pairs a lane of the batched plane sums walks
+static int kzg_open_small_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, uint32_t n_vars, const uint64_t* h_points,
+                                const uint8_t* d_folded_inf, const uint32_t* d_level_tables, uint64_t* h_evaluations, uint64_t* h_proofs_xy,
+                                uint8_t* h_proofs_inf, uint32_t chunk_max) {
+    if (n_vars > (uint32_t)MSM_SMALL_PROBS || chunk_max == 0) return ZKHIP_ERR_SHAPE;
+    const uint32_t bc_max = std::min(batch, chunk_max);
+    // the rounds' geometry, once for the whole batch: round j commits n >> (j + 1) quotients against level j as zkhip_srs_level_tables laid it out
+    MsmSmallArgs a = {};
+    a.table = d_level_tables; a.inf = d_folded_inf; a.nprob = n_vars;
+    size_t entry = 0, lvl_off = 0, total_pairs = 0;
+    for (uint32_t j = 0; j < n_vars; ++j) {
+        const size_t h = n >> (j + 1);
+        const MsmLevelWidths lw = msm_level_table_widths(h, n - 1);
+        a.n[j] = (uint32_t)h; a.stride[j] = (uint32_t)h; a.W[j] = lw.W; a.hi[j] = lw.hi; a.n_hi[j] = lw.n_hi;
+        a.tab_off[j] = (uint32_t)entry; a.sc_off[j] = (uint32_t)lvl_off;
+        a.planes = std::max(a.planes, lw.hi);
+        total_pairs += h * lw.W;
+        entry += (size_t)lw.W * h;
+        lvl_off += h;
+    }
+    // the slots: msm_small_batch's ~2 waves per SIMD in all, dealt over the WHOLE chunk -- an opening's share of them goes to its rounds by
+    // their pairs, at least one slot per (opening, round).  One opening: the single call's split.  From a dozen openings on the minimum
+    // alone is more than the budget: one wave per (opening, round, plane), and the chip is full of them.
+    // But no lane walks more than OPEN_BATCH_LANE_PAIRS pairs: a full chip is as fast as its longest wave lets it be, and with one slot per
+    // round the first round of a 2^12 opening is ONE wave of 608 pairs per lane beside waves of a handful -- measured at B = 64: 32 ms in
+    // this launch, no faster per opening than the loop, against 0.31 ms per opening at B = 16, whose share still split the round five ways
+    // (profiles/open_batch/NOTES.md).  The single call's own split is 8-17 pairs per lane: the cap changes nothing for B <= 2.
+    const size_t budget = std::max<size_t>(1, 2048 / a.planes / bc_max);
+    for (uint32_t j = 0; j < n_vars; ++j) {
+        const size_t pairs = (size_t)a.n[j] * a.W[j], chunks = (pairs + 63) / 64;
+        const size_t share = (budget * pairs + total_pairs - 1) / total_pairs, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
+        a.slot_first[j + 1] = a.slot_first[j] + (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(share, capped)));
+    }
+    a.total_slots = a.slot_first[n_vars];
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // staging (pinned -> aux): the chunk's table pointers, then its points
+    const size_t o_pts = al((size_t)bc_max * 8), stage_bytes = o_pts + al((size_t)bc_max * n_vars * 32);
+    const size_t q_stride = n, ping_stride = n / 2, pong_stride = n / 4;             // scalars per opening
+    const size_t o_q = stage_bytes, o_ping = o_q + al(bc_max * q_stride * 32), o_pong = o_ping + al(bc_max * ping_stride * 32);
+    ZK_TRY(c->reserve_aux(o_pong + al(bc_max * pong_stride * 32)));
+    const size_t part_bytes = al((size_t)bc_max * a.planes * a.total_slots * 256);
+    const size_t terms_bytes = (size_t)bc_max * n_vars * a.planes * 192, out_bytes = al(terms_bytes + (size_t)bc_max * 32);    // terms | evaluations: ONE copy
+    ZK_TRY(c->reserve_ws(part_bytes + out_bytes));
+    ZK_TRY(c->reserve_msm_pin(0, out_bytes + stage_bytes));
+    char* aux = (char*)c->aux.ptr;
+    char* pin = (char*)c->msm_pin[0].ptr;
+    a.partials = (uint32_t*)c->ws.ptr;
+    a.terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
+    a.scalars = (const uint64_t*)(aux + o_q);
+    ZkHostPool* pool = c->pool();
+    for (uint32_t b0 = 0; b0 < batch; b0 += bc_max) {
+        const uint32_t bc = std::min(bc_max, batch - b0);
+        uint64_t* d_evals_out = a.terms + 24 * (size_t)bc * n_vars * a.planes;
+        const size_t copy_bytes = (size_t)bc * n_vars * a.planes * 192 + (size_t)bc * 32;
+        // (the previous chunk's upload has ended: every chunk ends in a synchronisation)
+        std::memcpy(pin + out_bytes, h_eval_ptrs + b0, (size_t)bc * 8);
+        std::memcpy(pin + out_bytes + o_pts, h_points + 4 * (size_t)n_vars * b0, (size_t)bc * n_vars * 32);
+        ZK_HIP(c, hipMemcpyAsync(aux, pin + out_bytes, o_pts + (size_t)bc * n_vars * 32, hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, "open_batch_steps", 96.0 * (double)n * bc);
+            hipLaunchKernelGGL(open_steps_small_batch_kernel, dim3(bc), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t* const*)aux, (uint32_t)n,
+                               (const uint64_t*)(aux + o_pts), n_vars, (uint64_t*)(aux + o_q), q_stride, (uint64_t*)(aux + o_ping), ping_stride,
+                               (uint64_t*)(aux + o_pong), pong_stride, d_evals_out);
+        }
+        {
+            ProfScope ps(c, "open_batch_planes", 128.0 * (double)total_pairs * bc);
+            hipLaunchKernelGGL(msm_small_batch_planes_kernel, dim3(a.total_slots, a.planes, bc), dim3(64), 0, c->stream, a, q_stride);
+        }
+        {
+            ProfScope ps(c, "open_batch_reduce", 0.0);
+            hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(a.planes, n_vars, bc), dim3(64), 0, c->stream, a);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(pin, a.terms, copy_bytes, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        // the single call's host fold per (opening, round): the weighted sum of its plane sums, <= 20 doublings.  (With the profile on,
+        // events on the now idle stream bracket it: their distance is the host time.)
+        ProfScope ps(c, "open_batch_fold", 0.0);
+        auto finish = [&](uint32_t k) {
+            const uint32_t j = k % n_vars;
+            std::vector<zkhost::Xyzz> pts(a.hi[j]);
+            std::vector<uint32_t> exps(a.hi[j]);
+            for (uint32_t t = 0; t < a.hi[j]; ++t) {
+                std::memcpy(&pts[t], pin + 192 * ((size_t)k * a.planes + t), 192);
+                exps[t] = t;
+            }
+            const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
+            const size_t o = (size_t)b0 * n_vars + k;
+            h_proofs_inf[o] = zkhost::xyzz_to_affine(res, h_proofs_xy + 12 * o) ? 0 : 1;
+        };
+        if (!pool) {
+            for (uint32_t k = 0; k < bc * n_vars; ++k) finish(k);
+        } else {
+            pool->run(bc * n_vars, [&](unsigned k) { finish(k); });
+        }
+        std::memcpy(h_evaluations + 4 * (size_t)b0, pin + (size_t)bc * n_vars * a.planes * 192, (size_t)bc * 32);
+    }
+    return ZKHIP_OK;
+}
+static int kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, const uint64_t* h_points, size_t n_eval_points,
+                          const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_folded_xy,
+                          const uint8_t* d_folded_inf, const void* d_level_tables_with_header, uint64_t* h_evaluations, uint64_t* h_proofs_xy,
+                          uint8_t* h_proofs_inf, uint32_t chunk_max) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!h_eval_ptrs || !h_points || !d_points_xy || !h_evaluations || !h_proofs_xy || !h_proofs_inf) return ZKHIP_ERR_ARG;
+    for (uint32_t b = 0; b < batch; ++b) if (!h_eval_ptrs[b]) return ZKHIP_ERR_ARG;
+    uint32_t n_vars = 0;
+    const void* d_level_tables = nullptr;
+    ZK_TRY(kzg_open_check(c, n, n_eval_points, n_points, d_folded_xy, d_folded_inf, d_level_tables_with_header, &n_vars, &d_level_tables));
+    if (d_level_tables && n <= MSM_SMALL_MAX && !open_pipelines_on() && msm_small_on())
+        return kzg_open_small_batch(c, batch, h_eval_ptrs, n, n_vars, h_points, d_folded_inf, (const uint32_t*)d_level_tables, h_evaluations,
+                                    h_proofs_xy, h_proofs_inf, chunk_max);
+    // every other size and configuration: one after another through the single opening (several openings in ONE bucket-pipeline commit
+    // would need a point base per problem in msm_enqueue's sort keys: not built)
+    for (uint32_t b = 0; b < batch; ++b)
+        ZK_TRY(kzg_open_one(c, h_eval_ptrs[b], n, n_vars, h_points + 4 * (size_t)n_vars * b, d_points_xy, d_points_inf, d_folded_xy, d_folded_inf,
+                            d_level_tables, h_evaluations + 4 * (size_t)b, h_proofs_xy + 12 * (size_t)n_vars * b, h_proofs_inf + (size_t)n_vars * b));
+    return ZKHIP_OK;
+}
+extern "C" int zkhip_kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, const uint64_t* h_points,
+                                    size_t n_eval_points, const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points,
+                                    const uint64_t* d_folded_xy, const uint8_t* d_folded_inf, const void* d_level_tables_with_header,
+                                    uint64_t* h_evaluations, uint64_t* h_proofs_xy, uint8_t* h_proofs_inf) {
+    return kzg_open_batch(c, batch, h_eval_ptrs, n, h_points, n_eval_points, d_points_xy, d_points_inf, n_points, d_folded_xy, d_folded_inf,
+                          d_level_tables_with_header, h_evaluations, h_proofs_xy, h_proofs_inf, OPEN_BATCH_CHUNK);
 }
 
 // ---------------------------------------------------------------------------------------

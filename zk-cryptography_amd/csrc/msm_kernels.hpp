@@ -653,7 +653,9 @@ struct MsmSmallArgs {
     uint32_t n[MSM_SMALL_PROBS], stride[MSM_SMALL_PROBS], W[MSM_SMALL_PROBS], hi[MSM_SMALL_PROBS], n_hi[MSM_SMALL_PROBS];
     uint32_t tab_off[MSM_SMALL_PROBS], sc_off[MSM_SMALL_PROBS], slot_first[MSM_SMALL_PROBS + 1];
 };
-static __global__ __launch_bounds__(64) void msm_small_planes_kernel(MsmSmallArgs a) {
+// (the bodies are shared with the batched launches below: opening b of a batch reads its scalars from scalar index sc_base on and
+// owns the partials [b][plane][slot] and the terms [b][j][plane]; a lone launch is b = 0, sc_base = 0)
+__device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uint32_t b, size_t sc_base) {
     const uint32_t slot = blockIdx.x, plane = blockIdx.y, lane = threadIdx.x;
     uint32_t j = 0;
     while (j + 1 < a.nprob && slot >= a.slot_first[j + 1]) ++j;
@@ -664,33 +666,42 @@ static __global__ __launch_bounds__(64) void msm_small_planes_kernel(MsmSmallArg
     for (uint32_t p = s * 64 + lane; p < pairs; p += lanes_total) {
         const uint32_t w = p / n, i = p - w * n;
         if (a.inf && a.inf[a.sc_off[j] + i]) continue;
-        DigitStream ds(load_fr(a.scalars, (size_t)a.sc_off[j] + i).from_mont());
+        DigitStream ds(load_fr(a.scalars, sc_base + a.sc_off[j] + i).from_mont());
         int32_t d = 0;
         for (uint32_t v = 0; v <= w; ++v) d = ds.next(v < n_hi ? hi : hi - 1);
         const uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
         if ((mag >> plane) & 1u) g1u_madd(acc, load_affine_u(a.table, (size_t)a.tab_off[j] + (size_t)w * a.stride[j] + i), d < 0);
     }
     msm_wave_tree_sum(acc, 64);
-    if (lane == 0) store_xyzz_u(a.partials, (size_t)plane * a.total_slots + slot, acc);
+    if (lane == 0) store_xyzz_u(a.partials, ((size_t)b * a.planes + plane) * a.total_slots + slot, acc);
 }
-static __global__ __launch_bounds__(64) void msm_small_reduce_kernel(MsmSmallArgs a) {
+__device__ __forceinline__ void msm_small_reduce_body(const MsmSmallArgs& a, uint32_t b) {
     const uint32_t plane = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
     if (plane >= a.hi[j]) return;
     const uint32_t s0 = a.slot_first[j], ns = a.slot_first[j + 1] - s0;
     G1XyzzU acc = G1XyzzU::identity();
     for (uint32_t s = lane; s < ns; s += 64) {
-        const G1XyzzU v = load_xyzz_u(a.partials, (size_t)plane * a.total_slots + s0 + s);
+        const G1XyzzU v = load_xyzz_u(a.partials, ((size_t)b * a.planes + plane) * a.total_slots + s0 + s);
         g1u_add(acc, v);
     }
     msm_wave_tree_sum(acc, 64);
     if (lane == 0) {
-        uint64_t* o = a.terms + 24 * ((size_t)j * a.planes + plane);
+        uint64_t* o = a.terms + 24 * (((size_t)b * a.nprob + j) * a.planes + plane);
         store_fq(o, fqu_to_ark(acc.x));
         store_fq(o + 6, fqu_to_ark(acc.y));
         store_fq(o + 12, fqu_to_ark(acc.zz));
         store_fq(o + 18, fqu_to_ark(acc.zzz));
     }
 }
+static __global__ __launch_bounds__(64) void msm_small_planes_kernel(MsmSmallArgs a) { msm_small_planes_body(a, 0, 0); }
+static __global__ __launch_bounds__(64) void msm_small_reduce_kernel(MsmSmallArgs a) { msm_small_reduce_body(a, 0); }
+// B openings of ONE SRS (zkhip_kzg_open_batch): round j of every opening commits against the same level table with the same widths,
+// so the per-round arrays above describe all of them; only the scalars (opening b's quotients lie q_stride scalars behind opening
+// b - 1's) and the outputs gain the batch index, a grid dimension: (slot, plane, b) and (plane, round, b).
+static __global__ __launch_bounds__(64) void msm_small_batch_planes_kernel(MsmSmallArgs a, size_t q_stride) {
+    msm_small_planes_body(a, blockIdx.z, (size_t)blockIdx.z * q_stride);
+}
+static __global__ __launch_bounds__(64) void msm_small_batch_reduce_kernel(MsmSmallArgs a) { msm_small_reduce_body(a, blockIdx.z); }
 
 // ---- shifted-SRS table (zkhip_srs_precompute) -------------------------------------------------------------
 static __global__ __launch_bounds__(MSM_BLOCK) void msm_clear_inf_kernel(const uint8_t* __restrict__ inf, size_t n, uint32_t* __restrict__ table) {

@@ -498,4 +498,5 @@ class SuccintGKRProtocol:
         b_clone = np.concatenate([ch[:half], zeros])
         c_clone = np.concatenate([ch[half:], np.zeros((poly.n_vars - (len(ch) - half), 4), dtype=np.uint64)])
         commitment = MultilinearKZG.commitment(poly, tau)
-        return commitment, SuccintGKRProof(base, MultilinearKZG.open(poly, b_clone, tau), MultilinearKZG.open(poly, c_clone, tau))
+        open_b, open_c = MultilinearKZG.open_batch([poly, poly], [b_clone, c_clone], tau)      # one polynomial at two points: one batch
+        return commitment, SuccintGKRProof(base, open_b, open_c)

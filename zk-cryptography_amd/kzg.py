@@ -483,6 +483,54 @@ class MultilinearKZG:
         N.check(st, "open: points / SRS length must match the polynomial (and n_vars >= 2)")
         return MultilinearKZGProof(ev, [G1Affine(pxy[i], pinf[i]) for i in range(nv)])
 
+    @staticmethod
+    def open_batch(polys, evaluation_points, srs, cache_folded_srs=True):
+        """`open` of polys[b] at evaluation_points[b] for every b against one SRS in one call (zkhip_kzg_open_batch) -> a list of
+        MultilinearKZGProof, each bit for bit what `open` returns.  The polynomials have one length; the same object may appear several
+        times (one polynomial at several points).  With at most 2^12 entries the whole batch shares three launches."""
+        b = len(polys)
+        if len(evaluation_points) != b:
+            raise AssertionError("open_batch: one point vector per polynomial")
+        if b == 0:
+            return []
+        for p in polys:
+            assert isinstance(p, Multilinear)
+        n = len(polys[0])
+        pts = [_fr_host(v) for v in evaluation_points]
+        nv = pts[0].shape[0]
+        for i in range(b):
+            if len(polys[i]) != n:
+                raise AssertionError("open_batch: the polynomials must have one length")
+            if pts[i].shape[0] != nv:
+                raise AssertionError("open_batch: the point vectors must have one length")
+        device = polys[0].evaluations.device
+        for p in polys:
+            if p.evaluations.device != device:
+                raise ValueError("open_batch: the polynomials must live on one device")
+        z = np.ascontiguousarray(np.stack(pts).reshape(b * nv, 4)) if nv else np.zeros((1, 4), dtype=np.uint64)
+        ev = np.empty((b, 4), dtype=np.uint64)
+        pxy = np.zeros((b * max(nv, 1), 12), dtype=np.uint64)
+        pinf = np.zeros(b * max(nv, 1), dtype=np.uint8)
+        ctx = N.Context.get(device.index)
+        tables = None
+        if cache_folded_srs and len(srs) == n and n >= 4 and n & (n - 1) == 0:      # as `open`
+            fxy, finf = srs.folded()
+            fxy_p, finf_p = N.ptr(fxy), N.ptr(finf)
+            tables = getattr(srs, "_level_tables", None)
+            if tables is None and n <= TrustedSetup.SMALL_SRS:
+                tables = srs.precompute_open()._level_tables
+        else:
+            fxy_p = finf_p = None
+        for p in polys:
+            assert p.evaluations.is_contiguous()
+        ptrs = (C.c_void_p * b)(*[p.evaluations.data_ptr() for p in polys])
+        vp = C.c_void_p
+        st = N.lib().zkhip_kzg_open_batch(ctx.handle, C.c_uint32(b), ptrs, C.c_size_t(n), z.ctypes.data_as(vp), C.c_size_t(nv),
+                                          N.ptr(srs.powers_of_tau_in_g1), N.ptr(srs.inf), C.c_size_t(len(srs)), fxy_p, finf_p,
+                                          N.ptr(tables) if tables is not None else None, ev.ctypes.data_as(vp), pxy.ctypes.data_as(vp),
+                                          pinf.ctypes.data_as(vp))
+        N.check(st, "open_batch: points / SRS length must match the polynomials (and n_vars >= 2)")
+        return [MultilinearKZGProof(ev[i].copy(), [G1Affine(pxy[i * nv + k], pinf[i * nv + k]) for k in range(nv)]) for i in range(b)]
 
     @staticmethod
     def verify(commit, verifier_points, proof, srs):
