@@ -242,3 +242,104 @@ def test_poly_sum_with_the_total_deferred(zk, ora, log_n):
     proof3, ch3 = sc3.prove()
     assert zk.Fr.to_ints(proof3.sum) == [5] and not np.array_equal(ch3, wch)
     assert np.array_equal(proof3.univariate_poly[0], wrp[0])
+
+
+# ---- the host's enqueue order ---------------------------------------------------------------------------------------------------
+# The library's profile (zkhip_profile_enable) records one name per launch scope in the order the HOST enqueues them, whatever stream they
+# go to: the schedule of the prover, which no proof's bits show.  Recorded at the commit before the schedule's host code was split into
+# setup / overlapped plan / stage plan; a change of these lists is a change of schedule and wants its own measurements.
+_STAGE = ["sumcheck_small", "multifold_small"]
+_OVERLAPPED_FIRST_HALF = ["fine_sums", "coarse_sums", "sumcheck_small", "blockfold"]
+_OVERLAPPED_PROOF = _OVERLAPPED_FIRST_HALF + ["multifold", "multifold_valu", "sumcheck_small", "blockfold", "sumcheck_small"]
+_OVERLAPPED_SECOND_HALF = ["multifold", "multifold_valu", "blockfold", "sumcheck_small"]       # held back: the second serial launch went out before it
+ENQUEUE_ORDER = {
+    10: ["sumcheck_small"],                                                               # the serial kernel alone
+    11: ["chunk_sums"] + _STAGE + ["sumcheck_small"],                                     # one stage, the short fold form
+    19: ["chunk_sums"] + _STAGE + _STAGE + ["sumcheck_small"],                            # two stages: tabA / tabB, partA / partB
+    21: ["chunk_sums", "sumcheck_small", "multifold"] + _STAGE + ["sumcheck_small"],      # the first fold in the matrix-core form
+}
+ENQUEUE_ORDER_OVERLAPPED = {                                                              # with ZKHIP_OVERLAP_MIN_LOG=19
+    "19": _OVERLAPPED_PROOF,                                                              # k1 = 3 (the vector form: both names), k2 = 8
+    "20": _OVERLAPPED_PROOF,                                                              # k2 = 9
+    # four begun, then collected: the first two whole, the third and the fourth up to their second serial launch; the third's second
+    # half goes out when the fourth begins, the fourth's with the first wait()
+    "4 x 19": 2 * _OVERLAPPED_PROOF + 2 * (_OVERLAPPED_FIRST_HALF + ["sumcheck_small"]) + 2 * _OVERLAPPED_SECOND_HALF,
+}
+
+
+def _enqueue_order(zk, run):
+    """What run() returns, and the names the profile recorded while it ran, in host enqueue order."""
+    import ctypes as C
+    from zk_cryptography_amd import _native as N
+    ctx, lib, mx = N.Context.get(), N.lib(), 256
+    N.check(lib.zkhip_profile_enable(ctx.handle, 1), "profile_enable")
+    try:
+        out = run()
+        names, st, sp, cnt = C.create_string_buffer(32 * mx), (C.c_double * mx)(), (C.c_double * mx)(), C.c_uint32(0)
+        N.check(lib.zkhip_profile_timeline(ctx.handle, mx, names, st, sp, C.byref(cnt)), "profile_timeline")
+    finally:
+        N.check(lib.zkhip_profile_enable(ctx.handle, 0), "profile_enable")
+    assert cnt.value < mx
+    return out, [names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode() for i in range(cnt.value)]
+
+
+def _unsummed(zk, ev):
+    """A prover that never ran poly_sum() and hands in no claimed sum: the library computes every sum itself and absorbs the true one."""
+    sc = zk.Sumcheck(zk.Multilinear(ev))
+    sc._sum_deferred = True
+    return sc
+
+
+def _same_as_oracle(ora, ev, got):
+    (proof, ch), (s, rp, och) = got, ora.sumcheck_prove(ev)
+    return np.array_equal(proof.sum, s) and np.array_equal(proof.univariate_poly, rp) and np.array_equal(ch, och)
+
+
+def _synchronous_order(zk, ora, log_n):
+    ev = ora.random_fr(1 << log_n, 6200 + log_n)
+    sc = _unsummed(zk, ev)
+    got, names = _enqueue_order(zk, sc.prove)
+    assert _same_as_oracle(ora, ev, got)
+    return names
+
+
+def _four_in_flight_order(zk, ora, log_n):
+    """Four proofs begun back to back, then collected: the third and the fourth hold their second halves back (zkhip_ctx::deferred)."""
+    evs = [ora.random_fr(1 << log_n, 6300 + j) for j in range(4)]
+    scs = [_unsummed(zk, ev) for ev in evs]
+    got, names = _enqueue_order(zk, lambda: [h.wait() for h in [sc.prove_begin() for sc in scs]])
+    assert all(_same_as_oracle(ora, ev, g) for ev, g in zip(evs, got))
+    return names
+
+
+@pytest.mark.parametrize("log_n", sorted(ENQUEUE_ORDER))
+def test_enqueue_order_of_the_stage_plan(zk, ora, log_n):
+    names = _synchronous_order(zk, ora, log_n)
+    print(log_n, names)
+    assert names == ENQUEUE_ORDER[log_n]
+
+
+def _overlapped_orders():
+    """Runs in a process of its own: the switch is read once."""
+    import zk_cryptography_amd as zk
+    from oracle import oracle as ora
+    ora.lib()
+    return {"19": _synchronous_order(zk, ora, 19), "20": _synchronous_order(zk, ora, 20), "4 x 19": _four_in_flight_order(zk, ora, 19)}
+
+
+def test_enqueue_order_of_the_overlapped_plan():
+    """The overlapped plan at its smallest sizes, synchronous and with the second halves of two of four proofs held back."""
+    import json, os, subprocess, sys
+    env = dict(os.environ, ZKHIP_OVERLAP_MIN_LOG="19")
+    out = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    text = out.stdout.decode()
+    assert out.returncode == 0, text[-3000:]
+    got = json.loads(text.strip().splitlines()[-1])
+    print(got)
+    assert got == ENQUEUE_ORDER_OVERLAPPED
+
+
+if __name__ == "__main__":
+    import json, os, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(json.dumps(_overlapped_orders()))

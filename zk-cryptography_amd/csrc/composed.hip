@@ -569,6 +569,29 @@ struct ComposedRun {
         for (uint32_t p = 0; p < n_terms; ++p) if (lin_cur[p]) tt.in[meta.lin_tab[p]] = lin_cur[p];
         return tt;
     }
+    // every round from the current one down to and including the tail: from the round whose tables fit the LDS on, one launch
+    // finishes the proof
+    int rounds_to_tail() {
+        while (round < n_rounds) {
+            if (after() <= tail_len) return tail(current_tables(), (uint32_t)after(), folds());
+            if (stage_ok()) { ZK_TRY(stage()); continue; }
+            if (pipe_mid_ok()) {                 // one launch per round, one round ahead, down to the LDS tail
+                ZK_TRY(pipe_mid());
+                // pipe_mid() ends with the tables still unfolded at the last closed round's challenge and that challenge's Montgomery form
+                // not yet in d_ch: only tail_after_pipe() continues from there.  It runs down to the LDS tail by construction (tail_len >=
+                // 256 >= the steady loop's exit); if a change of constants ever broke that, fail here rather than fold by an unwritten value.
+                if (pipe_records) {
+                    if (cn > tail_len) return ZKHIP_ERR_ARG;
+                    return tail_after_pipe();
+                }
+                continue;
+            }
+            int grid = 0;
+            ZK_TRY(round_sums(&grid));
+            close(d_partials, (uint32_t)grid);
+        }
+        return ZKHIP_OK;
+    }
     // round polynomials and challenges to the host, in the layouts of the C ABI
     // launch errors of everything enqueued so far (the transcript already lives in the context's persistent state, where a
     // continuation picks it up)
@@ -621,29 +644,7 @@ static int composed_prove_impl(zkhip_ctx* c, const uint64_t* const* ptrs, const 
     ZK_TRY(c->activate());
     ComposedRun run;
     ZK_TRY(run.setup(c, ptrs, term_sizes, n_terms, n, n_vars, multi, h_sum, partial, lin_ptrs, cont));
-    // From the round whose tables fit the LDS on, one launch finishes the proof.
-    while (run.round < n_vars) {
-        if (run.after() <= run.tail_len) {
-            ZK_TRY(run.tail(run.current_tables(), (uint32_t)run.after(), run.folds()));
-            break;
-        }
-        if (run.stage_ok()) { ZK_TRY(run.stage()); continue; }
-        if (run.pipe_mid_ok()) {                 // one launch per round, one round ahead, down to the LDS tail
-            ZK_TRY(run.pipe_mid());
-            // pipe_mid() ends with the tables still unfolded at the last closed round's challenge and that challenge's Montgomery form
-            // not yet in d_ch: only tail_after_pipe() continues from there.  It runs down to the LDS tail by construction (tail_len >=
-            // 256 >= the steady loop's exit); if a change of constants ever broke that, fail here rather than fold by an unwritten value.
-            if (run.pipe_records) {
-                if (run.cn > run.tail_len) return ZKHIP_ERR_ARG;
-                ZK_TRY(run.tail_after_pipe());
-                break;
-            }
-            continue;
-        }
-        int grid = 0;
-        ZK_TRY(run.round_sums(&grid));
-        run.close(run.d_partials, (uint32_t)grid);
-    }
+    ZK_TRY(run.rounds_to_tail());
     return run.collect(h_lens, h_round_polys, h_challenges);
 }
 
@@ -670,28 +671,7 @@ int zk_multi_composed_enqueue(zkhip_ctx* c, const uint64_t* const* ptrs, const u
         if (ex->d_round_polys) run.d_rp = ex->d_round_polys;
         if (ex->d_challenges) run.d_ch = ex->d_challenges;
     }
-    while (run.round < n_vars) {
-        if (run.after() <= run.tail_len) {
-            ZK_TRY(run.tail(run.current_tables(), (uint32_t)run.after(), run.folds()));
-            break;
-        }
-        if (run.stage_ok()) { ZK_TRY(run.stage()); continue; }
-        if (run.pipe_mid_ok()) {                 // one launch per round, one round ahead, down to the LDS tail
-            ZK_TRY(run.pipe_mid());
-            // pipe_mid() ends with the tables still unfolded at the last closed round's challenge and that challenge's Montgomery form
-            // not yet in d_ch: only tail_after_pipe() continues from there.  It runs down to the LDS tail by construction (tail_len >=
-            // 256 >= the steady loop's exit); if a change of constants ever broke that, fail here rather than fold by an unwritten value.
-            if (run.pipe_records) {
-                if (run.cn > run.tail_len) return ZKHIP_ERR_ARG;
-                ZK_TRY(run.tail_after_pipe());
-                break;
-            }
-            continue;
-        }
-        int grid = 0;
-        ZK_TRY(run.round_sums(&grid));
-        run.close(run.d_partials, (uint32_t)grid);
-    }
+    ZK_TRY(run.rounds_to_tail());
     return run.check_launches();
 }
 int zk_multi_composed_collect(zkhip_ctx* c, uint32_t n_rounds, uint32_t* h_lens, uint64_t* h_round_polys, uint64_t* h_challenges) {

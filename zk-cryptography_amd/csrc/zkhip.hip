@@ -561,8 +561,26 @@ static int launch_small(zkhip_ctx* c, const SmallArgs& a, SumcheckDev* st, uint6
     return ZKHIP_OK;
 }
 
-// the first fold of the overlapped plan (k <= 6 variables, 2^19 .. 2^24 entries) leaves its partial tables in 2 x 1024 entries (d_p1
+// the arguments of a serial launch: n_rounds rounds from round0 on, on this source; every other field zero (the transcript continues)
+static SmallArgs small_rounds(const uint64_t* src, uint32_t group, uint32_t stride, uint32_t canon, uint32_t log_n, uint32_t n_rounds,
+                              uint32_t round0, uint64_t* weights_out) {
+    SmallArgs a = {};
+    a.src = src; a.group = group; a.stride = stride; a.canon = canon; a.log_n = log_n; a.n_rounds = n_rounds; a.round0 = round0;
+    a.weights_out = weights_out;
+    return a;
+}
+// how the transcript opens (SmallArgs::first; the first serial launch of a proof alone consumes it): not at all when the launch continues
+// one, else with the host's claimed sum, the device's, or lo + hi
+static void small_open(SmallArgs& a, bool opens, const uint64_t* h_claimed, const uint64_t* d_claimed) {
+    a.first = !opens ? 0u : h_claimed ? 2u : d_claimed ? 3u : 1u;
+    if (a.first == 2) std::memcpy(a.claimed.v, h_claimed, 32);   // prove(&self) absorbs self.sum (sumcheck.rs:33-35)
+    if (a.first == 3) a.d_claimed = d_claimed;
+}
+
+// the first fold of the overlapped plan (k <= 6 variables, 2^19 .. 2^24 entries) leaves its partial tables in 2 x 1024 entries (ProofLayout::p1
 // below, the sharded stage's d_mid), the second one (m = 256, k <= 10) in 32 x 256
+constexpr size_t SC_FINE_ENTRIES = (size_t)1 << 16;       // fine sums: n / 256 <= 2^16
+constexpr size_t SC_P1_ENTRIES = 2 * 1024, SC_P2_ENTRIES = 32 * 256;
 constexpr bool blockfold_fits(uint32_t m, uint32_t k_max, uint32_t room) {
     for (uint32_t k = 1; k <= k_max; ++k) {
         BlockfoldShape sh = {};
@@ -570,7 +588,8 @@ constexpr bool blockfold_fits(uint32_t m, uint32_t k_max, uint32_t room) {
     }
     return true;
 }
-static_assert(blockfold_fits(256, 6, 2048) && blockfold_fits(512, 6, 2048) && blockfold_fits(1024, 6, 2048) && blockfold_fits(256, 10, 32 * 256),
+static_assert(blockfold_fits(256, 6, SC_P1_ENTRIES) && blockfold_fits(512, 6, SC_P1_ENTRIES) && blockfold_fits(1024, 6, SC_P1_ENTRIES) &&
+              blockfold_fits(256, 10, SC_P2_ENTRIES),
               "blockfold_shape: more partial tables than the prover's buffers hold");
 // k-variable fold of a small table spread over the chip: partial tables P[y][m], y < *n_slices (blockfold_kernel; its grid and
 // the split of the terms come from blockfold_shape, multifold_kernels.hpp)
@@ -611,32 +630,19 @@ static int launch_fine_sums(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uin
     return ZKHIP_OK;
 }
 
+// partial sums of the table `cur` (cn entries in blocks of m) at chunk = min(m, 4096) entries per workgroup, on `stream` into d_partials
+// (cn / chunk values).  Returns how many partials each block has and leaves in *parts where they are: the table's entries themselves,
+// and no launch, when a block is shorter than a workgroup.
+static uint32_t launch_chunk_sums(zkhip_ctx* c, hipStream_t stream, const uint64_t* cur, size_t cn, size_t m, uint64_t* d_partials,
+                                  const uint64_t** parts) {
+    const uint32_t chunk = (uint32_t)std::min<size_t>(m, 4096);
+    if (chunk < (uint32_t)MLE_BLOCK) { *parts = cur; return (uint32_t)m; }   // tiny table: every entry is its own partial
+    ProfScope ps(c, "chunk_sums", 32.0 * (double)cn, stream);
+    hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)(cn / chunk)), dim3(MLE_BLOCK), 0, stream, cur, chunk, d_partials);
+    *parts = d_partials;
+    return (uint32_t)(m / chunk);
+}
 // (2^log_blocks block sums, then the total) of a table, on the device
-static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks, uint64_t* d_out, uint64_t* h_total, bool want_total);
-extern "C" int zkhip_mle_block_sums(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks,
-                                    uint64_t* d_out, uint64_t* h_total) {
-    return block_sums_impl(c, d_evals, n, log_blocks, d_out, h_total, true);
-}
-// The same without the total where it would cost a launch of its own (the fine granularity of the overlapped plan): a prover that
-// is going to absorb the TRUE sum gets it from its own sum tree (zkhip_sumcheck_prove with both claimed-sum arguments NULL), and
-// zkhip_mle_block_sums_total delivers it to a caller who wants to look at it first.
-extern "C" int zkhip_mle_block_sums_deferred(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks, uint64_t* d_out) {
-    return block_sums_impl(c, d_evals, n, log_blocks, d_out, nullptr, false);
-}
-extern "C" int zkhip_mle_block_sums_total(zkhip_ctx* c, uint64_t* d_block_sums, uint32_t log_blocks, uint64_t* h_total) {
-    if (!c || !d_block_sums || !h_total || log_blocks > 16) return ZKHIP_ERR_ARG;
-    ZK_TRY(c->activate());
-    // two levels: 2^(lb/2) workgroups sum runs of the block sums into the context's scratch, one workgroup adds those
-    const uint32_t hi = log_blocks / 2, lo = log_blocks - hi;
-    uint64_t* tmp = c->small_u64(ZK_SMALL_PARTIALS);
-    hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << hi), dim3(MLE_BLOCK), 0, c->stream, d_block_sums, 1u << lo, tmp, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, tmp, 1u << hi, d_block_sums + 4 * ((size_t)1 << log_blocks), (uint64_t*)nullptr);
-    ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->pinned_u64(ZK_PIN_RES), d_block_sums + 4 * ((size_t)1 << log_blocks), 32, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(h_total, c->pinned_u64(ZK_PIN_RES), 32);
-    return ZKHIP_OK;
-}
 static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks, uint64_t* d_out, uint64_t* h_total, bool want_total) {
     if (!c || !d_evals || !d_out) return ZKHIP_ERR_ARG;
     if (!is_pow2(n) || log_blocks > 16 || ((size_t)1 << log_blocks) > n) return ZKHIP_ERR_SHAPE;
@@ -671,19 +677,13 @@ static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint
             c->coarse_of[cs] = d_out; c->coarse_n[cs] = n; c->coarse_k1[cs] = k1;
         }
     } else {
-        const uint32_t chunk = (uint32_t)std::min<size_t>(m, 4096);
-        const size_t n_chunks = n / chunk;
+        const size_t n_chunks = n / std::min<size_t>(m, 4096);
         uint64_t* d_partials;
         if (n_chunks <= 8 * (size_t)ZK_MAX_PARTIALS) d_partials = c->small_u64(ZK_SMALL_PARTIALS);
         else { ZK_TRY(c->reserve_ws(n_chunks * 32)); d_partials = (uint64_t*)c->ws.ptr; }
-        if (chunk >= (uint32_t)MLE_BLOCK) {
-            ProfScope ps(c, "chunk_sums", 32.0 * (double)n);
-            hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)n_chunks), dim3(MLE_BLOCK), 0, c->stream, d_evals, chunk, d_partials);
-            hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, d_partials, (uint32_t)(m / chunk),
-                               1u << log_blocks, d_out);
-        } else {   // tiny table: every entry is its own partial
-            hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, d_evals, (uint32_t)m, 1u << log_blocks, d_out);
-        }
+        const uint64_t* parts = nullptr;
+        const uint32_t group = launch_chunk_sums(c, c->stream, d_evals, n, m, d_partials, &parts);
+        hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, parts, group, 1u << log_blocks, d_out);
     }
     ZK_HIP(c, hipGetLastError());
     if (h_total) {
@@ -694,195 +694,240 @@ static int block_sums_impl(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint
     return ZKHIP_OK;
 }
 
+extern "C" int zkhip_mle_block_sums(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks,
+                                    uint64_t* d_out, uint64_t* h_total) {
+    return block_sums_impl(c, d_evals, n, log_blocks, d_out, h_total, true);
+}
+// The same without the total where it would cost a launch of its own (the fine granularity of the overlapped plan): a prover that
+// is going to absorb the TRUE sum gets it from its own sum tree (zkhip_sumcheck_prove with both claimed-sum arguments NULL), and
+// zkhip_mle_block_sums_total delivers it to a caller who wants to look at it first.
+extern "C" int zkhip_mle_block_sums_deferred(zkhip_ctx* c, const uint64_t* d_evals, size_t n, uint32_t log_blocks, uint64_t* d_out) {
+    return block_sums_impl(c, d_evals, n, log_blocks, d_out, nullptr, false);
+}
+extern "C" int zkhip_mle_block_sums_total(zkhip_ctx* c, uint64_t* d_block_sums, uint32_t log_blocks, uint64_t* h_total) {
+    if (!c || !d_block_sums || !h_total || log_blocks > 16) return ZKHIP_ERR_ARG;
+    ZK_TRY(c->activate());
+    // two levels: 2^(lb/2) workgroups sum runs of the block sums into the context's scratch, one workgroup adds those
+    const uint32_t hi = log_blocks / 2, lo = log_blocks - hi;
+    uint64_t* tmp = c->small_u64(ZK_SMALL_PARTIALS);
+    hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << hi), dim3(MLE_BLOCK), 0, c->stream, d_block_sums, 1u << lo, tmp, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, tmp, 1u << hi, d_block_sums + 4 * ((size_t)1 << log_blocks), (uint64_t*)nullptr);
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(c->pinned_u64(ZK_PIN_RES), d_block_sums + 4 * ((size_t)1 << log_blocks), 32, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(h_total, c->pinned_u64(ZK_PIN_RES), 32);
+    return ZKHIP_OK;
+}
+
+// Where the buffers of one proof lie in its workspace, in field elements: stage tables (n/4 + n/16 + ...; overlapped: n / 2^k1 <= n/8),
+// partial sums (chunk sums of stage 0, per-workgroup sums of stage outputs), fold weights, and for the overlapped plan the fine sums
+// (n/256 <= 2^16) and two sets of partial tables (<= 2 x 1024 and 32 x 256).  The tables' alignment is part of the measured speed.
+struct ProofLayout { size_t tabA, tabB, partA, partB, w, w2, fine, p1, p2, total; };
+constexpr ProofLayout proof_layout(size_t n, bool overlap) {
+    const size_t part = n / 256 + 1024, w = (size_t)1 << TREE_MAX_LOG;
+    ProofLayout l = {};
+    l.tabA = 0;
+    l.tabB = (overlap ? n / 8 : n / 4) + 32;
+    l.partA = (overlap ? n / 8 : n / 4 + n / 16) + 64;
+    l.partB = l.partA + part;
+    l.w = l.partB + part;
+    l.w2 = l.w + w;
+    l.fine = l.w2 + w;                                 // overlapped plan only from here on
+    l.p1 = l.fine + SC_FINE_ENTRIES;
+    l.p2 = l.p1 + SC_P1_ENTRIES;
+    l.total = overlap ? l.p2 + SC_P2_ENTRIES : l.fine;
+    return l;
+}
+static_assert(proof_layout((size_t)1 << 24, true).tabB == 2097184 && proof_layout((size_t)1 << 24, true).partA == 2097216 &&
+              proof_layout((size_t)1 << 24, true).total == 2230336 + (2 << TREE_MAX_LOG) + 65536 + 2048 + 8192,
+              "the bench size's tables have moved");
+// One proof in flight: its streams, events and buffers and where its transcript stands.  Plain data: the deferred second half keeps a copy.
+struct ProofRun {
+    hipStream_t S, F;                        // serial / fold streams
+    hipEvent_t fork_ev, serial_ev;
+    uint64_t *tabA, *tabB, *partA, *partB, *w, *w2, *fine, *p1, *p2;
+    SumcheckDev* st;
+    uint64_t *d_rp, *d_ch, *d_fin;
+    long long host_delta;                    // the proof leaves through the LAST serial kernel: it writes [sum .. round polynomials] into the pinned slot itself (SmallArgs::host_delta)
+    uint32_t round;                          // rounds enqueued so far
+    const uint64_t *h_claimed, *d_claimed;   // read by the launch of round 0 only (the host's pointer is the caller's: dead in a deferred half)
+    // the next k rounds of the proof, on a working table of 2^k entries
+    SmallArgs rounds(const uint64_t* src, uint32_t group, uint32_t stride, uint32_t canon, uint32_t k, uint64_t* weights_out) {
+        SmallArgs a = small_rounds(src, group, stride, canon, k, k, round, weights_out);
+        small_open(a, round == 0, h_claimed, d_claimed);
+        round += k;
+        return a;
+    }
+    // ... which are the last ones
+    SmallArgs closing_rounds(const uint64_t* src, uint32_t group, uint32_t stride, uint32_t canon, uint32_t k) {
+        SmallArgs a = rounds(src, group, stride, canon, k, nullptr);
+        a.final_out = d_fin; a.host_delta = host_delta;
+        return a;
+    }
+};
+// `lane` < 0: on the caller's stream with the context's buffers (the synchronous call); otherwise on the private streams and buffers of
+// c->lanes[lane], behind everything the caller's stream holds at this moment
+static int proof_setup(zkhip_ctx* c, size_t n, bool overlap, const uint64_t* h_claimed_sum, const uint64_t* d_claimed_sum, int slot, int lane,
+                       ProofRun& p) {
+    const ProofLayout l = proof_layout(n, overlap);
+    const size_t ws_need = l.total * 32;
+    p = {};
+    uint64_t *ws, *small;
+    if (lane < 0) {
+        ZK_TRY(c->reserve_ws(ws_need));
+        ws = (uint64_t*)c->ws.ptr; small = (uint64_t*)c->d_small.get(); p.S = c->stream;
+        if (overlap) { ZK_TRY(c->ensure_fold_stream()); p.F = c->fold_stream.get(); p.fork_ev = c->fork_ev.get(); p.serial_ev = c->serial_ev.get(); }
+    } else {
+        ZK_TRY(c->ensure_lane(lane, ws_need));
+        zkhip_ctx::ProofLane& L = c->lanes[lane];
+        ws = (uint64_t*)L.ws.ptr; small = (uint64_t*)L.small.get(); p.S = L.serial; p.F = L.fold; p.fork_ev = L.fork_ev.get(); p.serial_ev = L.serial_ev.get();
+        ZK_HIP(c, hipEventRecord(L.begin_ev.get(), c->stream));          // the table, its block sums and the claimed sum are ready behind this
+        ZK_HIP(c, hipStreamWaitEvent(p.S, L.begin_ev.get(), 0));
+    }
+    p.tabA = ws + 4 * l.tabA; p.tabB = ws + 4 * l.tabB; p.partA = ws + 4 * l.partA; p.partB = ws + 4 * l.partB;
+    p.w = ws + 4 * l.w; p.w2 = ws + 4 * l.w2; p.fine = ws + 4 * l.fine; p.p1 = ws + 4 * l.p1; p.p2 = ws + 4 * l.p2;
+    p.st = (SumcheckDev*)(small + ZK_SMALL_STATE);
+    p.d_rp = small + ZK_SMALL_ROUNDPOLYS;
+    p.d_ch = small + ZK_SMALL_CHALLENGES;
+    p.d_fin = small + ZK_SMALL_RES;
+    ZK_TRY(c->ensure_proof_slot(slot));
+    p.host_delta = ((long long)(intptr_t)c->proof_pin[slot].get() - (long long)(intptr_t)(small + ZK_SMALL_STATE)) / 8;
+    p.h_claimed = h_claimed_sum; p.d_claimed = d_claimed_sum;
+    return ZKHIP_OK;
+}
+// the overlapped plan's last stage, on the stream that has the big fold's result: the 2^(8 + k2)-entry table folded by k2 variables,
+// then the closing eight rounds, which deliver the proof
+static int proof_last_stage(zkhip_ctx* c, ProofRun p, hipStream_t stream, uint32_t k2) {
+    uint32_t ny = 0;
+    ZK_TRY(launch_blockfold(c, stream, p.tabA, 256, k2, p.w2, p.p2, &ny));
+    return launch_small(c, p.closing_rounds(p.p2, ny, 256, 1, 8), p.st, p.d_rp, p.d_ch, 0, stream);
+}
+// The overlapped plan (above stage_k).  *tail: the stream the proof ends on, or null when its second half was held back (three or more
+// proofs in flight), which then records the proof's event itself.
+static int proof_overlapped(zkhip_ctx* c, ProofRun& p, const uint64_t* d_evals, size_t n, const uint64_t* d_block_sums, uint32_t log_blocks,
+                            int slot, int lane, int in_flight, hipStream_t* tail) {
+    const uint32_t g = log2_exact(n) - 8, k2 = overlapped_k2(n), k1 = g - k2;
+    const hipStream_t S = p.S;
+    const uint64_t* fine = d_block_sums;
+    if (!fine || log_blocks != g) {             // poly_sum() was not called (or with another granularity)
+        // three or more proofs in flight: this streaming pass belongs onto the caller's stream like every other one (below); the
+        // serial stream follows it
+        const bool on_callers = lane >= 0 && in_flight >= 3;
+        ZK_TRY(launch_fine_sums(c, d_evals, n, g, p.fine, nullptr, on_callers ? c->stream : S));
+        if (on_callers) {
+            ZK_HIP(c, hipEventRecord(c->lanes[lane].begin_ev.get(), c->stream));
+            ZK_HIP(c, hipStreamWaitEvent(S, c->lanes[lane].begin_ev.get(), 0));
+        }
+        fine = p.fine;
+    }
+    // the coarse sums poly_sum() left for this table (the newest ring entry that names its fine sums), or our own
+    int cs = -1;
+    for (int q = 1; q <= zkhip_ctx::COARSE_RING && cs < 0; ++q) {
+        const int e = (c->coarse_next - q + 2 * zkhip_ctx::COARSE_RING) % zkhip_ctx::COARSE_RING;
+        if (fine == d_block_sums && c->coarse_of[e] == fine && c->coarse_n[e] == n && c->coarse_k1[e] == k1) cs = e;
+    }
+    if (cs < 0) {
+        ZK_TRY(c->next_coarse(&cs));
+        ProfScope ps(c, "coarse_sums", 0.0, S);
+        hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << k1), dim3(MLE_BLOCK), 0, S, fine, 1u << k2, (uint64_t*)nullptr, (uint64_t*)c->d_coarse[cs].get());
+    }
+    const uint64_t* coarse = (const uint64_t*)c->d_coarse[cs].get();
+    c->coarse_of[cs] = nullptr;                 // the entry belongs to this proof from here on:
+    c->coarse_owner[cs] = slot + 1;             // the ring skips it until the proof has been collected (sumcheck_collect / prove_end)
+    ZK_TRY(launch_small(c, p.rounds(coarse, 0, 0, 1, k1, p.w), p.st, p.d_rp, p.d_ch, 0, S));
+    // fork: the big fold on the fold stream next to rounds k1+1 .. g.  The serial kernel of those rounds asks for
+    // (nearly) a whole CU's LDS, so no fold workgroup shares its CU (beside 8+ fold waves per SIMD the transcript
+    // wave ran at half speed)
+    // The fork comes BEHIND the small fold: the serial kernel (next in this queue) and the big fold (another queue, behind
+    // an event) then become ready together and the serial kernel's single workgroup is placed first.  Forked before
+    // the small fold, the big fold filled every CU first and the serial kernel waited for one to drain (~60 us).
+    uint32_t ny = 0, n_parts = 0;
+    ZK_TRY(launch_blockfold(c, S, fine, 1u << k2, k1, p.w, p.p1, &ny));
+    ZK_HIP(c, hipEventRecord(p.fork_ev, S));
+    const SmallArgs b = p.rounds(p.p1, ny, 1u << k2, 1, k2, p.w2);
+    if (lane >= 0 && in_flight < 3) { ZK_TRY(c->ensure_lane_fold(lane)); p.F = c->lanes[lane].fold; }
+    if (lane >= 0 && in_flight >= 3) {
+        // Three or more proofs in flight: the streaming passes of ALL of them on ONE stream, the caller's -- where poly_sum() puts the sums
+        // passes already.  The big fold and what follows it are enqueued LATER (zkhip_ctx::deferred), behind the sums passes of the next
+        // one to three tables, so that the caller's stream never stands waiting for this proof's first rounds; the serial kernel of
+        // rounds k1+1 .. g goes out now, the last stage follows the fold on the serial stream.  Measured at 2^24 (profiles/r06/NOTES.md
+        // section 7): 0.207 ms per proof with eight in flight against 0.233 with a fold stream per lane.
+        ZK_TRY(launch_small(c, b, p.st, p.d_rp, p.d_ch, 156 * 1024, S));
+        c->deferred_rc[slot] = ZKHIP_OK;
+        const ProofRun held = p;
+        c->deferred.emplace_back(slot, [c, held, d_evals, n, k1, k2, slot]() -> int {
+            uint32_t np2 = 0;
+            ZK_HIP(c, hipStreamWaitEvent(c->stream, held.fork_ev, 0));
+            ZK_TRY(launch_multifold(c, c->stream, d_evals, n, k1, held.w, held.tabA, held.partA, &np2));
+            ZK_HIP(c, hipEventRecord(held.serial_ev, c->stream));
+            ZK_HIP(c, hipStreamWaitEvent(held.S, held.serial_ev, 0));
+            ZK_TRY(proof_last_stage(c, held, held.S, k2));
+            ZK_HIP(c, hipEventRecord(c->proof_ev[slot].get(), held.S));
+            return ZKHIP_OK;
+        });
+        // how many second halves stay back: enough sums passes in front of a fold that its proof's first rounds are over when its turn
+        // comes (1-3 tables), few enough that the host, which stops at its depth, still has passes queued (depth 3 / 4: 1, 5: 2, 6+: 3)
+        // (a second half that cannot be enqueued is its OWN proof's failure -- recorded in deferred_rc, reported by that proof's prove_end --
+        // not this proof's: this one's second half is in the queue now and the ticket must reach the caller)
+        (void)c->flush_deferred((size_t)std::min(3, std::max(1, in_flight - 3)));
+        *tail = nullptr;
+        return ZKHIP_OK;
+    }
+    ZK_HIP(c, hipStreamWaitEvent(p.F, p.fork_ev, 0));
+    ZK_TRY(launch_multifold(c, p.F, d_evals, n, k1, p.w, p.tabA, p.partA, &n_parts));
+    ZK_TRY(launch_small(c, b, p.st, p.d_rp, p.d_ch, 156 * 1024, S));
+    // join ON THE FOLD STREAM: the serial kernel ends well before the big fold, so its event is long set when the fold
+    // ends and the last stage follows the fold in stream order (joining on the caller's stream left the chip idle for the
+    // ~13 us a cross-stream dependency takes to resolve); the proof is copied from there too
+    ZK_HIP(c, hipEventRecord(p.serial_ev, S));
+    ZK_HIP(c, hipStreamWaitEvent(p.F, p.serial_ev, 0));
+    *tail = p.F;
+    return proof_last_stage(c, p, p.F, k2);
+}
+// The stage plan (stage_k): per stage, the k rounds on partial sums of the table and its fold by their k challenges; the serial kernel
+// takes the rest.  All on the serial stream.
+static int proof_stages(zkhip_ctx* c, ProofRun& p, const uint64_t* d_evals, size_t n, const uint64_t* d_block_sums, uint32_t log_blocks) {
+    const uint64_t* cur = d_evals;
+    size_t cn = n;
+    const uint64_t* parts = nullptr;   // partial sums of `cur`, `group` consecutive ones per block of this stage
+    uint32_t n_parts = 0;
+    for (uint32_t stage = 0; stage_k(cn) != 0; ++stage) {
+        const uint32_t k = stage_k(cn);
+        const size_t m = cn >> k;
+        uint32_t group;
+        if (stage == 0 && d_block_sums && log_blocks >= k && log_blocks <= (uint32_t)MF_CAP_LOGK) {   // poly_sum() already streamed the table once
+            parts = d_block_sums;
+            group = 1u << (log_blocks - k);
+        } else if (stage == 0) {
+            group = launch_chunk_sums(c, p.S, cur, cn, m, p.partA, &parts);   // m >= 256 here
+        } else {
+            group = (uint32_t)(n_parts >> k);
+        }
+        ZK_TRY(launch_small(c, p.rounds(parts, group, 0, 0, k, p.w), p.st, p.d_rp, p.d_ch, 0, p.S));
+        uint64_t* dst = (stage & 1) ? p.tabB : p.tabA;
+        uint64_t* pdst = (stage & 1) ? p.partB : p.partA;
+        ZK_TRY(launch_multifold(c, p.S, cur, cn, k, p.w, dst, pdst, &n_parts));
+        parts = pdst;
+        cur = dst;
+        cn = m;
+    }
+    return launch_small(c, p.closing_rounds(cur, 0, 0, 0, log2_exact(cn)), p.st, p.d_rp, p.d_ch, 0, p.S);
+}
 // The prover in two halves: sumcheck_enqueue launches every kernel and the copy of the proof into pinned slot `slot`,
 // sumcheck_collect waits for that copy (polling its event) and hands the proof out.  A caller with several tables to prove
 // begins the next proof before it collects the previous one (zkhip_sumcheck_prove_begin / _end): the kernels of successive
 // proofs run in stream order, what disappears is the idle time between them (host wake-up, return, next call's first launch).
-// `lane` < 0: on the caller's stream with the context's buffers (the synchronous call); otherwise on the private streams and buffers of
-// c->lanes[lane], behind everything the caller's stream holds at this moment
 static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, const uint64_t* h_claimed_sum,
                             const uint64_t* d_claimed_sum, const uint64_t* d_block_sums, uint32_t log_blocks, int slot, int lane, int in_flight = 1) {
-    const uint32_t n_vars = log2_exact(n);
     const bool overlap = overlapped_plan(n);
-    // workspace: stage tables (n/4 + n/16 + ...; overlapped: n / 2^k1 <= n/8), partial sums, fold weights, and for the
-    // overlapped plan the fine sums (n/256 <= 2^16) and two sets of partial tables (<= 2 x 1024 and 32 x 256)
-    const size_t tab_entries = overlap ? n / 8 + 64 : n / 4 + n / 16 + 64;
-    const size_t tabA_entries = overlap ? n / 8 + 32 : n / 4 + 32;
-    const size_t part_entries = std::max<size_t>(n / 4096, n / 256) + 1024;   // chunk sums of stage 0, per-workgroup sums of stage outputs
-    const size_t w_entries = (size_t)1 << TREE_MAX_LOG;
-    const size_t fine_entries = overlap ? 65536 + 2 * 1024 + 32 * 256 : 0;
-    const size_t ws_need = (tab_entries + 2 * part_entries + 2 * w_entries + fine_entries) * 32;
-    hipStream_t S, F = nullptr;                   // serial / fold streams of this proof
-    hipEvent_t fork_ev = nullptr, serial_ev = nullptr;
-    uint64_t *ws, *small;
-    if (lane < 0) {
-        ZK_TRY(c->reserve_ws(ws_need));
-        ws = (uint64_t*)c->ws.ptr; small = (uint64_t*)c->d_small.get(); S = c->stream;
-        if (overlap) { ZK_TRY(c->ensure_fold_stream()); F = c->fold_stream.get(); fork_ev = c->fork_ev.get(); serial_ev = c->serial_ev.get(); }
-    } else {
-        ZK_TRY(c->ensure_lane(lane, ws_need));
-        zkhip_ctx::ProofLane& L = c->lanes[lane];
-        ws = (uint64_t*)L.ws.ptr; small = (uint64_t*)L.small.get(); S = L.serial; F = L.fold; fork_ev = L.fork_ev.get(); serial_ev = L.serial_ev.get();
-        ZK_HIP(c, hipEventRecord(L.begin_ev.get(), c->stream));          // the table, its block sums and the claimed sum are ready behind this
-        ZK_HIP(c, hipStreamWaitEvent(S, L.begin_ev.get(), 0));
-    }
-    uint64_t* tabA = ws;
-    uint64_t* tabB = tabA + 4 * tabA_entries;
-    uint64_t* partA = ws + 4 * tab_entries;
-    uint64_t* partB = partA + 4 * part_entries;
-    uint64_t* d_w = partB + 4 * part_entries;
-    uint64_t* d_w2 = d_w + 4 * w_entries;
-    uint64_t* d_fine = d_w2 + 4 * w_entries;           // overlapped plan only from here on
-    uint64_t* d_p1 = d_fine + 4 * 65536;
-    uint64_t* d_p2 = d_p1 + 4 * 2 * 1024;
-    SumcheckDev* st = (SumcheckDev*)(small + ZK_SMALL_STATE);
-    uint64_t* d_rp = small + ZK_SMALL_ROUNDPOLYS;
-    uint64_t* d_ch = small + ZK_SMALL_CHALLENGES;
-    uint64_t* d_fin = small + ZK_SMALL_RES;
-    // the proof leaves through the LAST serial kernel: it writes [sum .. round polynomials] into the pinned slot itself (SmallArgs::host_delta)
-    ZK_TRY(c->ensure_proof_slot(slot));
-    const long long host_delta = ((long long)(intptr_t)c->proof_pin[slot].get() - (long long)(intptr_t)(small + ZK_SMALL_STATE)) / 8;
-
-    FrArg claimed = {};
-    uint32_t first = 1;
-    if (h_claimed_sum) { std::memcpy(claimed.v, h_claimed_sum, 32); first = 2; }   // prove(&self) absorbs self.sum (sumcheck.rs:33-35)
-    else if (d_claimed_sum) first = 3;
-
-    const uint64_t* cur = d_evals;
-    size_t cn = n;
-    uint32_t round = 0, stage = 0;
-    const uint64_t* parts = nullptr;   // partial sums of `cur`, `group` consecutive ones per block of this stage
-    uint32_t n_parts = 0;
-    bool done = false;
-    hipStream_t tail_stream = S;              // where the last kernels of the proof run (the overlapped plan ends on its fold stream)
+    ProofRun p;
+    ZK_TRY(proof_setup(c, n, overlap, h_claimed_sum, d_claimed_sum, slot, lane, p));
+    hipStream_t tail_stream = p.S;            // where the last kernels of the proof run (the overlapped plan ends on its fold stream)
     if (overlap) {
-        const uint32_t g = n_vars - 8, k2 = overlapped_k2(n), k1 = g - k2;
-        const uint64_t* fine = d_block_sums;
-        if (!fine || log_blocks != g) {             // poly_sum() was not called (or with another granularity)
-            // three or more proofs in flight: this streaming pass belongs onto the caller's stream like every other one (below); the
-            // serial stream follows it
-            const bool on_callers = lane >= 0 && in_flight >= 3;
-            ZK_TRY(launch_fine_sums(c, d_evals, n, g, d_fine, nullptr, on_callers ? c->stream : S));
-            if (on_callers) {
-                ZK_HIP(c, hipEventRecord(c->lanes[lane].begin_ev.get(), c->stream));
-                ZK_HIP(c, hipStreamWaitEvent(S, c->lanes[lane].begin_ev.get(), 0));
-            }
-            fine = d_fine;
-        }
-        // the coarse sums poly_sum() left for this table (the newest ring entry that names its fine sums), or our own
-        int cs = -1;
-        for (int q = 1; q <= zkhip_ctx::COARSE_RING && cs < 0; ++q) {
-            const int e = (c->coarse_next - q + 2 * zkhip_ctx::COARSE_RING) % zkhip_ctx::COARSE_RING;
-            if (fine == d_block_sums && c->coarse_of[e] == fine && c->coarse_n[e] == n && c->coarse_k1[e] == k1) cs = e;
-        }
-        if (cs < 0) {
-            ZK_TRY(c->next_coarse(&cs));
-            ProfScope ps(c, "coarse_sums", 0.0, S);
-            hipLaunchKernelGGL(group_sums_wg_kernel, dim3(1u << k1), dim3(MLE_BLOCK), 0, S, fine, 1u << k2, (uint64_t*)nullptr, (uint64_t*)c->d_coarse[cs].get());
-        }
-        const uint64_t* coarse = (const uint64_t*)c->d_coarse[cs].get();
-        c->coarse_of[cs] = nullptr;                 // the entry belongs to this proof from here on:
-        c->coarse_owner[cs] = slot + 1;             // the ring skips it until the proof has been collected (sumcheck_collect / prove_end)
-        SmallArgs a = {};
-        a.src = coarse; a.group = 0; a.canon = 1; a.log_n = k1; a.n_rounds = k1; a.round0 = 0; a.first = first; a.claimed = claimed;
-        a.d_claimed = d_claimed_sum; a.weights_out = d_w; a.final_out = nullptr;
-        ZK_TRY(launch_small(c, a, st, d_rp, d_ch, 0, S));
-        first = 0;
-        // fork: the big fold on the fold stream next to rounds k1+1 .. g.  The serial kernel of those rounds asks for
-        // (nearly) a whole CU's LDS, so no fold workgroup shares its CU (beside 8+ fold waves per SIMD the transcript
-        // wave ran at half speed)
-        // The fork comes BEHIND the small fold: the serial kernel (next in this queue) and the big fold (another queue, behind
-        // an event) then become ready together and the serial kernel's single workgroup is placed first.  Forked before
-        // the small fold, the big fold filled every CU first and the serial kernel waited for one to drain (~60 us).
-        uint32_t ny = 0;
-        ZK_TRY(launch_blockfold(c, S, fine, 1u << k2, k1, d_w, d_p1, &ny));
-        ZK_HIP(c, hipEventRecord(fork_ev, S));
-        SmallArgs b = {};
-        b.src = d_p1; b.group = ny; b.stride = 1u << k2; b.canon = 1; b.log_n = k2; b.n_rounds = k2; b.round0 = k1; b.first = 0;
-        b.weights_out = d_w2; b.final_out = nullptr;
-        if (lane >= 0 && in_flight < 3) { ZK_TRY(c->ensure_lane_fold(lane)); F = c->lanes[lane].fold; }
-        if (lane >= 0 && in_flight >= 3) {
-            // Three or more proofs in flight: the streaming passes of ALL of them on ONE stream, the caller's -- where poly_sum() puts the sums
-            // passes already.  The big fold and what follows it are enqueued LATER (zkhip_ctx::deferred), behind the sums passes of the next
-            // one to three tables, so that the caller's stream never stands waiting for this proof's first rounds; the serial kernel of
-            // rounds k1+1 .. g goes out now, the last stage follows the fold on the serial stream.  Measured at 2^24 (profiles/r06/NOTES.md
-            // section 7): 0.207 ms per proof with eight in flight against 0.233 with a fold stream per lane.
-            ZK_TRY(launch_small(c, b, st, d_rp, d_ch, 156 * 1024, S));
-            hipEvent_t fold_ev = serial_ev;
-            c->deferred_rc[slot] = ZKHIP_OK;
-            c->deferred.emplace_back(slot, [=]() -> int {
-                uint32_t np2 = 0, ny2 = 0;
-                ZK_HIP(c, hipStreamWaitEvent(c->stream, fork_ev, 0));
-                ZK_TRY(launch_multifold(c, c->stream, d_evals, n, k1, d_w, tabA, partA, &np2));
-                ZK_HIP(c, hipEventRecord(fold_ev, c->stream));
-                ZK_HIP(c, hipStreamWaitEvent(S, fold_ev, 0));
-                ZK_TRY(launch_blockfold(c, S, tabA, 256, k2, d_w2, d_p2, &ny2));
-                SmallArgs t = {};
-                t.src = d_p2; t.group = ny2; t.stride = 256; t.canon = 1; t.log_n = 8; t.n_rounds = 8; t.round0 = g; t.first = 0;
-                t.weights_out = nullptr; t.final_out = d_fin; t.host_delta = host_delta;
-                ZK_TRY(launch_small(c, t, st, d_rp, d_ch, 0, S));
-                ZK_HIP(c, hipEventRecord(c->proof_ev[slot].get(), S));
-                return ZKHIP_OK;
-            });
-            // how many second halves stay back: enough sums passes in front of a fold that its proof's first rounds are over when its turn
-            // comes (1-3 tables), few enough that the host, which stops at its depth, still has passes queued (depth 3 / 4: 1, 5: 2, 6+: 3)
-            // (a second half that cannot be enqueued is its OWN proof's failure -- recorded in deferred_rc, reported by that proof's prove_end --
-            // not this proof's: this one's second half is in the queue now and the ticket must reach the caller)
-            (void)c->flush_deferred((size_t)std::min(3, std::max(1, in_flight - 3)));
-            return ZKHIP_OK;
-        }
-        ZK_HIP(c, hipStreamWaitEvent(F, fork_ev, 0));
-        ZK_TRY(launch_multifold(c, F, d_evals, n, k1, d_w, tabA, partA, &n_parts));
-        ZK_TRY(launch_small(c, b, st, d_rp, d_ch, 156 * 1024, S));
-        // join ON THE FOLD STREAM: the serial kernel ends well before the big fold, so its event is long set when the fold
-        // ends and the last stage follows the fold in stream order (joining on the caller's stream left the chip idle for the
-        // ~13 us a cross-stream dependency takes to resolve); the proof is copied from there too
-        ZK_HIP(c, hipEventRecord(serial_ev, S));
-        ZK_HIP(c, hipStreamWaitEvent(F, serial_ev, 0));
-        tail_stream = F;
-        round = g;
-        ZK_TRY(launch_blockfold(c, tail_stream, tabA, 256, k2, d_w2, d_p2, &ny));       // 2^(8 + k2) entries -> 2^8, the last 8 rounds
-        SmallArgs t = {};
-        t.src = d_p2; t.group = ny; t.stride = 256; t.canon = 1; t.log_n = 8; t.n_rounds = 8; t.round0 = round; t.first = 0;
-        t.weights_out = nullptr; t.final_out = d_fin; t.host_delta = host_delta;
-        ZK_TRY(launch_small(c, t, st, d_rp, d_ch, 0, tail_stream));
-        done = true;
-    }
-    while (!done && stage_k(cn) != 0) {
-        const uint32_t k = stage_k(cn);
-        const size_t m = cn >> k;
-        SmallArgs a = {};
-        if (stage == 0 && d_block_sums && log_blocks >= k && log_blocks <= (uint32_t)MF_CAP_LOGK) {   // poly_sum() already streamed the table once
-            a.src = d_block_sums;
-            a.group = 1u << (log_blocks - k);
-        } else if (stage == 0) {
-            const uint32_t chunk = (uint32_t)std::min<size_t>(m, 4096);   // m >= 256 here
-            ProfScope ps(c, "chunk_sums", 32.0 * (double)cn, S);
-            hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)(cn / chunk)), dim3(MLE_BLOCK), 0, S, cur, chunk, partA);
-            a.src = partA;
-            a.group = (uint32_t)(m / chunk);
-        } else {
-            a.src = parts;
-            a.group = (uint32_t)(n_parts >> k);
-        }
-        a.log_n = k; a.n_rounds = k; a.round0 = round; a.first = first; a.claimed = claimed; a.d_claimed = d_claimed_sum;
-        a.weights_out = d_w; a.final_out = nullptr;
-        ZK_TRY(launch_small(c, a, st, d_rp, d_ch, 0, S));
-        first = 0;
-        uint64_t* dst = (stage & 1) ? tabB : tabA;
-        uint64_t* pdst = (stage & 1) ? partB : partA;
-        ZK_TRY(launch_multifold(c, S, cur, cn, k, d_w, dst, pdst, &n_parts));
-        parts = pdst;
-        cur = dst;
-        cn = m;
-        round += k;
-        ++stage;
-    }
-    if (!done) {
-        SmallArgs a = {};
-        a.src = cur; a.group = 0; a.log_n = log2_exact(cn); a.n_rounds = a.log_n; a.round0 = round; a.first = first;
-        a.claimed = claimed; a.d_claimed = d_claimed_sum; a.weights_out = nullptr; a.final_out = d_fin; a.host_delta = host_delta;
-        ZK_TRY(launch_small(c, a, st, d_rp, d_ch, 0, S));
+        ZK_TRY(proof_overlapped(c, p, d_evals, n, d_block_sums, log_blocks, slot, lane, in_flight, &tail_stream));
+        if (!tail_stream) return ZKHIP_OK;
+    } else {
+        ZK_TRY(proof_stages(c, p, d_evals, n, d_block_sums, log_blocks));
     }
     // results -> host: written by the last kernel into the pinned slot (no copy launch); the collector polls the event behind it
     // the event the collector polls; the caller's stream stays ordered behind the proof (the next call reuses the scratch)
@@ -995,10 +1040,10 @@ struct zkhip_sc_state {
     // overlapped stage (zkhip_sc_overlap_*): scratch inside B -- fine sums, fold weights of both halves, partial tables, local table
     uint32_t ov_k1 = 0, ov_k2 = 0, ov_ny1 = 0, ov_phase = 0;
     uint64_t* ov_fine() { return B; }
-    uint64_t* ov_w1() { return B + 4 * (size_t)65536; }
+    uint64_t* ov_w1() { return B + 4 * SC_FINE_ENTRIES; }
     uint64_t* ov_w2() { return ov_w1() + 4 * ((size_t)1 << TREE_MAX_LOG); }
     uint64_t* ov_p2() { return ov_w2() + 4 * ((size_t)1 << TREE_MAX_LOG); }      // <= 32 x 256
-    uint64_t* ov_loc() { return ov_p2() + 4 * (size_t)32 * 256; }                // 256
+    uint64_t* ov_loc() { return ov_p2() + 4 * SC_P2_ENTRIES; }                   // 256
     uint64_t* sw() { return stage_buf; }
     uint64_t* spx() { return stage_buf + 4 * ((size_t)1 << MF_CAP_LOGK); }
     uint64_t* spy() { return spx() + 4 * stage_parts_cap; }
@@ -1086,14 +1131,9 @@ extern "C" int zkhip_sc_stage_block_sums(zkhip_sc_state* st, uint64_t* d_out) {
     const uint32_t k = st->stage_k_cur;
     const size_t m = st->cn >> k;
     if (st->stage_idx == 0) {
-        const uint32_t chunk = (uint32_t)std::min<size_t>(m, 4096);
-        if (chunk >= (uint32_t)MLE_BLOCK) {
-            ProfScope ps(c, "chunk_sums", 32.0 * (double)st->cn);
-            hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)(st->cn / chunk)), dim3(MLE_BLOCK), 0, c->stream, st->cur, chunk, st->spx());
-            hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, st->spx(), (uint32_t)(m / chunk), 1u << k, st->sbs());
-        } else {
-            hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, st->cur, (uint32_t)m, 1u << k, st->sbs());
-        }
+        const uint64_t* parts = nullptr;
+        const uint32_t group = launch_chunk_sums(c, c->stream, st->cur, st->cn, m, st->spx(), &parts);
+        hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, parts, group, 1u << k, st->sbs());
     } else {
         hipLaunchKernelGGL(group_sums_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, st->parts, st->n_parts >> k, 1u << k, st->sbs());
     }
@@ -1106,12 +1146,8 @@ extern "C" int zkhip_sc_stage_absorb(zkhip_sc_state* st, const uint64_t* d_gathe
     zkhip_ctx* c = st->c;
     ZK_TRY(c->activate());
     const uint32_t k = st->stage_k_cur;
-    SmallArgs a = {};
-    a.src = d_gathered; a.group = world; a.stride = 1u << k;
-    a.log_n = k; a.n_rounds = k; a.round0 = st->round;
-    a.first = st->round == 0 ? 1u : 0u;
-    if (a.first && h_claimed) { std::memcpy(a.claimed.v, h_claimed, 32); a.first = 2; }
-    a.weights_out = st->sw(); a.final_out = nullptr;
+    SmallArgs a = small_rounds(d_gathered, world, 1u << k, 0, k, k, st->round, st->sw());
+    small_open(a, st->round == 0, h_claimed, nullptr);
     ZK_TRY(launch_small(c, a, st->dev(), st->rp(), st->ch()));
     st->round += k;
     return ZKHIP_OK;
@@ -1186,10 +1222,8 @@ extern "C" int zkhip_sc_overlap_rounds1(zkhip_sc_state* st, const uint64_t* d_ga
     ZK_TRY(c->activate());
     ZK_TRY(c->ensure_fold_stream());
     const uint32_t k1 = st->ov_k1, k2 = st->ov_k2;
-    SmallArgs a = {};
-    a.src = d_gathered; a.group = world; a.stride = 1u << k1; a.canon = 1; a.log_n = k1; a.n_rounds = k1; a.round0 = 0; a.first = 1;
-    if (h_claimed) { std::memcpy(a.claimed.v, h_claimed, 32); a.first = 2; }
-    a.weights_out = st->ov_w1(); a.final_out = nullptr;
+    SmallArgs a = small_rounds(d_gathered, world, 1u << k1, 1, k1, k1, 0, st->ov_w1());
+    small_open(a, true, h_claimed, nullptr);
     ZK_TRY(launch_small(c, a, st->dev(), st->rp(), st->ch()));
     uint32_t ny = 0, n_parts = 0;
     ZK_TRY(launch_blockfold(c, c->stream, st->ov_fine(), 1u << k2, k1, st->ov_w1(), d_mid, &ny));
@@ -1209,9 +1243,7 @@ extern "C" int zkhip_sc_overlap_rounds2(zkhip_sc_state* st, const uint64_t* d_ga
     zkhip_ctx* c = st->c;
     ZK_TRY(c->activate());
     const uint32_t k1 = st->ov_k1, k2 = st->ov_k2;
-    SmallArgs b = {};
-    b.src = d_gathered; b.group = world * st->ov_ny1; b.stride = 1u << k2; b.canon = 1; b.log_n = k2; b.n_rounds = k2; b.round0 = k1; b.first = 0;
-    b.weights_out = st->ov_w2(); b.final_out = nullptr;
+    const SmallArgs b = small_rounds(d_gathered, world * st->ov_ny1, 1u << k2, 1, k2, k2, k1, st->ov_w2());
     // no exclusive-CU request here (cf. sumcheck_enqueue): the exchange puts this launch tens of microseconds behind the fold's
     // start, the chip is full by then and a whole free CU only appears when the fold drains
     ZK_TRY(launch_small(c, b, st->dev(), st->rp(), st->ch()));
@@ -1255,11 +1287,11 @@ extern "C" int zkhip_sc_absorb(zkhip_sc_state* st, const uint64_t* d_gathered, u
     if (st->round >= ZK_MAX_ROUNDS) return ZKHIP_ERR_SHAPE;
     zkhip_ctx* c = st->c;
     ZK_TRY(c->activate());
-    FrArg claimed = {}, z = {};
-    uint32_t first = st->round == 0 ? 1 : 0;
-    if (first && h_claimed) { std::memcpy(claimed.v, h_claimed, 32); first = 2; }
+    FrArg z = {};
+    SmallArgs o = {};                           // (carries `first` and the claimed sum only)
+    small_open(o, st->round == 0, h_claimed, nullptr);
     hipLaunchKernelGGL(sumcheck_round_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, d_gathered, world, st->dev(), st->round,
-                       first, claimed, 0u, z, z, st->rp(), st->ch());
+                       o.first, o.claimed, 0u, z, z, st->rp(), st->ch());
     ZK_HIP(c, hipGetLastError());
     st->round++;
     return ZKHIP_OK;
@@ -1297,27 +1329,25 @@ extern "C" int zkhip_sc_tail(zkhip_sc_state* st, const uint64_t* d_values, uint3
     if (m == 1) return ZKHIP_OK;
     zkhip_ctx* c = st->c;
     ZK_TRY(c->activate());
-    uint32_t first = st->round == 0 ? 1u : 0u;
-    FrArg claimed = {};
-    if (first && h_claimed) { std::memcpy(claimed.v, h_claimed, 32); first = 2; }
     if (m > (1u << TREE_MAX_LOG)) {
         if (st->round >= ZK_MAX_ROUNDS) return ZKHIP_ERR_SHAPE;
         FrArg z = {};
+        SmallArgs o = {};                       // (carries `first` and the claimed sum only)
+        small_open(o, st->round == 0, h_claimed, nullptr);
         const int grid = mle_grid((m + 3) / 4);
         uint64_t* folded = st->partials() + 64;              // m/2 entries behind the two records of half sums
         hipLaunchKernelGGL(half_sums_kernel, dim3(grid), dim3(MLE_BLOCK), 0, c->stream, d_values, (size_t)m, st->partials());
         hipLaunchKernelGGL(sumcheck_round_kernel, dim3(1), dim3(MLE_BLOCK), 0, c->stream, st->partials(), (uint32_t)grid, st->dev(), st->round,
-                           first, claimed, 0u, z, z, st->rp(), st->ch());
+                           o.first, o.claimed, 0u, z, z, st->rp(), st->ch());
         ZK_TRY(launch_fold(c, d_values, m, st->ch() + 4 * st->round, nullptr, 0, folded, false, nullptr, nullptr));
         st->round++;
-        first = 0;
         d_values = folded;
         m >>= 1;
     }
-    SmallArgs a = {};
-    a.src = d_values; a.group = 0; a.stride = 0; a.log_n = log2_exact(m); a.n_rounds = a.log_n; a.round0 = st->round;
-    a.first = first; a.claimed = claimed;
-    a.weights_out = nullptr; a.final_out = st->fin();
+    const uint32_t lg = log2_exact(m);
+    SmallArgs a = small_rounds(d_values, 0, 0, 0, lg, lg, st->round, nullptr);
+    small_open(a, st->round == 0, h_claimed, nullptr);
+    a.final_out = st->fin();
     ZK_TRY(launch_small(c, a, st->dev(), st->rp(), st->ch()));
     st->round += a.log_n;
     return ZKHIP_OK;
