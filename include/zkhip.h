@@ -726,6 +726,34 @@ int zkhip_plonk_verify(zkhip_ctx *ctx, size_t n, const uint64_t *h_vk_xy, const 
                        const uint8_t *h_points_inf, const uint64_t *h_evals, const uint64_t *d_public, const uint64_t *d_g2_xy,
                        const uint8_t *d_g2_inf, size_t n_g2, uint8_t *h_ok);
 
+/* ---- PLONK: a batch of proofs of one circuit in one call (verifier.rs:62-172 per proof) ------------------------------------------
+ * The layouts are the PLONK block's above, one proof after the other.
+ *
+ * zkhip_plonk_vkey_create: what the proofs of one circuit share, made resident.  h_vk_xy / h_vk_inf: the eight commitments of vpi in
+ *   the order above; each finite one is checked once for curve and subgroup -> ZKHIP_ERR_ARG.  d_g2_xy / d_g2_inf: the SRS's G2 half,
+ *   n_g2 < 2 -> ZKHIP_ERR_INDEX (powers_of_tau_in_g2[1], verifier.rs:34); the buffers are read during the call only.  n: a power of two,
+ *   4 <= n <= 2^28, else ZKHIP_ERR_SHAPE.  The handle owns the commitments, the prepared lines of [G2, powers_of_tau_in_g2[1]] (what
+ *   zkhip_kzg_prepare(d_g2_xy + 24, d_g2_inf + 1, 1, ..) writes) and the table w^0 .. w^(n-1) of the group of order n.  Destroy the key
+ *   before its context.
+ * zkhip_plonk_verify_batch: h_ok[b] = 1 iff PlonkVerifier::verify accepts proof b, 0 if it does not, 2 if proof b is malformed -- a
+ *   finite point off the curve, outside the subgroup or with an unreduced coordinate, or an evaluation that is not a reduced field
+ *   element; then the call returns ZKHIP_ERR_ARG, and every other verdict is what it would be without that proof.  A point whose flag
+ *   is set is the identity.  h_public_ptrs: a HOST array of `batch` DEVICE columns in evaluation form, n values each; entries may
+ *   repeat; a NULL entry -> ZKHIP_ERR_ARG.  h_pair_xy / h_pair_inf (both or neither): per proof the affine G1 arguments of the two
+ *   pairings, `right` then `left` as the reference names them (left itself, not the negated point of the Miller loop); an identity
+ *   has its flag set and zero coordinates.  batch = 0 returns ZKHIP_OK and touches nothing; batch > 65535 -> ZKHIP_ERR_SHAPE.
+ *   Host work per proof: the Merlin transcript and the verifier's scalar algebra.  Device work: PI(zeta_b) of every proof from its
+ *   column by the barycentric sum over the key's table, one lane per (proof, term) for the twenty G1 terms, one lane per proof for the
+ *   two sums, then e(right, G2) e(-left, tau G2) == 1: two Miller loops, one product and ONE final exponentiation per proof.  One
+ *   synchronisation, at the end.  The workspace is the context's: no split-phase session or commit may be in flight (ZKHIP_ERR_BUSY). */
+typedef struct zkhip_plonk_vkey zkhip_plonk_vkey;
+int zkhip_plonk_vkey_create(zkhip_ctx *ctx, size_t n, const uint64_t *h_vk_xy, const uint8_t *h_vk_inf, const uint64_t *d_g2_xy,
+                            const uint8_t *d_g2_inf, size_t n_g2, zkhip_plonk_vkey **out);
+int zkhip_plonk_vkey_destroy(zkhip_plonk_vkey *vk);
+int zkhip_plonk_verify_batch(zkhip_plonk_vkey *vk, size_t batch, const uint64_t *h_points_xy, const uint8_t *h_points_inf,
+                             const uint64_t *h_evals, const uint64_t *const *h_public_ptrs, uint8_t *h_ok, uint64_t *h_pair_xy,
+                             uint8_t *h_pair_inf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 
 #include "ctx.hpp"
 #include "pairing.hpp"
+#include "pairing_internal.hpp"
 #include "srs_kernels.hpp"
 
 using namespace zk;
@@ -199,13 +200,19 @@ __global__ __launch_bounds__(PAIR_BLOCK) void kzg_combine_kernel(const uint64_t*
 int pairing_groups(zkhip_ctx* c, const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
                    const uint64_t* prep, size_t q_mod, size_t n_groups, size_t m, uint64_t* f, uint64_t* out_gt, uint8_t* out_ok) {
     const size_t n_pairs = n_groups * m;
-    hipLaunchKernelGGL(miller_loop_kernel, dim3(pair_grid(n_pairs)), dim3(PAIR_BLOCK), 0, c->stream, p_xy, p_inf, q_xy, q_inf, prep,
-                       n_pairs, q_mod, f);
+    {
+        ProfScope ps(c, "pairing_miller_loops", 576.0 * (double)n_pairs);
+        hipLaunchKernelGGL(miller_loop_kernel, dim3(pair_grid(n_pairs)), dim3(PAIR_BLOCK), 0, c->stream, p_xy, p_inf, q_xy, q_inf, prep,
+                           n_pairs, q_mod, f);
+    }
     for (size_t stride = 1; stride < m; stride *= 2) {
         const size_t per = (m + 2 * stride - 1) / (2 * stride);
         hipLaunchKernelGGL(f12_product_kernel, dim3(pair_grid(n_groups * per)), dim3(PAIR_BLOCK), 0, c->stream, f, n_groups, m, stride);
     }
-    hipLaunchKernelGGL(final_exp_kernel, dim3(pair_grid(n_groups)), dim3(PAIR_BLOCK), 0, c->stream, f, n_groups, m, out_gt, out_ok);
+    {
+        ProfScope ps(c, "pairing_final_exp", 576.0 * (double)n_groups);
+        hipLaunchKernelGGL(final_exp_kernel, dim3(pair_grid(n_groups)), dim3(PAIR_BLOCK), 0, c->stream, f, n_groups, m, out_gt, out_ok);
+    }
     ZK_HIP(c, hipGetLastError());
     return ZKHIP_OK;
 }
@@ -280,6 +287,16 @@ int verify_batch(zkhip_ctx* c, size_t batch, size_t n, const uint64_t* h_commits
 }
 
 }  // namespace
+
+// ---- pairing_internal.hpp: the three helpers above for plonk.hip ------------------------------------------------------------------------
+int zk_pairing_groups(zkhip_ctx* c, const uint64_t* d_p_xy, const uint8_t* d_p_inf, const uint64_t* d_prep, size_t q_mod, size_t n_groups, size_t m,
+                      uint64_t* d_f, uint8_t* d_out_ok) {
+    return pairing_groups(c, d_p_xy, d_p_inf, nullptr, nullptr, d_prep, q_mod, n_groups, m, d_f, nullptr, d_out_ok);
+}
+int zk_pairing_prepare_kzg(zkhip_ctx* c, const uint64_t* d_xy, const uint8_t* d_inf, size_t n, uint64_t* d_prep, uint8_t* d_bad) {
+    return prepare(c, d_xy, d_inf, n, 1, d_prep, d_bad);
+}
+int zk_pairing_any_flag(zkhip_ctx* c, const uint8_t* d_flags, size_t n, bool* any) { return any_flag(c, d_flags, n, any); }
 
 extern "C" int zkhip_srs_multilinear_g2(zkhip_ctx* c, const uint64_t* h_tau, uint32_t n_vars, uint64_t* d_out_xy, uint8_t* d_out_inf) {
     if (!c || (n_vars && (!h_tau || !d_out_xy || !d_out_inf))) return ZKHIP_ERR_ARG;

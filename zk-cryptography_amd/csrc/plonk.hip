@@ -16,7 +16,10 @@
 #include "host_fr.hpp"
 #include "host_g1.hpp"
 #include "host_util.hpp"
+#include "pairing_internal.hpp"
 #include "plonk_kernels.hpp"
+#include "plonk_scalars.hpp"
+#include "plonk_verify_kernels.hpp"
 #include "tunables.hpp"
 
 using namespace zk;
@@ -30,14 +33,11 @@ using zkhost::fr_sub;
 
 inline HFr h_load(const uint64_t* p) { HFr r; std::memcpy(r.l, p, 32); return r; }
 inline FrArg fa(const HFr& a) { FrArg r; std::memcpy(r.v, a.l, 32); return r; }
-inline bool h_is_zero(const HFr& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
 inline bool h_eq(const HFr& a, const HFr& b) { return std::memcmp(a.l, b.l, 32) == 0; }
-inline HFr h_neg(const HFr& a) { return fr_sub(zkhost::fr_zero(), a); }
-inline HFr h_pow(HFr a, uint64_t e) {
-    HFr acc = zkhost::fr_one();
-    for (; e; e >>= 1) { if (e & 1) acc = fr_mul(acc, a); a = fr_mul(a, a); }
-    return acc;
-}
+using zkplonk::h_is_zero;      // plonk_scalars.hpp: shared with the verifier's scalar algebra
+using zkplonk::h_neg;
+using zkplonk::h_pow;
+using zkplonk::l1_at;
 
 // ---- MerlinTranscript (transcripts/merlin/src/lib.rs:11-49) and PlonkRoundTranscript (plonk/src/protocol/transcript.rs) ----------
 // canonical integer of a Montgomery Fq element in decimal, leading zeros trimmed (ark-ff 0.4.2 Display for Fp: zero prints as "")
@@ -242,13 +242,6 @@ int read_flags(zkhip_ctx* c, const Work& w, bool* any) {
     *any = false;
     for (int i = 0; i < PLONK_FLAGS; ++i) *any = *any || h[i] != 0;
     return ZKHIP_OK;
-}
-
-// L_1(zeta) = (zeta^n - 1) / (n (zeta - 1)); at zeta = 1 the polynomial with all coefficients 1/n gives 1
-HFr l1_at(const HFr& zeta, const HFr& zh_zeta, uint64_t n) {
-    const HFr d = fr_sub(zeta, zkhost::fr_one());
-    if (h_is_zero(d)) return zkhost::fr_one();
-    return fr_mul(zh_zeta, zkhost::fr_inv(fr_mul(zkhost::fr_from_u64(n), d)));
 }
 
 void absorb_challenges_from_proof(const uint64_t* xy, const uint8_t* inf, const uint64_t* evals, HFr* ch) {   // protocol/utils.rs:56-96
@@ -558,7 +551,7 @@ extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_x
     ZK_TRY(c->activate());
     HFr ch[N_CHALLENGES];
     absorb_challenges_from_proof(h_points_xy, h_points_inf, h_evals, ch);
-    const HFr beta = ch[C_BETA], gamma = ch[C_GAMMA], alpha = ch[C_ALPHA], zeta = ch[C_ZETA], nu = ch[C_NU], mu = ch[C_MU];
+    const HFr zeta = ch[C_ZETA], mu = ch[C_MU];
     // PI(zeta): to_coefficient_poly().evaluate(zeta) on the device
     DevMem tmp;
     const size_t prep_bytes = zkhip_g2_prepared_bytes(2);
@@ -571,18 +564,10 @@ extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_x
     ZK_TRY(zkhip_dense_evaluate(c, (const uint64_t*)(base + o_pi), n, zeta.l, piz.l));
     HFr e[N_EVALS];
     for (int j = 0; j < N_EVALS; ++j) e[j] = h_load(h_evals + 4 * j);
-    const HFr az = e[E_A], bz = e[E_B], cz = e[E_C], s1z = e[E_S1], s2z = e[E_S2], zwz = e[E_ZW];
-    const HFr a2 = fr_mul(alpha, alpha), zn = h_pow(zeta, (uint64_t)n), zh = fr_sub(zn, zkhost::fr_one());
-    const HFr l1z = l1_at(zeta, zh, (uint64_t)n);
-    const HFr fa1 = fr_add(fr_add(az, fr_mul(s1z, beta)), gamma), fb1 = fr_add(fr_add(bz, fr_mul(s2z, beta)), gamma);
-    const HFr r0 = fr_sub(fr_sub(piz, fr_mul(l1z, a2)), fr_mul(alpha, fr_mul(fr_mul(fa1, fb1), fr_mul(fr_add(cz, gamma), zwz))));   // :82-88
-    const HFr bzeta = fr_mul(beta, zeta);
-    const HFr k_acc = fr_add(fr_add(fr_mul(fr_mul(fr_mul(fr_add(fr_add(az, bzeta), gamma), fr_add(fr_add(bz, fr_add(bzeta, bzeta)), gamma)),
-                                                  fr_add(fr_add(cz, fr_add(bzeta, fr_add(bzeta, bzeta))), gamma)), alpha), fr_mul(l1z, a2)), mu);
-    const HFr k_s3 = fr_mul(fr_mul(fr_mul(fa1, fb1), fr_mul(alpha, beta)), zwz);
-    HFr nup[6];
-    nup[0] = zkhost::fr_one();
-    for (int j = 1; j < 6; ++j) nup[j] = fr_mul(nup[j - 1], nu);
+    const HFr az = e[E_A], bz = e[E_B], cz = e[E_C];
+    const zkplonk::VerifierScalars sc = zkplonk::verifier_scalars((uint64_t)n, ch, e, piz);     // plonk_scalars.hpp
+    const HFr zn = sc.zn, zh = sc.zh, k_acc = sc.k_acc, k_s3 = sc.k_s3, es = sc.es;
+    const HFr* nup = sc.nup;
     auto pt = [&](const uint64_t* xy, const uint8_t* inf, int i) { return zkhost::xyzz_from_affine(xy + 12 * i, inf[i] != 0); };
     auto P = [&](int i) { return pt(h_points_xy, h_points_inf, i); };
     auto V = [&](int i) { return pt(h_vk_xy, h_vk_inf, i); };       // q_m, q_l, q_r, q_o, q_c, sigma_1, sigma_2, sigma_3
@@ -594,9 +579,6 @@ extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_x
     d1 = xyzz_add(d1, g1_mul(t_comb, h_neg(zh)));                                                                                               // :123-126
     Xyzz f1 = xyzz_add(d1, xyzz_add(xyzz_add(g1_mul(P(P_AS), nup[1]), g1_mul(P(P_BS), nup[2])),
                                     xyzz_add(g1_mul(P(P_CS), nup[3]), xyzz_add(g1_mul(V(5), nup[4]), g1_mul(V(6), nup[5])))));                    // :134-139
-    HFr es = fr_sub(fr_mul(mu, zwz), r0);
-    const HFr opened[5] = {az, bz, cz, s1z, s2z};
-    for (int j = 0; j < 5; ++j) es = fr_add(es, fr_mul(nup[j + 1], opened[j]));
     const Xyzz e1_neg = g1_mul(g1_generator_host(), h_neg(es));                                                                                // :141-150
     const Xyzz left = xyzz_add(P(P_WZ), g1_mul(P(P_WZW), mu));                                                                                 // :157-160
     const Xyzz right = xyzz_add(xyzz_add(g1_mul(P(P_WZ), zeta), g1_mul(P(P_WZW), fr_mul(fr_mul(wn, mu), zeta))), xyzz_add(f1, e1_neg));         // :162-169
@@ -615,4 +597,146 @@ extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_x
     ZK_HIP(c, hipStreamSynchronize(c->stream));
     *h_ok = std::memcmp(gt, gt + 72, 576) == 0 ? 1 : 0;            // GT has one encoding: left == right (:171)
     return ZKHIP_OK;
+}
+
+// ---- the batched verifier ---------------------------------------------------------------------------------------------------------
+static_assert(C_BETA == 0 && C_GAMMA == 1 && C_ALPHA == 2 && C_ZETA == 3 && C_NU == 4 && C_MU == 5 && E_A == 0 && E_ZW == 5,
+              "plonk_scalars.hpp indexes challenges and evaluations in the ABI's order");
+static_assert(zkplonk::VERIFY_TERMS == PV_TERMS && N_POINTS == PV_PROOF_POINTS, "one term table on both sides");
+
+// What every proof of one circuit shares: the eight commitments of vpi (validated once), the prepared lines of [G2, tau G2] and the
+// table w^0 .. w^(n-1) of the PI pass.
+struct zkhip_plonk_vkey {
+    zkhip_ctx* ctx = nullptr;
+    size_t n = 0;
+    HFr w_n, n_inv;
+    DevMem vk_xy, vk_inf, prep, omega;
+};
+
+extern "C" int zkhip_plonk_vkey_destroy(zkhip_plonk_vkey* vk) {
+    if (!vk) return ZKHIP_OK;
+    if (vk->ctx) {
+        (void)vk->ctx->activate();
+        vk->ctx->drain_streams();       // nothing of this key's may still be read by a kernel
+    }
+    delete vk;
+    return ZKHIP_OK;
+}
+
+extern "C" int zkhip_plonk_vkey_create(zkhip_ctx* c, size_t n, const uint64_t* h_vk_xy, const uint8_t* h_vk_inf, const uint64_t* d_g2_xy,
+                                       const uint8_t* d_g2_inf, size_t n_g2, zkhip_plonk_vkey** out) {
+    if (!c || !h_vk_xy || !h_vk_inf || !d_g2_xy || !d_g2_inf || !out) return ZKHIP_ERR_ARG;
+    *out = nullptr;
+    if (!is_pow2(n) || n < 4 || log2_exact(n) > 28) return ZKHIP_ERR_SHAPE;
+    if (n_g2 < 2) return ZKHIP_ERR_INDEX;                          // powers_of_tau_in_g2[1] (verifier.rs:34)
+    ZK_TRY(c->activate());
+    std::unique_ptr<zkhip_plonk_vkey> k(new (std::nothrow) zkhip_plonk_vkey());
+    if (!k) return ZKHIP_ERR_NOMEM;
+    k->ctx = c; k->n = n;
+    if (dev_alloc(k->vk_xy, PV_VK_POINTS * 96) != hipSuccess || dev_alloc(k->vk_inf, 256) != hipSuccess ||
+        dev_alloc(k->prep, zkhip_g2_prepared_bytes(2)) != hipSuccess || dev_alloc(k->omega, n * 32) != hipSuccess)
+        return ZKHIP_ERR_NOMEM;
+    HFr t1;
+    ZK_TRY(zkhip_domain_params((uint64_t)n, k->w_n.l, t1.l, k->n_inv.l));
+    k->n_inv = zkhost::fr_inv(zkhost::fr_from_u64((uint64_t)n));
+    uint8_t* d_bad = (uint8_t*)k->vk_inf.get() + 64;               // scratch beside the eight flags
+    ZK_HIP(c, hipMemcpyAsync(k->vk_xy.get(), h_vk_xy, PV_VK_POINTS * 96, hipMemcpyHostToDevice, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(k->vk_inf.get(), h_vk_inf, PV_VK_POINTS, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(plonk_points_check_kernel, dim3(1), dim3(PV_BLOCK), 0, c->stream, (const uint64_t*)k->vk_xy.get(),
+                       (const uint8_t*)k->vk_inf.get(), (size_t)PV_VK_POINTS, d_bad);
+    ZK_HIP(c, hipGetLastError());
+    bool any = false;
+    ZK_TRY(zk_pairing_any_flag(c, d_bad, PV_VK_POINTS, &any));
+    if (any) return ZKHIP_ERR_ARG;                                 // a commitment off the curve or outside the subgroup
+    ZK_TRY(zk_pairing_prepare_kzg(c, d_g2_xy + 24, d_g2_inf + 1, 1, (uint64_t*)k->prep.get(), d_bad));
+    ZK_TRY(powers(c, k->w_n, zkhost::fr_one(), n, (uint64_t*)k->omega.get()));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    *out = k.release();
+    return ZKHIP_OK;
+}
+
+// PlonkVerifier::verify (verifier.rs:62-172) of `batch` proofs of one circuit: h_ok[b] = 1 verifies, 0 does not, 2 malformed
+extern "C" int zkhip_plonk_verify_batch(zkhip_plonk_vkey* vk, size_t batch, const uint64_t* h_points_xy, const uint8_t* h_points_inf,
+                                        const uint64_t* h_evals, const uint64_t* const* h_public_ptrs, uint8_t* h_ok, uint64_t* h_pair_xy,
+                                        uint8_t* h_pair_inf) {
+    if (!vk) return ZKHIP_ERR_ARG;
+    if (!batch) return ZKHIP_OK;
+    if (!h_points_xy || !h_points_inf || !h_evals || !h_public_ptrs || !h_ok || (!h_pair_xy != !h_pair_inf)) return ZKHIP_ERR_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!h_public_ptrs[b]) return ZKHIP_ERR_ARG;
+    zkhip_ctx* c = vk->ctx;
+    ZK_TRY(c->activate());
+    const size_t n = vk->n, n_blocks = (n + PV_PI_ROWS - 1) / PV_PI_ROWS, nt = batch * PV_TERMS;
+    if (batch > 65535 || n_blocks > 0x7fffffffu) return ZKHIP_ERR_SHAPE;   // the PI pass puts the proofs on the grid's second axis
+    // host: challenges and the scalar table of every well-formed proof (an unreduced evaluation makes a proof malformed: zero scalars)
+    std::vector<HFr> scal(nt, zkhost::fr_zero()), zetas(batch, zkhost::fr_zero()), factors(batch, zkhost::fr_zero());
+    std::vector<uint8_t> malformed(batch, 0);
+    for (size_t b = 0; b < batch; ++b) {
+        const uint64_t* ev = h_evals + 4 * N_EVALS * b;
+        for (int e = 0; e < N_EVALS; ++e) if (zkhost::fr_geq_p(ev + 4 * e)) malformed[b] = 1;
+        if (malformed[b]) continue;
+        HFr ch[N_CHALLENGES], e[N_EVALS];
+        absorb_challenges_from_proof(h_points_xy + 12 * N_POINTS * b, h_points_inf + N_POINTS * b, ev, ch);
+        for (int j = 0; j < N_EVALS; ++j) e[j] = h_load(ev + 4 * j);
+        const zkplonk::VerifierScalars sc = zkplonk::verifier_scalars((uint64_t)n, ch, e, zkhost::fr_zero());   // es + PI(zeta): the device adds PI(zeta) to -es
+        zkplonk::verifier_term_table(sc, ch, e, vk->w_n, &scal[PV_TERMS * b]);
+        zetas[b] = ch[C_ZETA];
+        factors[b] = fr_mul(sc.zh, vk->n_inv);
+    }
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_points = carve(batch * N_POINTS * 96), o_pinf = carve(batch * N_POINTS), o_scal = carve(nt * 32), o_zeta = carve(batch * 32);
+    const size_t o_fact = carve(batch * 32), o_cols = carve(batch * 8), o_part = carve(batch * n_blocks * 32), o_hit = carve(batch * 8);
+    const size_t o_terms = carve(nt * 192), o_pxy = carve(batch * 2 * 96), o_pairinf = carve(batch * 2), o_oxy = carve(batch * 2 * 96);
+    const size_t o_oinf = carve(batch * 2), o_f = carve(batch * 2 * 576), o_bad = carve(nt), o_ok = carve(batch);
+    ZK_TRY(c->reserve_ws(off));
+    char* ws = (char*)c->ws.ptr;
+    auto up = [&](size_t o, const void* h, size_t bytes) { return hipMemcpyAsync(ws + o, h, bytes, hipMemcpyHostToDevice, c->stream); };
+    ZK_HIP(c, up(o_points, h_points_xy, batch * N_POINTS * 96));
+    ZK_HIP(c, up(o_pinf, h_points_inf, batch * N_POINTS));
+    ZK_HIP(c, up(o_scal, scal.data(), nt * 32));
+    ZK_HIP(c, up(o_zeta, zetas.data(), batch * 32));
+    ZK_HIP(c, up(o_fact, factors.data(), batch * 32));
+    ZK_HIP(c, up(o_cols, h_public_ptrs, batch * 8));
+    ZK_HIP(c, hipMemsetAsync(ws + o_hit, 0, batch * 8, c->stream));
+    const uint64_t* const* d_cols = (const uint64_t* const*)(ws + o_cols);
+    uint64_t* d_scal = (uint64_t*)(ws + o_scal);
+    uint8_t* d_bad = (uint8_t*)(ws + o_bad);
+    const unsigned per_proof_grid = (unsigned)((batch + PV_BLOCK - 1) / PV_BLOCK);
+    {
+        ProfScope ps(c, "plonk_verify_pi", 64.0 * (double)n * (double)batch);
+        hipLaunchKernelGGL(plonk_pi_kernel, dim3((unsigned)n_blocks, (unsigned)batch), dim3(PV_PI_T), 0, c->stream, d_cols, (const uint64_t*)vk->omega.get(),
+                           (const uint64_t*)(ws + o_zeta), n, (uint64_t*)(ws + o_part), (unsigned long long*)(ws + o_hit));
+        hipLaunchKernelGGL(plonk_pi_finish_kernel, dim3(per_proof_grid), dim3(PV_BLOCK), 0, c->stream, d_cols, (const uint64_t*)(ws + o_part),
+                           (const unsigned long long*)(ws + o_hit), (const uint64_t*)(ws + o_fact), batch, n_blocks, d_scal + 4 * PV_TERM_G,
+                           (size_t)PV_TERMS, (uint64_t*)nullptr);
+    }
+    {
+        ProfScope ps(c, "plonk_verify_terms", 192.0 * (double)nt);
+        hipLaunchKernelGGL(plonk_terms_kernel, dim3((unsigned)((nt + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0, c->stream, (const uint64_t*)vk->vk_xy.get(),
+                           (const uint8_t*)vk->vk_inf.get(), (const uint64_t*)(ws + o_points), (const uint8_t*)(ws + o_pinf), (const uint64_t*)d_scal, batch,
+                           (uint64_t*)(ws + o_terms), d_bad);
+    }
+    {
+        ProfScope ps(c, "plonk_verify_combine", 192.0 * (double)nt);
+        hipLaunchKernelGGL(plonk_combine_kernel, dim3(per_proof_grid), dim3(PV_BLOCK), 0, c->stream, (const uint64_t*)(ws + o_terms), (const uint8_t*)d_bad, batch,
+                           (uint64_t*)(ws + o_pxy), (uint8_t*)(ws + o_pairinf), (uint64_t*)(ws + o_oxy), (uint8_t*)(ws + o_oinf));
+    }
+    ZK_HIP(c, hipGetLastError());
+    // e(right, G2) e(-left, tau G2) == 1: two Miller loops, one product, one final exponentiation per proof
+    ZK_TRY(zk_pairing_groups(c, (const uint64_t*)(ws + o_pxy), (const uint8_t*)(ws + o_pairinf), (const uint64_t*)vk->prep.get(), 2, batch, 2,
+                             (uint64_t*)(ws + o_f), (uint8_t*)(ws + o_ok)));
+    std::vector<uint8_t> bad(nt);
+    ZK_HIP(c, hipMemcpyAsync(h_ok, ws + o_ok, batch, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipMemcpyAsync(bad.data(), d_bad, nt, hipMemcpyDeviceToHost, c->stream));
+    if (h_pair_xy) {
+        ZK_HIP(c, hipMemcpyAsync(h_pair_xy, ws + o_oxy, batch * 2 * 96, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipMemcpyAsync(h_pair_inf, ws + o_oinf, batch * 2, hipMemcpyDeviceToHost, c->stream));
+    }
+    ZK_HIP(c, hipStreamSynchronize(c->stream));                    // the call's one wait: verdicts, flags and pair points
+    bool any = false;
+    for (size_t b = 0; b < batch; ++b) {
+        for (int j = 0; j < PV_TERMS; ++j) if (bad[PV_TERMS * b + j]) malformed[b] = 1;
+        if (malformed[b]) { h_ok[b] = 2; any = true; }
+    }
+    return any ? ZKHIP_ERR_ARG : ZKHIP_OK;
 }

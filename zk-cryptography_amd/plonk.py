@@ -425,6 +425,53 @@ def _key_for(cpi, srs):
     return key
 
 
+class _VerifierKey:
+    """zkhip_plonk_vkey: the eight commitments of vpi, the prepared lines of [G2, tau G2] and the domain's powers, resident on the device"""
+
+    def __init__(self, ctx, n, vxy, vinf, srs):
+        self.ctx, self.n = ctx, n
+        self.handle = C.c_void_p()
+        st = N.lib().zkhip_plonk_vkey_create(ctx.handle, C.c_size_t(n), vxy.ctypes.data_as(_vp), vinf.ctypes.data_as(_vp),
+                                             N.ptr(srs.powers_of_tau_in_g2), N.ptr(srs.g2_inf), C.c_size_t(len(srs.powers_of_tau_in_g2)),
+                                             C.byref(self.handle))
+        if st == N.ERR_ARG:
+            raise ValueError("plonk verify: a point is off its curve or outside the prime-order subgroup")
+        N.check(st, "plonk verifier key (group_order a power of two, 4 .. 2^28)")
+        self._ref = _KeyRef(self)
+        ctx._circuits.append(self._ref)
+
+    def close(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h and self.ctx.handle:
+            N.lib().zkhip_plonk_vkey_destroy(h)
+        ref = getattr(self, "_ref", None)
+        if ref is not None and ref in self.ctx._circuits:
+            self.ctx._circuits.remove(ref)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+_VKEY_SLOTS = 4                 # verifier keys kept: a key holds group_order field elements on the device
+_vkeys = {}                     # (context, group_order, the eight commitments, the SRS's G2 half) -> _VerifierKey, oldest first
+
+
+def _vkey_for(ctx, n, vxy, vinf, srs):
+    g2 = srs.powers_of_tau_in_g2
+    tag = (id(ctx), n, vxy.tobytes(), vinf.tobytes(), g2.data_ptr(), len(g2))
+    key = _vkeys.pop(tag, None)
+    if key is None or not key.handle or key.ctx is not ctx or not ctx.handle:
+        key = _VerifierKey(ctx, n, vxy, vinf, srs)
+        key._g2 = g2                                # the tag holds its address: keep the tensor for as long as the key
+    _vkeys[tag] = key
+    while len(_vkeys) > _VKEY_SLOTS:
+        _vkeys.pop(next(iter(_vkeys))).close()
+    return key
+
+
 class VerifierPreprocessedInput:
     """protocol/primitives.rs:74-84"""
 
@@ -542,3 +589,41 @@ class PlonkVerifier:
             raise ValueError("plonk verify: a point is off its curve or outside the prime-order subgroup")
         N.check(st, "plonk verify")
         return bool(ok.value)
+
+    @staticmethod
+    def verify_batch(group_order, proofs, srs, verifier_preprocessed_input, public_input_polys):
+        """PlonkVerifier::verify of many proofs of one circuit in one call (zkhip_plonk_verify_batch) -> list[bool], proof for proof
+        what `verify` returns.  `public_input_polys`: one column for all proofs, or one per proof.  A malformed proof -- a point off
+        the curve or outside the subgroup, an evaluation that is not reduced -- raises ValueError naming its index."""
+        import torch
+        if srs.powers_of_tau_in_g2 is None:
+            raise ValueError("this TrustedSetup has no G2 half: build it with generate_srs(..., g2=True)")
+        proofs = list(proofs)
+        polys = public_input_polys
+        one_for_all = isinstance(polys, torch.Tensor) and polys.dim() == 2 or isinstance(polys, np.ndarray) and polys.ndim == 2 \
+            or (len(polys) > 0 and isinstance(polys[0], (int, np.integer)))
+        cols = [_column(polys)] * len(proofs) if one_for_all else [_column(p) for p in polys]
+        if len(cols) != len(proofs):
+            raise AssertionError("public_input_polys: one column, or one per proof")
+        for t in cols:
+            if t.shape[0] != group_order:
+                raise AssertionError("the public-input column does not have group_order entries")
+        batch = len(proofs)
+        if not batch:
+            return []
+        ctx = N.Context.get(cols[0].device.index)
+        vxy, vinf = _points_arrays(verifier_preprocessed_input._commitments())
+        key = _vkey_for(ctx, group_order, vxy, vinf, srs)
+        xy, inf = np.zeros((batch, 9, 12), dtype=np.uint64), np.zeros((batch, 9), dtype=np.uint8)
+        ev = np.zeros((batch, 6, 4), dtype=np.uint64)
+        for b, proof in enumerate(proofs):
+            xy[b], inf[b], ev[b] = proof._arrays()
+        ptrs = (C.c_void_p * batch)(*[t.data_ptr() for t in cols])
+        ok = np.zeros(batch, dtype=np.uint8)
+        st = N.lib().zkhip_plonk_verify_batch(key.handle, C.c_size_t(batch), xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp),
+                                              ev.ctypes.data_as(_vp), ptrs, ok.ctypes.data_as(_vp), None, None)
+        if st == N.ERR_ARG:
+            raise ValueError("plonk verify: a point is off its curve or outside the prime-order subgroup, or an evaluation is not "
+                             "reduced, in proofs %s" % [int(i) for i in np.nonzero(ok == 2)[0]])
+        N.check(st, "plonk verify_batch")
+        return [bool(v) for v in ok]
