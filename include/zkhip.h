@@ -678,6 +678,34 @@ int zkhip_pointwise_mul(zkhip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b
 /* UnivariateEval::multiply (evaluation.rs:59-86): d_out[na + nb - 1] = coefficients of a * b via three transforms. */
 int zkhip_univariate_multiply(zkhip_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb,
                               uint64_t *d_out);
+/* A batch of transforms of one size in one call.  Transform b, b < batch, is exactly
+ *   zkhip_domain_transform(ctx, d_src + 4 b src_stride, n_src, d_dst + 4 b dst_stride, log_n, inverse):
+ * n_src <= 2^log_n values zero-padded inside the first pass, natural order in and out, the inverse scaled by 1/n, every limb equal
+ * to the single call's.  Strides count field elements (32 bytes).  The number of launches does not depend on batch: one launch up
+ * to 2^11 points (a workgroup's tile holds 2^10 >> log_n whole transforms up to 2^10, one transform of 2^11), and from 2^12 the single
+ * transform's launch chain with the transform index as a grid dimension; all transforms share the context's twiddle tables and
+ * pass plans, which are also the single call's.  Elements of d_dst between one transform's 2^log_n results and the next stride
+ * are never written.
+ * Aliasing: d_dst == d_src transforms in place and requires src_stride == dst_stride and n_src == 2^log_n, otherwise ZKHIP_ERR_ARG;
+ * buffers that overlap in any other way are not supported.
+ * Memory: nothing is allocated when d_dst != d_src (the passes run in d_dst) or 2^log_n <= 2^11.  In place from 2^12 points the
+ * call holds min(batch, max(1, 256 MiB / (32 * 2^log_n))) transforms of the context's workspace and runs the batch as consecutive
+ * chunks of that many transforms, one launch chain each.
+ * Errors (nothing is written): NULL ctx / d_dst / d_src (with n_src > 0) -> ZKHIP_ERR_ARG; log_n > 30, n_src > 2^log_n,
+ * dst_stride < 2^log_n, src_stride < n_src with batch > 1, batch > 65535 -> ZKHIP_ERR_SHAPE; the workspace lent to a commit or a
+ * split-phase session in flight -> ZKHIP_ERR_BUSY.  batch == 0 -> ZKHIP_OK, nothing touched. */
+int zkhip_domain_transform_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *d_src, size_t src_stride, size_t n_src,
+                                 uint64_t *d_dst, size_t dst_stride, uint32_t log_n, int inverse);
+/* Product b, b < batch, is zkhip_univariate_multiply(ctx, d_a + 4 b a_stride, na, d_b + 4 b b_stride, nb, d_out + 4 b out_stride):
+ * na + nb - 1 coefficients, the rest of an output row untouched.  One batched forward transform of all a, one of all b, and one
+ * batched inverse whose gather takes the evaluation-form product and whose store cuts to na + nb - 1.
+ * Memory: three buffers (two up to 2^11 points) of n = the transform size per product, for min(batch, max(1, 256 MiB / (96 n, resp. 64 n)))
+ * products of the context's workspace; a larger batch runs as consecutive chunks of that many products.
+ * Errors (nothing is written): NULL pointer -> ZKHIP_ERR_ARG; na == 0, nb == 0, out_stride < na + nb - 1, a_stride < na or
+ * b_stride < nb with batch > 1, batch > 65535, a transform of more than 2^30 points -> ZKHIP_ERR_SHAPE; workspace lent ->
+ * ZKHIP_ERR_BUSY.  batch == 0 -> ZKHIP_OK. */
+int zkhip_univariate_multiply_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *d_a, size_t a_stride, size_t na,
+                                    const uint64_t *d_b, size_t b_stride, size_t nb, uint64_t *d_out, size_t out_stride);
 
 /* ---- PLONK (plonk/src/protocol/{prover,verifier,utils,transcript}.rs over transcripts/merlin/src/lib.rs) ---------------------
  * Layouts shared by the four calls below:

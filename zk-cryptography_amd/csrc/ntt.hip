@@ -13,6 +13,7 @@
 #include "ctx.hpp"
 #include "host_fr.hpp"
 #include "host_util.hpp"
+#include "ntt_batch_kernels.hpp"
 #include "ntt_kernels.hpp"
 
 using namespace zk;
@@ -266,6 +267,157 @@ extern "C" int zkhip_univariate_multiply(zkhip_ctx* c, const uint64_t* d_a, size
     hipLaunchKernelGGL(pointwise_mul_kernel, dim3(mle_grid_stream(n)), dim3(MLE_BLOCK), 0, c->stream, ea, eb, n, ea);   // :79-82
     ZK_TRY(ntt_inplace(c, ea, log_n, 1, scratch));                                                   // domain.ifft :84
     ZK_HIP(c, hipMemcpyAsync(d_out, ea, unscaled * 32, hipMemcpyDeviceToDevice, c->stream));         // truncate :85
+    return ZKHIP_OK;
+}
+
+// ---- a batch of transforms of one size (ntt_batch_kernels.hpp) ---------------------------------------------------------------
+// Scratch a batch call may hold beyond the caller's buffers: this much, or what ONE row needs if that is more.  A batch that
+// needs more runs as consecutive chunks of rows, each chunk one launch chain.  A constant, not a switch.
+constexpr size_t NTT_BATCH_SCRATCH_BYTES = (size_t)256 << 20;
+
+// Shapes that run as the loop of single calls: those at which the batched kernels were not measured ahead of the loop beyond the
+// repeat-to-repeat spread (profiles/ntt_batch/NOTES.md).  That is a batch of ONE transform of >= 2^12 points -- the same workgroups
+// as the single chain, 44.20 against 44.11 us at 2^12 and 50.88 against 50.75 us at 2^14; up to 2^11 points one transform is one
+// launch instead of three and 1.1 to 1.5 times faster, and every batch of four or more is ahead at every size measured.
+static bool ntt_batch_as_loop(uint32_t log_n, uint32_t batch) { return batch == 1 && log_n >= 12; }
+
+// rows of n <= 2^11 points: one launch, no scratch; in / out may be the same rows
+static int ntt_small_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* d_src, size_t src_stride, size_t n_src, const uint64_t* d_src2,
+                           size_t src2_stride, uint64_t* d_dst, size_t dst_stride, size_t n_dst, uint32_t log_n, int inverse) {
+    const size_t n = (size_t)1 << log_n;
+    uint64_t* tw = nullptr;
+    if (log_n) ZK_TRY(get_twiddles(c, log_n, inverse, &tw));
+    FrArg sc = {};
+    if (inverse) {
+        const zkhost::Fr ni = zkhost::fr_inv(zkhost::fr_from_u64((uint64_t)n));
+        std::memcpy(sc.v, ni.l, 32);
+    }
+    const uint32_t scaled = inverse && log_n ? 1u : 0u;
+    const double bytes = (double)batch * (32.0 * (double)(n_src + n_dst) + (d_src2 ? 32.0 * (double)n_src : 0.0));
+    if (log_n <= (uint32_t)NTT_TILE_LOG) {
+        const uint32_t per = (uint32_t)NTT_TILE >> log_n;
+        ProfScope ps(c, "ntt_batch_small", bytes);
+        hipLaunchKernelGGL(ntt_batch_small_kernel<NTT_TILE_LOG>, dim3((batch + per - 1) / per), dim3(NTT_TILE / 4), (size_t)NTT_TILE * 32, c->stream,
+                           d_src, src_stride, n_src, d_src2, src2_stride, d_dst, dst_stride, n_dst, batch, log_n, (const uint64_t*)tw, sc, scaled);
+    } else {
+        ProfScope ps(c, "ntt_batch_tile11", bytes);
+        hipLaunchKernelGGL(ntt_batch_small_kernel<NTT_BIG_TILE_LOG>, dim3(batch), dim3(NTT_BIG_TILE / 4), (size_t)NTT_BIG_TILE * 32, c->stream,
+                           d_src, src_stride, n_src, d_src2, src2_stride, d_dst, dst_stride, n_dst, batch, log_n, (const uint64_t*)tw, sc, scaled);
+    }
+    ZK_HIP(c, hipGetLastError());
+    return ZKHIP_OK;
+}
+
+// rows of n >= 2^12 points, ntt_big with the row as the grid's second dimension: the first pass gathers src -> work, the passes run
+// in place in work, the last one writes dst.  work == dst (n_dst == n, dst distinct from src) needs no scratch at all.
+static int ntt_big_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* d_src, size_t src_stride, size_t n_src, const uint64_t* d_src2,
+                         size_t src2_stride, uint64_t* d_dst, size_t dst_stride, size_t n_dst, uint32_t log_n, int inverse,
+                         uint64_t* d_work, size_t work_stride) {
+    const size_t n = (size_t)1 << log_n;
+    NttPlan* plan = nullptr;
+    ZK_TRY(get_plan(c, log_n, inverse, &plan));
+    const size_t lds = (size_t)NTT_BIG_TILE * 32;
+    const dim3 grid((unsigned)(n >> NTT_BIG_TILE_LOG), batch);
+    {
+        ProfScope ps(c, "ntt_batch_first8", (double)batch * (32.0 * (double)(n_src + n) + (d_src2 ? 32.0 * (double)n : 0.0)));
+        hipLaunchKernelGGL(ntt_batch_first8_kernel, grid, dim3(NTT_BIG_BLOCK), lds, c->stream, d_src, src_stride, n_src, d_src2, src2_stride,
+                           d_work, work_stride, log_n, (const uint64_t*)plan->tw1.get());
+    }
+    FrArg sc = {};
+    std::memcpy(sc.v, plan->n_inv.l, 32);
+    for (size_t p = 0; p < plan->passes.size(); ++p) {
+        const NttPass& ps = plan->passes[p];
+        const bool last = p + 1 == plan->passes.size();
+        ProfScope pr(c, "ntt_batch_pass", (double)batch * 32.0 * (double)(n + (last ? n_dst : n)) + 32.0 * (double)((((size_t)1 << ps.T) - 1) << ps.s0));
+        if (last && inverse)
+            hipLaunchKernelGGL(ntt_batch_pass_kernel<true>, grid, dim3(NTT_BIG_BLOCK), lds, c->stream, (const uint64_t*)d_work, work_stride, d_dst, dst_stride,
+                               ps.s0, ps.T, (const uint64_t*)ps.table.get(), sc, n_dst);
+        else
+            hipLaunchKernelGGL(ntt_batch_pass_kernel<false>, grid, dim3(NTT_BIG_BLOCK), lds, c->stream, (const uint64_t*)d_work, work_stride,
+                               last ? d_dst : d_work, last ? dst_stride : work_stride, ps.s0, ps.T, (const uint64_t*)ps.table.get(), sc, last ? n_dst : n);
+    }
+    ZK_HIP(c, hipGetLastError());
+    return ZKHIP_OK;
+}
+
+// rows per chunk when every row needs bufs scratch buffers of n elements
+static uint32_t ntt_batch_chunk(uint32_t batch, size_t n, size_t bufs) {
+    const size_t fit = std::max<size_t>(1, NTT_BATCH_SCRATCH_BYTES / (bufs * n * 32));
+    return (uint32_t)std::min<size_t>(batch, fit);
+}
+
+// The batch form of zkhip_domain_transform (include/zkhip.h).  Allocates nothing when d_dst != d_src or n <= 2^11; in place at
+// n >= 2^12 it holds min(batch, max(1, NTT_BATCH_SCRATCH_BYTES / 32n)) rows of the context's workspace and runs the batch in chunks of
+// that many rows.
+extern "C" int zkhip_domain_transform_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* d_src, size_t src_stride, size_t n_src,
+                                            uint64_t* d_dst, size_t dst_stride, uint32_t log_n, int inverse) {
+    if (!c || !d_dst || (n_src && !d_src)) return ZKHIP_ERR_ARG;
+    if (log_n > 30) return ZKHIP_ERR_SHAPE;
+    const size_t n = (size_t)1 << log_n;
+    if (n_src > n || dst_stride < n || (batch > 1 && src_stride < n_src) || batch > 65535) return ZKHIP_ERR_SHAPE;
+    const bool in_place = d_dst == d_src;
+    if (in_place && (n_src != n || src_stride != dst_stride)) return ZKHIP_ERR_ARG;
+    ZK_TRY(c->activate());
+    if (ntt_batch_as_loop(log_n, batch)) {
+        if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;                         // before the first row is written, not between two
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_domain_transform(c, d_src ? d_src + 4 * (size_t)b * src_stride : nullptr, n_src, d_dst + 4 * (size_t)b * dst_stride, log_n, inverse));
+        return ZKHIP_OK;
+    }
+    const bool scratch = in_place && log_n >= 12;
+    const uint32_t chunk = scratch ? ntt_batch_chunk(batch, n, 1) : batch;
+    ZK_TRY(c->reserve_ws(scratch ? (size_t)chunk * n * 32 : 0));
+    if (batch == 0) return ZKHIP_OK;
+    if (log_n < 12) return ntt_small_batch(c, batch, d_src, src_stride, n_src, nullptr, 0, d_dst, dst_stride, n, log_n, inverse);
+    if (!scratch) return ntt_big_batch(c, batch, d_src, src_stride, n_src, nullptr, 0, d_dst, dst_stride, n, log_n, inverse, d_dst, dst_stride);
+    for (uint32_t b0 = 0; b0 < batch; b0 += chunk) {
+        const uint32_t cnt = std::min(chunk, batch - b0);
+        ZK_TRY(ntt_big_batch(c, cnt, d_src + 4 * (size_t)b0 * src_stride, src_stride, n_src, nullptr, 0, d_dst + 4 * (size_t)b0 * dst_stride, dst_stride,
+                             n, log_n, inverse, (uint64_t*)c->ws.ptr, n));
+    }
+    return ZKHIP_OK;
+}
+
+// The batch form of zkhip_univariate_multiply: per chunk one batched forward transform of the a rows, one of the b rows and one
+// batched inverse whose gather takes their product and whose store keeps na + nb - 1 coefficients.  Holds three buffers of n elements
+// per row of a chunk (two at n <= 2^11), min(batch, max(1, NTT_BATCH_SCRATCH_BYTES / (96n, resp. 64n))) rows.
+extern "C" int zkhip_univariate_multiply_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* d_a, size_t a_stride, size_t na,
+                                               const uint64_t* d_b, size_t b_stride, size_t nb, uint64_t* d_out, size_t out_stride) {
+    if (!c || !d_a || !d_b || !d_out) return ZKHIP_ERR_ARG;
+    if (na == 0 || nb == 0) return ZKHIP_ERR_SHAPE;
+    const size_t unscaled = na + nb - 1;
+    uint32_t log_n = 0;
+    while (log_n <= 30 && ((size_t)1 << log_n) < unscaled) ++log_n;
+    if (log_n > 30 || out_stride < unscaled || batch > 65535 || (batch > 1 && (a_stride < na || b_stride < nb))) return ZKHIP_ERR_SHAPE;
+    ZK_TRY(c->activate());
+    if (ntt_batch_as_loop(log_n, batch)) {
+        if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_univariate_multiply(c, d_a + 4 * (size_t)b * a_stride, na, d_b + 4 * (size_t)b * b_stride, nb, d_out + 4 * (size_t)b * out_stride));
+        return ZKHIP_OK;
+    }
+    const size_t n = (size_t)1 << log_n;
+    const size_t bufs = log_n < 12 ? 2 : 3;                                      // up to 2^11 points the inverse needs no work buffer
+    const uint32_t chunk = ntt_batch_chunk(batch, n, bufs);
+    ZK_TRY(c->reserve_ws(bufs * chunk * n * 32));
+    uint64_t* ea = (uint64_t*)c->ws.ptr;
+    uint64_t* eb = ea + 4 * (size_t)chunk * n;
+    uint64_t* work = eb + 4 * (size_t)chunk * n;
+    for (uint32_t b0 = 0; b0 < batch; b0 += chunk) {
+        const uint32_t cnt = std::min(chunk, batch - b0);
+        const uint64_t* a = d_a + 4 * (size_t)b0 * a_stride;
+        const uint64_t* b = d_b + 4 * (size_t)b0 * b_stride;
+        uint64_t* out = d_out + 4 * (size_t)b0 * out_stride;
+        if (log_n < 12) {
+            ZK_TRY(ntt_small_batch(c, cnt, a, a_stride, na, nullptr, 0, ea, n, n, log_n, 0));
+            ZK_TRY(ntt_small_batch(c, cnt, b, b_stride, nb, nullptr, 0, eb, n, n, log_n, 0));
+            ZK_TRY(ntt_small_batch(c, cnt, ea, n, n, eb, n, out, out_stride, unscaled, log_n, 1));
+        } else {
+            ZK_TRY(ntt_big_batch(c, cnt, a, a_stride, na, nullptr, 0, ea, n, n, log_n, 0, ea, n));
+            ZK_TRY(ntt_big_batch(c, cnt, b, b_stride, nb, nullptr, 0, eb, n, n, log_n, 0, eb, n));
+            ZK_TRY(ntt_big_batch(c, cnt, ea, n, n, eb, n, out, out_stride, unscaled, log_n, 1, work, n));
+        }
+    }
     return ZKHIP_OK;
 }
 

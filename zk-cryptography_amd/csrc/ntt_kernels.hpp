@@ -34,6 +34,28 @@ static __global__ __launch_bounds__(MLE_BLOCK) void ntt_twiddle_kernel(const uin
     }
 }
 
+// `stages` radix-2 stages (butterfly distances 1, 2, ...) on an LDS table of bit-reversed inputs: `half` butterflies per stage,
+// butterfly b pairing i0 = ((b >> s) << (s + 1)) | j with i0 + 2^s, j = b & (2^s - 1), twiddle w_m^j = W[j * n/(2m)].  The table
+// may hold several independent transforms of 2^log_n points next to each other (log_n >= stages): the index arithmetic never crosses
+// a multiple of 2^stages.  Called by the whole workgroup of BLOCK threads; ends behind a barrier.
+template <int BLOCK>
+__device__ __forceinline__ void ntt_lds_stages(Fr* tab, uint32_t half, uint32_t stages, uint32_t log_n, const uint64_t* __restrict__ tw) {
+    const uint32_t n = 1u << log_n;
+    for (uint32_t s = 0; s < stages; ++s) {
+        const uint32_t m = 1u << s;                 // butterfly distance
+        const uint32_t tw_stride = n >> (s + 1);    // w_m^j = W[j * n/(2m)]
+        for (uint32_t b = threadIdx.x; b < half; b += BLOCK) {
+            const uint32_t j = b & (m - 1);
+            const uint32_t i0 = ((b >> s) << (s + 1)) | j;
+            Fr t = tab[i0 + m] * load_fr(tw, (size_t)j * tw_stride);
+            Fr u = tab[i0];
+            tab[i0 + m] = u - t;
+            tab[i0] = u + t;
+        }
+        __syncthreads();
+    }
+}
+
 // pass 1: out[tile] = first min(log_n, NTT_TILE_LOG) stages applied to the bit-reversed input
 static __global__ __launch_bounds__(MLE_BLOCK) void ntt_first_stages_kernel(const uint64_t* __restrict__ in,
                                                                      uint64_t* __restrict__ out, uint32_t log_n,
@@ -45,19 +67,7 @@ static __global__ __launch_bounds__(MLE_BLOCK) void ntt_first_stages_kernel(cons
     const uint32_t base = blockIdx.x * tile;
     for (uint32_t q = threadIdx.x; q < tile; q += MLE_BLOCK) tab[q] = load_fr(in, bitrev(base + q, log_n));
     __syncthreads();
-    for (uint32_t s = 0; s < stages; ++s) {
-        const uint32_t m = 1u << s;                 // butterfly distance
-        const uint32_t tw_stride = n >> (s + 1);    // w_m^j = W[j * n/(2m)]
-        for (uint32_t b = threadIdx.x; b < tile / 2; b += MLE_BLOCK) {
-            const uint32_t j = b & (m - 1);
-            const uint32_t i0 = ((b >> s) << (s + 1)) | j;
-            Fr t = tab[i0 + m] * load_fr(tw, (size_t)j * tw_stride);
-            Fr u = tab[i0];
-            tab[i0 + m] = u - t;
-            tab[i0] = u + t;
-        }
-        __syncthreads();
-    }
+    ntt_lds_stages<MLE_BLOCK>(tab, tile / 2, stages, log_n, tw);
     for (uint32_t q = threadIdx.x; q < tile; q += MLE_BLOCK) store_fr(out, base + q, tab[q]);
 }
 
@@ -149,12 +159,11 @@ static __global__ __launch_bounds__(MLE_BLOCK) void ntt_pass_table_kernel(const 
 // in: n_src <= n elements, zero beyond (coeffs.resize(size, F::zero()), domain.rs:109-110); in2 (nullable, n_src elements): the
 // input is the element-wise product in * in2 (UnivariateEval::multiply's evaluation-form product, evaluation.rs:79-82,
 // fused into the inverse transform's gather)
-static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_first8_kernel(const uint64_t* __restrict__ in, size_t n_src,
-                                                                          const uint64_t* __restrict__ in2, uint64_t* __restrict__ out,
-                                                                          uint32_t log_n, const uint64_t* __restrict__ tw1) {
+// (the body of workgroup g of one transform: ntt_first8_kernel below and the batched form in ntt_batch_kernels.hpp)
+__device__ __forceinline__ void ntt_first8_body(uint32_t g, const uint64_t* __restrict__ in, size_t n_src, const uint64_t* __restrict__ in2,
+                                                uint64_t* __restrict__ out, uint32_t log_n, const uint64_t* __restrict__ tw1) {
     extern __shared__ __attribute__((aligned(16))) unsigned char zk_dyn_lds[];
     Fr* tab = reinterpret_cast<Fr*>(zk_dyn_lds);
-    const uint32_t g = blockIdx.x;
     for (uint32_t e = threadIdx.x; e < (uint32_t)NTT_BIG_TILE; e += NTT_BIG_BLOCK) {
         const uint32_t k = e & 7, q = e >> 3;                 // the eight sub-transforms' inputs are neighbours in memory
         const uint32_t o = (k << (log_n - 3)) | (g << 8) | q;
@@ -194,17 +203,22 @@ static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_first8_kernel(const 
         store_fr(out, ((size_t)k << (log_n - 3)) | ((size_t)g << 8) | q, tab[e]);
     }
 }
+static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_first8_kernel(const uint64_t* __restrict__ in, size_t n_src,
+                                                                          const uint64_t* __restrict__ in2, uint64_t* __restrict__ out,
+                                                                          uint32_t log_n, const uint64_t* __restrict__ tw1) {
+    ntt_first8_body(blockIdx.x, in, n_src, in2, out, log_n, tw1);
+}
 
+// (the body of workgroup g of one transform: ntt_pass_kernel below and the batched form in ntt_batch_kernels.hpp)
 template <bool LAST_SCALED>
-static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_pass_kernel(const uint64_t* src, uint64_t* dst,   /* may alias: the middle passes run in place */
-                                                                        uint32_t s0, uint32_t T, const uint64_t* __restrict__ tw,
-                                                                        FrArg scale, size_t n_dst) {
+__device__ __forceinline__ void ntt_pass_body(uint32_t g, const uint64_t* src, uint64_t* dst,   /* may alias: the middle passes run in place */
+                                              uint32_t s0, uint32_t T, const uint64_t* __restrict__ tw, const FrArg& scale, size_t n_dst) {
     extern __shared__ __attribute__((aligned(16))) unsigned char zk_dyn_lds[];
     Fr* tab = reinterpret_cast<Fr*>(zk_dyn_lds);
     const uint32_t cols_log = NTT_BIG_TILE_LOG - T, cols = 1u << cols_log;
     const uint32_t lo_chunks = 1u << (s0 - cols_log);
-    const size_t hi = blockIdx.x / lo_chunks;
-    const uint32_t lo0 = (blockIdx.x % lo_chunks) << cols_log;
+    const size_t hi = g / lo_chunks;
+    const uint32_t lo0 = (g % lo_chunks) << cols_log;
     const size_t base = (hi << (s0 + T)) | lo0;
     for (uint32_t q = threadIdx.x; q < (uint32_t)NTT_BIG_TILE; q += NTT_BIG_BLOCK) {
         const uint32_t mid = q >> cols_log, c = q & (cols - 1);
@@ -242,6 +256,12 @@ static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_pass_kernel(const ui
         const size_t o = base + ((size_t)mid << s0) + cc;
         if (o < n_dst) store_fr(dst, o, tab[q]);              // a product keeps len_a + len_b - 1 coefficients (evaluation.rs:85)
     }
+}
+template <bool LAST_SCALED>
+static __global__ __launch_bounds__(NTT_BIG_BLOCK) void ntt_pass_kernel(const uint64_t* src, uint64_t* dst,   /* may alias: the middle passes run in place */
+                                                                        uint32_t s0, uint32_t T, const uint64_t* __restrict__ tw,
+                                                                        FrArg scale, size_t n_dst) {
+    ntt_pass_body<LAST_SCALED>(blockIdx.x, src, dst, s0, T, tw, scale, n_dst);
 }
 
 // out[i] = a[i] * b[i]   (evaluation.rs:79-82)

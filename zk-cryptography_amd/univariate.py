@@ -37,6 +37,30 @@ class Domain:
                                                C.c_uint32(self.size.bit_length() - 1), C.c_int(inverse)), "domain_transform")
         return buf
 
+    def _transform_batch(self, values, inverse):
+        import torch
+        t = values if isinstance(values, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(values).view(np.int64))
+        if t.dim() != 3 or t.shape[2] != 4:
+            raise AssertionError("a batch of transforms takes a [B, m, 4] array")
+        t = t.cuda().contiguous()
+        batch, m = t.shape[0], t.shape[1]
+        if m > self.size:
+            raise AssertionError("more values than the domain holds")
+        buf = torch.empty((batch, self.size, 4), dtype=torch.int64, device=t.device)
+        ctx = N.Context.get(buf.device.index)
+        N.check(N.lib().zkhip_domain_transform_batch(ctx.handle, C.c_uint32(batch), N.ptr(t), C.c_size_t(m), C.c_size_t(m), N.ptr(buf),
+                                                     C.c_size_t(self.size), C.c_uint32(self.size.bit_length() - 1), C.c_int(inverse)),
+                "domain_transform_batch")
+        return buf
+
+    def fft_batch(self, values):
+        """fft of every row of a [B, m, 4] array, m <= size, in one call -> int64 [B, size, 4] device tensor; row b equals fft(values[b])"""
+        return self._transform_batch(values, 0)
+
+    def ifft_batch(self, values):
+        """ifft of every row, as fft_batch"""
+        return self._transform_batch(values, 1)
+
     def fft(self, coeffs):
         """domain.rs:108-112 -> int64 [size, 4] device tensor of evaluations"""
         return self._transform(coeffs, 0)
@@ -79,3 +103,25 @@ class UnivariateEval:
         N.check(N.lib().zkhip_univariate_multiply(ctx.handle, N.ptr(a), C.c_size_t(a.shape[0]), N.ptr(b),
                                                   C.c_size_t(b.shape[0]), N.ptr(out)), "multiply")
         return DenseUnivariatePolynomial(out)
+
+    @staticmethod
+    def multiply_batch(polys_a, polys_b):
+        """multiply(polys_a[b], polys_b[b]) for every b in one call.  The polynomials of one list have one length; the products are
+        views of one [B, len_a + len_b - 1, 4] tensor."""
+        import torch
+        if len(polys_a) != len(polys_b):
+            raise AssertionError("multiply_batch takes as many left as right factors")
+        if not polys_a:
+            return []
+        ca, cb = [p.coefficients for p in polys_a], [p.coefficients for p in polys_b]
+        na, nb = ca[0].shape[0], cb[0].shape[0]
+        if any(t.shape[0] != na for t in ca) or any(t.shape[0] != nb for t in cb):
+            raise AssertionError("the polynomials of one list of multiply_batch have one length")
+        if na == 0 or nb == 0:
+            raise AssertionError("attempt to subtract with overflow")   # as multiply
+        a, b = torch.stack(ca).contiguous(), torch.stack(cb).contiguous()
+        out = torch.empty((len(ca), na + nb - 1, 4), dtype=torch.int64, device=a.device)
+        ctx = N.Context.get(a.device.index)
+        N.check(N.lib().zkhip_univariate_multiply_batch(ctx.handle, C.c_uint32(len(ca)), N.ptr(a), C.c_size_t(na), C.c_size_t(na), N.ptr(b),
+                                                        C.c_size_t(nb), C.c_size_t(nb), N.ptr(out), C.c_size_t(na + nb - 1)), "multiply_batch")
+        return [DenseUnivariatePolynomial(out[k]) for k in range(len(ca))]
