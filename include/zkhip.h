@@ -754,6 +754,33 @@ int zkhip_plonk_verify(zkhip_ctx *ctx, size_t n, const uint64_t *h_vk_xy, const 
                        const uint8_t *h_points_inf, const uint64_t *h_evals, const uint64_t *d_public, const uint64_t *d_g2_xy,
                        const uint8_t *d_g2_inf, size_t n_g2, uint8_t *h_ok);
 
+/* ---- PLONK: a batch of witnesses of one circuit proved in one call (prover.rs:39-96 per proof) --------------------------------------
+ * The layouts are the PLONK block's above, one proof after the other.
+ *
+ * zkhip_plonk_prove_batch: proof b is, limb for limb, what zkhip_plonk_prove(key, a_b, b_b, c_b, public_b, blinding_b, ..) returns.
+ *   h_a_ptrs, h_b_ptrs, h_c_ptrs, h_public_ptrs: HOST arrays of `batch` DEVICE columns in evaluation form, n values each; entries may
+ *   repeat.  h_blinding[batch][11][4]; outputs h_points_xy[batch][9][12], h_points_inf[batch][9], h_evals[batch][6][4],
+ *   h_challenges[batch][6][4] (may be NULL), h_status[batch].
+ *   A proof is REFUSED when its witness does not satisfy the circuit (any of the four conditions zkhip_plonk_prove names) or one of its
+ *   blinding scalars is not a reduced field element: h_status[b] = ZKHIP_ERR_ARG and its outputs are all zero; every other proof of the
+ *   call is exactly what it would be without the refused one, and the call returns ZKHIP_ERR_ARG.  Otherwise ZKHIP_OK with every status
+ *   ZKHIP_OK.  Refusals of the whole call launch nothing and leave the outputs untouched: a NULL key, array or entry -> ZKHIP_ERR_ARG;
+ *   batch > 65535 -> ZKHIP_ERR_SHAPE; the context's workspace lent to a commit in flight or a split-phase session -> ZKHIP_ERR_BUSY; the
+ *   batch work area cannot be allocated -> ZKHIP_ERR_NOMEM.  batch = 0 returns ZKHIP_OK and touches nothing.
+ *   The proofs run in chunks of min(batch, 64, what fits 256 MiB) proofs, at least one: a proof's work area is that of the single
+ *   prover plus a few hundred bytes, and a key that keeps no coset cache takes its ten coset columns (once, not per proof) out of the
+ *   256 MiB before they are divided.  The area is allocated by the first batch call, kept with the key and freed with it; the single
+ *   prover's own work area is not touched, but a key still serves ONE call at a time.  Per chunk, round r of every proof runs before
+ *   round r + 1 of any: one synchronisation per round, launches whose number does not depend on the proofs in the chunk, one Merlin
+ *   transcript per proof advanced on the context's host threads.  With a shifted-SRS table, n + 6 <= 4096 and the short commit path on,
+ *   a round's commits of the whole chunk are one launch of the plane sums and one of the reduce; otherwise they run three in flight,
+ *   proof after proof, as in the single prover.  A chunk of one proof IS the single prover.
+ * zkhip_plonk_batch_chunk: diagnostics -- the proofs per chunk of a batch of 64 or more for this key, >= 1 (0 for a NULL key). */
+int zkhip_plonk_prove_batch(zkhip_plonk_key *key, uint32_t batch, const uint64_t *const *h_a_ptrs, const uint64_t *const *h_b_ptrs,
+                            const uint64_t *const *h_c_ptrs, const uint64_t *const *h_public_ptrs, const uint64_t *h_blinding,
+                            uint64_t *h_points_xy, uint8_t *h_points_inf, uint64_t *h_evals, uint64_t *h_challenges, int32_t *h_status);
+uint32_t zkhip_plonk_batch_chunk(const zkhip_plonk_key *key);
+
 /* ---- PLONK: a batch of proofs of one circuit in one call (verifier.rs:62-172 per proof) ------------------------------------------
  * The layouts are the PLONK block's above, one proof after the other.
  *

@@ -365,3 +365,8 @@ struct ProfScope {
 
 // cross-unit internals (C++ linkage, not part of the C ABI)
 int zk_ntt_scaled_transform(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint64_t* d_mul, uint64_t* d_dst, uint32_t log_n);   // ntt.hip
+// msm.hip: one round's commits of a chunk of PLONK proofs on the short path (see there)
+bool zk_msm_commit_batch_serves(size_t n_points, size_t longest);
+int zk_msm_commit_batch(zkhip_ctx* c, const void* d_table_with_header, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_scalars,
+                        size_t q_stride, uint32_t batch, uint32_t m, const size_t* sc_off, const size_t* lens, uint64_t* h_out_xy,
+                        uint8_t* h_out_inf, size_t out_stride);

@@ -1067,6 +1067,86 @@ static int kzg_open_small_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* co
     }
     return ZKHIP_OK;
 }
+// The commits of one round of a CHUNK of PLONK proofs (zkhip_plonk_prove_batch, ctx.hpp): m <= 3 polynomials per proof, polynomial j of
+// proof b being lens[j] scalars from d_scalars + 4 (b q_stride + sc_off[j]) on, all against the one shifted-SRS table.  ONE launch of the
+// plane sums with the proof as grid.z, one of the reduce, one copy, one synchronisation -- which also completes whatever the caller
+// enqueued before -- and the weighted_sum_pow2 epilogues on the context's pool.  Result (b, j) goes to h_out_xy + 12 (b out_stride + j),
+// h_out_inf[b out_stride + j].  The group elements are those of any other commit path, so are the affine points.
+bool zk_msm_commit_batch_serves(size_t n_points, size_t longest) {
+    return msm_small_on() && longest <= MSM_SMALL_MAX && n_points * msm_table_widths(n_points).W < ((size_t)1 << 31);
+}
+int zk_msm_commit_batch(zkhip_ctx* c, const void* d_table_with_header, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_scalars,
+                        size_t q_stride, uint32_t batch, uint32_t m, const size_t* sc_off, const size_t* lens, uint64_t* h_out_xy,
+                        uint8_t* h_out_inf, size_t out_stride) {
+    if (!c || !d_table_with_header || !d_scalars || !sc_off || !lens || !h_out_xy || !h_out_inf) return ZKHIP_ERR_ARG;
+    if (m == 0 || m > 3 || batch == 0 || batch > 65535) return ZKHIP_ERR_SHAPE;
+    size_t longest = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        longest = std::max(longest, lens[j]);
+        if (lens[j] == 0 || sc_off[j] + lens[j] > q_stride || q_stride >= ((size_t)1 << 32)) return ZKHIP_ERR_SHAPE;
+    }
+    if (longest > n_points) return ZKHIP_ERR_INDEX;
+    if (!zk_msm_commit_batch_serves(n_points, longest)) return ZKHIP_ERR_SHAPE;
+    int trc = ZKHIP_OK;
+    const uint32_t* d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);
+    if (!d_table) return trc;
+    const MsmLevelWidths lw = msm_table_widths(n_points);
+    MsmSmallArgs a = {};
+    a.table = d_table; a.scalars = d_scalars; a.inf = d_points_inf; a.nprob = m; a.planes = lw.hi;
+    size_t total_pairs = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        a.n[j] = (uint32_t)lens[j]; a.stride[j] = (uint32_t)n_points; a.W[j] = lw.W; a.hi[j] = lw.hi; a.n_hi[j] = lw.n_hi;
+        a.tab_off[j] = 0; a.sc_off[j] = (uint32_t)sc_off[j];
+        total_pairs += lens[j] * lw.W;
+    }
+    // the slots of kzg_open_small_batch: ~2 waves per SIMD over the whole chunk, a proof's share dealt to its polynomials by their pairs,
+    // at least one slot each -- and no lane walks more than OPEN_BATCH_LANE_PAIRS pairs, however many proofs share the chip
+    const size_t budget = std::max<size_t>(1, 2048 / a.planes / batch);
+    for (uint32_t j = 0; j < m; ++j) {
+        const size_t pairs = lens[j] * lw.W, chunks = (pairs + 63) / 64;
+        const size_t share = (budget * pairs + total_pairs - 1) / total_pairs, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
+        a.slot_first[j + 1] = a.slot_first[j] + (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(share, capped)));
+    }
+    a.total_slots = a.slot_first[m];
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t part_bytes = al((size_t)batch * a.planes * a.total_slots * 256), terms_bytes = (size_t)batch * m * a.planes * 192;
+    ZK_TRY(c->reserve_ws(part_bytes + al(terms_bytes)));
+    ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
+    a.partials = (uint32_t*)c->ws.ptr;
+    a.terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
+    {
+        ProfScope ps(c, "plonk_batch_commit_planes", 128.0 * (double)total_pairs * batch / std::max<uint32_t>(1, lw.W));
+        hipLaunchKernelGGL(msm_small_commit_batch_planes_kernel, dim3(a.total_slots, a.planes, batch), dim3(64), 0, c->stream, a, q_stride);
+    }
+    {
+        ProfScope ps(c, "plonk_batch_commit_reduce", 0.0);
+        hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(a.planes, m, batch), dim3(64), 0, c->stream, a);
+    }
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, a.terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    const char* pin = (const char*)c->msm_pin[0].ptr;
+    auto finish = [&](uint32_t k) {                                  // k = b m + j: the weighted sum of its plane sums, <= 20 doublings
+        std::vector<zkhost::Xyzz> pts(lw.hi);
+        std::vector<uint32_t> exps(lw.hi);
+        for (uint32_t t = 0; t < lw.hi; ++t) {
+            std::memcpy(&pts[t], pin + 192 * ((size_t)k * a.planes + t), 192);
+            exps[t] = t;
+        }
+        const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
+        const size_t o = (size_t)(k / m) * out_stride + k % m;
+        h_out_inf[o] = zkhost::xyzz_to_affine(res, h_out_xy + 12 * o) ? 0 : 1;
+    };
+    ZkHostPool* pool = batch * m > 1 ? c->pool() : nullptr;
+    if (!pool) {
+        for (uint32_t k = 0; k < batch * m; ++k) finish(k);
+    } else {
+        pool->run(batch * m, [&](unsigned k) { finish(k); });
+    }
+    return ZKHIP_OK;
+}
+
+
 static int kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, const uint64_t* h_points, size_t n_eval_points,
                           const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_folded_xy,
                           const uint8_t* d_folded_inf, const void* d_level_tables_with_header, uint64_t* h_evaluations, uint64_t* h_proofs_xy,

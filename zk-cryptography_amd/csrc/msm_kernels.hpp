@@ -655,6 +655,8 @@ struct MsmSmallArgs {
 };
 // (the bodies are shared with the batched launches below: opening b of a batch reads its scalars from scalar index sc_base on and
 // owns the partials [b][plane][slot] and the terms [b][j][plane]; a lone launch is b = 0, sc_base = 0)
+// (INF_BY_POINT: the flags are indexed by the point alone, not like the scalars -- commits of several vectors against ONE table)
+template <bool INF_BY_POINT = false>
 __device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uint32_t b, size_t sc_base) {
     const uint32_t slot = blockIdx.x, plane = blockIdx.y, lane = threadIdx.x;
     uint32_t j = 0;
@@ -665,7 +667,7 @@ __device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uin
     G1XyzzU acc = G1XyzzU::identity();
     for (uint32_t p = s * 64 + lane; p < pairs; p += lanes_total) {
         const uint32_t w = p / n, i = p - w * n;
-        if (a.inf && a.inf[a.sc_off[j] + i]) continue;
+        if (a.inf && a.inf[(INF_BY_POINT ? 0u : a.sc_off[j]) + i]) continue;
         DigitStream ds(load_fr(a.scalars, sc_base + a.sc_off[j] + i).from_mont());
         int32_t d = 0;
         for (uint32_t v = 0; v <= w; ++v) d = ds.next(v < n_hi ? hi : hi - 1);
@@ -702,6 +704,12 @@ static __global__ __launch_bounds__(64) void msm_small_batch_planes_kernel(MsmSm
     msm_small_planes_body(a, blockIdx.z, (size_t)blockIdx.z * q_stride);
 }
 static __global__ __launch_bounds__(64) void msm_small_batch_reduce_kernel(MsmSmallArgs a) { msm_small_reduce_body(a, blockIdx.z); }
+// B proofs of one circuit (zkhip_plonk_prove_batch): problem j of every proof is a commit of n[j] scalars, sc_off[j] scalars into the
+// proof's work area, against the ONE shifted-SRS table (tab_off = 0); proof b's area lies q_stride scalars behind proof b - 1's.  The
+// reduce launch is msm_small_batch_reduce_kernel.
+static __global__ __launch_bounds__(64) void msm_small_commit_batch_planes_kernel(MsmSmallArgs a, size_t q_stride) {
+    msm_small_planes_body<true>(a, blockIdx.z, (size_t)blockIdx.z * q_stride);
+}
 
 // ---- shifted-SRS table (zkhip_srs_precompute) -------------------------------------------------------------
 static __global__ __launch_bounds__(MSM_BLOCK) void msm_clear_inf_kernel(const uint8_t* __restrict__ inf, size_t n, uint32_t* __restrict__ table) {

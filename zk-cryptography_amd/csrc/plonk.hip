@@ -17,6 +17,7 @@
 #include "host_g1.hpp"
 #include "host_util.hpp"
 #include "pairing_internal.hpp"
+#include "plonk_batch_kernels.hpp"
 #include "plonk_kernels.hpp"
 #include "plonk_scalars.hpp"
 #include "plonk_verify_kernels.hpp"
@@ -138,6 +139,9 @@ struct zkhip_plonk_key {
     uint32_t log_n = 0, log_D = 0, ratio = 0;
     const uint64_t* srs_xy = nullptr; const void* srs_table = nullptr; const uint8_t* srs_inf = nullptr; size_t n_points = 0;   // views
     DevMem evals, coeffs, omega, gpow, ginv, pre, work;
+    DevMem batch_work;                   // zkhip_plonk_prove_batch: the work areas of batch_chunk proofs, allocated by the first batch call
+    PinMem batch_pin;
+    uint32_t batch_chunk = 0;
     HFr w_n, zh_inv[8];
     uint64_t* col_eval(int k) const { return (uint64_t*)evals.get() + 4 * n * k; }
     uint64_t* col_coeff(int k) const { return (uint64_t*)coeffs.get() + 4 * S * k; }
@@ -242,6 +246,32 @@ int read_flags(zkhip_ctx* c, const Work& w, bool* any) {
     *any = false;
     for (int i = 0; i < PLONK_FLAGS; ++i) *any = *any || h[i] != 0;
     return ZKHIP_OK;
+}
+
+// round 5's scalars (prover.rs:295-359) from the challenges up to nu and the seven values of round 4 (the six evaluations, then
+// PI(zeta)): the fifteen weights of plonk_linearise_kernel in its order of terms, and the constant c0
+void round5_scalars(const zkhip_plonk_key& k, const HFr* ch, const HFr* ev, HFr* s, HFr* c0_out) {
+    const size_t n = k.n;
+    const HFr beta = ch[C_BETA], gamma = ch[C_GAMMA], alpha = ch[C_ALPHA], nu = ch[C_NU], zeta = ch[C_ZETA];
+    const HFr az = ev[E_A], bz = ev[E_B], cz = ev[E_C], s1z = ev[E_S1], s2z = ev[E_S2], zwz = ev[E_ZW], piz = ev[6];
+    const HFr a2 = fr_mul(alpha, alpha), zn = h_pow(zeta, (uint64_t)n), zh = fr_sub(zn, zkhost::fr_one());
+    const HFr l1z = l1_at(zeta, zh, (uint64_t)n);
+    const HFr bzeta = fr_mul(beta, zeta);
+    const HFr p1 = fr_mul(fr_mul(fr_add(fr_add(az, bzeta), gamma), fr_add(fr_add(bz, fr_add(bzeta, bzeta)), gamma)),
+                          fr_add(fr_add(cz, fr_add(bzeta, fr_add(bzeta, bzeta))), gamma));
+    const HFr p2 = fr_mul(fr_mul(fr_add(fr_add(az, fr_mul(beta, s1z)), gamma), fr_add(fr_add(bz, fr_mul(beta, s2z)), gamma)), zwz);
+    HFr nup[6];
+    nup[0] = zkhost::fr_one();
+    for (int j = 1; j < 6; ++j) nup[j] = fr_mul(nup[j - 1], nu);
+    const HFr w[PLONK_LIN_TERMS] = {fr_mul(az, bz), az, bz, cz, zkhost::fr_one(), fr_add(fr_mul(alpha, p1), fr_mul(a2, l1z)),
+                                    h_neg(fr_mul(fr_mul(alpha, beta), p2)), h_neg(zh), h_neg(fr_mul(zh, zn)), h_neg(fr_mul(zh, fr_mul(zn, zn))),
+                                    nup[1], nup[2], nup[3], nup[4], nup[5]};
+    for (int j = 0; j < PLONK_LIN_TERMS; ++j) s[j] = w[j];
+    HFr c0 = fr_sub(piz, fr_mul(fr_mul(alpha, fr_add(cz, gamma)), p2));
+    c0 = fr_sub(c0, fr_mul(a2, l1z));
+    const HFr opened[5] = {az, bz, cz, s1z, s2z};
+    for (int j = 0; j < 5; ++j) c0 = fr_sub(c0, fr_mul(nup[j + 1], opened[j]));
+    *c0_out = c0;
 }
 
 void absorb_challenges_from_proof(const uint64_t* xy, const uint8_t* inf, const uint64_t* evals, HFr* ch) {   // protocol/utils.rs:56-96
@@ -484,28 +514,12 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
     // ---- round 5 (:295-376): W_zeta = (r + nu-combination) / (X - zeta), W_zeta_omega = (z - z(w zeta)) / (X - w zeta)
     ch[C_NU] = tr.challenge("nu");
     {
-        const HFr beta = ch[C_BETA], gamma = ch[C_GAMMA], alpha = ch[C_ALPHA], nu = ch[C_NU];
-        const HFr az = ev[E_A], bz = ev[E_B], cz = ev[E_C], s1z = ev[E_S1], s2z = ev[E_S2], zwz = ev[E_ZW], piz = ev[6];
-        const HFr a2 = fr_mul(alpha, alpha), zn = h_pow(zeta, (uint64_t)n), zh = fr_sub(zn, zkhost::fr_one());
-        const HFr l1z = l1_at(zeta, zh, (uint64_t)n);
-        const HFr bzeta = fr_mul(beta, zeta);
-        const HFr p1 = fr_mul(fr_mul(fr_add(fr_add(az, bzeta), gamma), fr_add(fr_add(bz, fr_add(bzeta, bzeta)), gamma)),
-                              fr_add(fr_add(cz, fr_add(bzeta, fr_add(bzeta, bzeta))), gamma));
-        const HFr p2 = fr_mul(fr_mul(fr_add(fr_add(az, fr_mul(beta, s1z)), gamma), fr_add(fr_add(bz, fr_mul(beta, s2z)), gamma)), zwz);
-        HFr nup[6];
-        nup[0] = zkhost::fr_one();
-        for (int j = 1; j < 6; ++j) nup[j] = fr_mul(nup[j - 1], nu);
+        HFr s[PLONK_LIN_TERMS], c0;
+        round5_scalars(k, ch, ev, s, &c0);
         PlonkLinArg L = {};
         const uint64_t* ptr[PLONK_LIN_TERMS] = {k.col_coeff(0), k.col_coeff(1), k.col_coeff(2), k.col_coeff(3), k.col_coeff(4), w.Z, k.col_coeff(7),
                                                 w.TL, w.TM, w.TH, w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6)};
-        const HFr s[PLONK_LIN_TERMS] = {fr_mul(az, bz), az, bz, cz, zkhost::fr_one(), fr_add(fr_mul(alpha, p1), fr_mul(a2, l1z)),
-                                        h_neg(fr_mul(fr_mul(alpha, beta), p2)), h_neg(zh), h_neg(fr_mul(zh, zn)), h_neg(fr_mul(zh, fr_mul(zn, zn))),
-                                        nup[1], nup[2], nup[3], nup[4], nup[5]};
         for (int j = 0; j < PLONK_LIN_TERMS; ++j) { L.p[j] = ptr[j]; L.s[j] = fa(s[j]); }
-        HFr c0 = fr_sub(piz, fr_mul(fr_mul(alpha, fr_add(cz, gamma)), p2));
-        c0 = fr_sub(c0, fr_mul(a2, l1z));
-        const HFr opened[5] = {az, bz, cz, s1z, s2z};
-        for (int j = 0; j < 5; ++j) c0 = fr_sub(c0, fr_mul(nup[j + 1], opened[j]));
         L.c0 = fa(c0);
         {
             ProfScope ps(c, "plonk_linearise", 32.0 * 16.0 * (double)n);
@@ -525,6 +539,382 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
     ch[C_MU] = tr.challenge("mu");
     if (h_challenges) std::memcpy(h_challenges, ch, sizeof ch);
     return ZKHIP_OK;
+}
+
+// ---- the batched prover -------------------------------------------------------------------------------------------------------------
+// zkhip_plonk_prove_batch proves CHUNKS of proofs: round r of every proof of a chunk before round r + 1 of any, one synchronisation per
+// round and chunk, the launches of a chunk independent of the proofs in it (plonk_batch_kernels.hpp).  A chunk is
+// min(batch, PLONK_BATCH_CHUNK, what fits PLONK_BATCH_BUDGET) proofs, at least one: every proof owns a work area of the single
+// prover's layout plus the workgroup values of its seven Horner jobs, and a key without a coset cache adds its ten coset columns ONCE
+// (they are the key's, not a proof's: the budget pays for them before it is divided).  The area is allocated by the first batch call,
+// grown if a later call's chunk is larger, kept with the key and freed with it.
+constexpr size_t PLONK_BATCH_BUDGET = (size_t)256 << 20;
+constexpr uint32_t PLONK_BATCH_CHUNK = 64;
+
+namespace {
+
+struct BatchLayout {
+    size_t per = 0, ws = 0, fs = 0;                            // a proof's area: bytes, elements, ints
+    size_t hb = 0, o_hv = 0, o_hc = 0;                         // workgroup values per Horner job; the two scratch rows in a proof's area
+    size_t o_par = 0, o_cols = 0, o_pre = 0, o_areas = 0, dev_bytes = 0;
+    size_t p_par = 0, p_cols = 0, p_flags = 0, p_out = 0, pin_bytes = 0;
+};
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+BatchLayout batch_layout(const zkhip_plonk_key& k, uint32_t chunk) {
+    BatchLayout L;
+    const size_t base = work_layout(k, nullptr, false, nullptr);
+    L.hb = (k.S + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L) + 1;
+    L.o_hv = base;
+    L.o_hc = L.o_hv + al256((size_t)PB_JOBS * L.hb * 32);
+    L.per = L.o_hc + al256((size_t)PB_JOBS * L.hb * 32);
+    L.ws = L.per / 32; L.fs = L.per / sizeof(int);
+    L.o_par = 0;
+    L.o_cols = L.o_par + al256((size_t)chunk * PB_SLOTS * 32);
+    L.o_pre = L.o_cols + al256((size_t)chunk * 4 * sizeof(uint64_t*));
+    L.o_areas = L.o_pre + (k.pre ? 0 : al256((size_t)N_PRE * k.D * 32));
+    L.dev_bytes = L.o_areas + (size_t)chunk * L.per;
+    L.p_par = 0;
+    L.p_cols = L.p_par + al256((size_t)chunk * PB_SLOTS * 32);
+    L.p_flags = L.p_cols + al256((size_t)chunk * 4 * sizeof(uint64_t*));
+    L.p_out = L.p_flags + al256((size_t)chunk * PLONK_FLAGS * sizeof(int));
+    L.pin_bytes = L.p_out + al256((size_t)chunk * PB_JOBS * 32);
+    return L;
+}
+uint32_t batch_chunk_for(const zkhip_plonk_key& k, size_t batch) {
+    const size_t per = batch_layout(k, 1).per, pre_bytes = k.pre ? 0 : (size_t)N_PRE * k.D * 32;
+    const size_t fit = PLONK_BATCH_BUDGET > pre_bytes ? (PLONK_BATCH_BUDGET - pre_bytes) / per : 0;
+    return (uint32_t)std::max<size_t>(1, std::min({batch, (size_t)PLONK_BATCH_CHUNK, fit}));
+}
+
+// the pointer table of a chunk as the gather kernel reads it: proof b's a, b, c, public at [4 b .. 4 b + 3]
+void pack_columns(const uint64_t* const* a, const uint64_t* const* b, const uint64_t* const* c, const uint64_t* const* pub, size_t first, uint32_t count,
+                  const uint64_t** out) {
+    for (uint32_t i = 0; i < count; ++i) {
+        out[4 * i] = a[first + i]; out[4 * i + 1] = b[first + i]; out[4 * i + 2] = c[first + i]; out[4 * i + 3] = pub[first + i];
+    }
+}
+
+// one proof of a chunk on the host: its transcript, challenges, blinding and verdict
+struct BatchProof {
+    Merlin tr{"plonk_protocol"};
+    HFr ch[N_CHALLENGES], ev[PB_JOBS];
+    bool refused = false;
+};
+
+struct BatchRun {
+    zkhip_plonk_key& k;
+    zkhip_ctx* c;
+    BatchLayout L;
+    uint32_t bc;                                               // proofs of this chunk
+    char* dev; char* pin;
+    Work w;                                                    // proof 0's area
+    uint64_t *hv, *hc;
+    const uint64_t* par;                                       // device
+    HFr* h_par;                                                // pinned
+    std::vector<BatchProof> pr;
+    uint64_t* xy; uint8_t* inf;                                // the chunk's first proof in the caller's arrays
+
+    HFr& slot(uint32_t b, uint32_t s) { return h_par[(size_t)b * PB_SLOTS + s]; }
+    int upload_par() {
+        ZK_HIP(c, hipMemcpyAsync(dev + L.o_par, pin + L.p_par, (size_t)bc * PB_SLOTS * 32, hipMemcpyHostToDevice, c->stream));
+        return ZKHIP_OK;
+    }
+    template <class F> void each(F f) {                        // host work per proof: on the context's pool
+        ZkHostPool* pool = bc > 1 ? c->pool() : nullptr;
+        if (!pool) { for (uint32_t b = 0; b < bc; ++b) if (!pr[b].refused) f(b); }
+        else pool->run(bc, [&](unsigned b) { if (!pr[b].refused) f(b); });
+    }
+    int transform(const uint64_t* src, uint64_t* dst, size_t n_src, uint32_t log_n, int inverse) {
+        return zkhip_domain_transform_batch(c, bc, src, L.ws, n_src, dst, L.ws, log_n, inverse);
+    }
+    void blind(uint64_t* const* polys, uint32_t m, uint32_t kk, const uint8_t (*slots)[3]) {
+        PlonkBlindBatchArg a = {};
+        for (uint32_t q = 0; q < m; ++q) { a.p[q] = polys[q]; for (int j = 0; j < 3; ++j) a.slot[q][j] = slots[q][j]; }
+        hipLaunchKernelGGL(plonk_batch_blind_kernel, dim3(m, bc), dim3(64), 0, c->stream, a, k.n, kk, par, L.ws);
+    }
+    int copy_flags() {                                         // rides on the round's synchronisation
+        ZK_HIP(c, hipMemcpy2DAsync(pin + L.p_flags, PLONK_FLAGS * sizeof(int), w.flags, L.per, PLONK_FLAGS * sizeof(int), bc, hipMemcpyDeviceToHost, c->stream));
+        return ZKHIP_OK;
+    }
+    void read_flags() {
+        const int* f = (const int*)(pin + L.p_flags);
+        for (uint32_t b = 0; b < bc; ++b)
+            for (int i = 0; i < PLONK_FLAGS; ++i) if (f[PLONK_FLAGS * b + i]) pr[b].refused = true;
+    }
+    // One round's commits of the chunk, m polynomials per proof, results at point `first` on; ends in the round's synchronisation.
+    // Short path: one launch chain for all of them.  Otherwise commit_group, three in flight, proof after proof.
+    int commit(uint64_t* const* polys, const size_t* lens, uint32_t m, int first) {
+        if (k.srs_table && zk_msm_commit_batch_serves(k.n_points, k.n + 6)) {
+            size_t off[3];
+            for (uint32_t j = 0; j < m; ++j) off[j] = (size_t)(polys[j] - w.A) / 4;
+            return zk_msm_commit_batch(c, k.srs_table, k.srs_inf, k.n_points, w.A, L.ws, bc, m, off, lens, xy + 12 * first, inf + first, N_POINTS);
+        }
+        ZK_HIP(c, hipStreamSynchronize(c->stream));            // the flags and values of this round: a refused proof is not committed
+        read_flags();
+        for (uint32_t b = 0; b < bc; ++b) {
+            if (pr[b].refused) continue;
+            const uint64_t* p[3]; uint64_t* oxy[3]; uint8_t* oinf[3];
+            for (uint32_t j = 0; j < m; ++j) {
+                p[j] = polys[j] + 4 * (size_t)b * L.ws;
+                oxy[j] = xy + 12 * ((size_t)b * N_POINTS + first + j);
+                oinf[j] = inf + (size_t)b * N_POINTS + first + j;
+            }
+            ZK_TRY(commit_group(k, p, lens, (int)m, oxy, oinf));
+        }
+        return ZKHIP_OK;
+    }
+    int rounds(const uint64_t* const* h_cols, bool* pre_ready);
+};
+
+int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
+    const size_t n = k.n, D = k.D, ws = L.ws, fs = L.fs;
+    const uint64_t* pre = k.pre ? (const uint64_t*)k.pre.get() : (const uint64_t*)(dev + L.o_pre);
+    auto point = [&](uint32_t b, int p) { return xy + 12 * ((size_t)b * N_POINTS + p); };
+    auto is_inf = [&](uint32_t b, int p) { return inf[(size_t)b * N_POINTS + p] != 0; };
+    ZK_HIP(c, hipMemset2DAsync(w.A, L.per, 0, w.zero_bytes, bc, c->stream));
+    // ---- round 1: the columns into the areas, to coefficients, blinded, committed
+    std::memcpy(pin + L.p_cols, h_cols, (size_t)bc * 4 * sizeof(uint64_t*));
+    ZK_HIP(c, hipMemcpyAsync(dev + L.o_cols, pin + L.p_cols, (size_t)bc * 4 * sizeof(uint64_t*), hipMemcpyHostToDevice, c->stream));
+    ZK_TRY(upload_par());
+    uint64_t* const stage = w.ev;                              // a, b, c, public of a proof in evaluation form: n each (the coset rows come later)
+    {
+        ProfScope ps(c, "plonk_batch_gather", 64.0 * 4.0 * (double)n * bc);
+        hipLaunchKernelGGL(plonk_batch_gather_kernel, dim3(mle_grid_stream(n), 4, bc), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t* const*)(dev + L.o_cols), n,
+                           stage, ws);
+    }
+    ZK_HIP(c, hipGetLastError());
+    {
+        uint64_t* dst[4] = {w.A, w.B, w.C, w.PI};
+        for (int j = 0; j < 4; ++j) ZK_TRY(transform(stage + 4 * n * j, dst[j], n, k.log_n, 1));
+        static const uint8_t slots[3][3] = {{1, 0, 0}, {3, 2, 0}, {5, 4, 0}};      // constant coefficient: rands[1], then rands[0] X
+        blind(dst, 3, 2, slots);
+        ZK_HIP(c, hipGetLastError());
+        const size_t lens[3] = {n + 2, n + 2, n + 2};
+        ZK_TRY(copy_flags());
+        ZK_TRY(commit(dst, lens, 3, P_AS));
+    }
+    each([&](uint32_t b) {
+        for (int p = P_AS; p <= P_CS; ++p) pr[b].tr.append_point("first_round", point(b, p), is_inf(b, p));
+        pr[b].ch[C_BETA] = pr[b].tr.challenge("beta");
+        pr[b].ch[C_GAMMA] = pr[b].tr.challenge("gamma");
+        slot(b, PB_BETA) = pr[b].ch[C_BETA]; slot(b, PB_GAMMA) = pr[b].ch[C_GAMMA];
+    });
+    // ---- round 2: the accumulator
+    ZK_TRY(upload_par());
+    {
+        PlonkCols cols;
+        for (int j = 0; j < 8; ++j) cols.q[j] = k.col_eval(j);
+        const uint32_t nb = (uint32_t)((n + GP_ROWS - 1) / GP_ROWS);
+        {
+            ProfScope ps(c, "plonk_batch_grand_product", 32.0 * 14.0 * (double)n * bc);
+            hipLaunchKernelGGL(plonk_batch_gp_ratio_kernel, dim3(nb, bc), dim3(GP_T), 0, c->stream, (const uint64_t*)stage, (const uint64_t*)(stage + 4 * n),
+                               (const uint64_t*)(stage + 8 * n), (const uint64_t*)(stage + 12 * n), cols, (const uint64_t*)k.omega.get(), n, par, w.F, w.bp,
+                               w.flags, ws, fs);
+            hipLaunchKernelGGL(plonk_batch_gp_top_kernel, dim3(bc), dim3(1024), 0, c->stream, (const uint64_t*)w.bp, nb, w.bx, ws);
+            hipLaunchKernelGGL(plonk_batch_gp_apply_kernel, dim3(nb, bc), dim3(GP_T), 0, c->stream, (const uint64_t*)w.F, (const uint64_t*)w.bx, n, w.ACC, w.flags,
+                               ws, fs);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(copy_flags());
+        ZK_TRY(transform(w.ACC, w.Z, n, k.log_n, 1));
+        uint64_t* polys[1] = {w.Z};
+        static const uint8_t slots[1][3] = {{6, 7, 8}};
+        blind(polys, 1, 3, slots);
+        ZK_HIP(c, hipGetLastError());
+        const size_t lens[1] = {n + 3};
+        ZK_TRY(commit(polys, lens, 1, P_ACC));
+        read_flags();       // a row breaks the gate identity, a denominator vanishes or the accumulator does not close: that proof is refused
+    }
+    each([&](uint32_t b) {
+        pr[b].tr.append_point("second_round", point(b, P_ACC), is_inf(b, P_ACC));
+        pr[b].ch[C_ALPHA] = pr[b].tr.challenge("alpha");
+        slot(b, PB_ALPHA) = pr[b].ch[C_ALPHA]; slot(b, PB_ALPHA2) = fr_mul(pr[b].ch[C_ALPHA], pr[b].ch[C_ALPHA]);
+    });
+    // ---- round 3: the quotient on the coset
+    ZK_TRY(upload_par());
+    {
+        PlonkPadBatchArg pad = {};
+        const uint64_t* src[PB_COSET_ROWS] = {w.A, w.B, w.C, w.Z, w.PI};
+        const size_t lens5[PB_COSET_ROWS] = {n + 2, n + 2, n + 2, n + 3, n};
+        for (int j = 0; j < PB_COSET_ROWS; ++j) { pad.src[j] = src[j]; pad.len[j] = (uint32_t)lens5[j]; }
+        {
+            ProfScope ps(c, "plonk_batch_scale_pad", 32.0 * 5.0 * (double)(D + n) * bc);
+            hipLaunchKernelGGL(plonk_batch_scale_pad_kernel, dim3(mle_grid_stream(D), PB_COSET_ROWS, bc), dim3(MLE_BLOCK), 0, c->stream, pad,
+                               (const uint64_t*)k.gpow.get(), D, w.ev, ws);
+        }
+        ZK_HIP(c, hipGetLastError());
+        for (int j = 0; j < PB_COSET_ROWS; ++j) ZK_TRY(transform(w.ev + 4 * D * j, w.ev + 4 * D * j, D, k.log_D, 0));
+        if (!k.pre && !*pre_ready) {
+            ZK_TRY(fill_pre(k, (uint64_t*)(dev + L.o_pre), w.W));
+            *pre_ready = true;
+        }
+        PlonkQuotBatchArg q = {};
+        for (int j = 0; j < 8; ++j) q.zh_inv[j] = fa(k.zh_inv[j]);
+        q.rot = k.ratio;
+        {
+            ProfScope ps(c, "plonk_batch_quotient", 32.0 * 17.0 * (double)D * bc);
+            hipLaunchKernelGGL(plonk_batch_quotient_kernel, dim3(mle_grid_stream(D), bc), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)w.ev, pre, D, q, par, w.T, ws);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(transform(w.T, w.T, D, k.log_D, 1));
+        {
+            ProfScope ps(c, "plonk_batch_split", 32.0 * (double)(D + 6 * n) * bc);
+            hipLaunchKernelGGL(plonk_batch_split_kernel, dim3(mle_grid_stream(D), bc), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)w.T,
+                               (const uint64_t*)k.ginv.get(), n, D, par, w.TL, w.TM, w.TH, w.flags, ws, fs);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(copy_flags());
+        uint64_t* polys[3] = {w.TL, w.TM, w.TH};
+        const size_t lens[3] = {n + 1, n + 1, n + 6};
+        ZK_TRY(commit(polys, lens, 3, P_TL));
+        read_flags();       // Z_H does not divide the numerator: no proof from it
+    }
+    each([&](uint32_t b) {
+        for (int p = P_TL; p <= P_TH; ++p) pr[b].tr.append_point("third_round", point(b, p), is_inf(b, p));
+        pr[b].ch[C_ZETA] = pr[b].tr.challenge("zeta");
+        slot(b, PB_ZETA) = pr[b].ch[C_ZETA]; slot(b, PB_ZETA_W) = fr_mul(pr[b].ch[C_ZETA], k.w_n);
+    });
+    // ---- round 4: the six evaluations and PI(zeta), seven jobs per proof in one scan and one top launch
+    ZK_TRY(upload_par());
+    const size_t per_block = (size_t)HS_T * HS_L;
+    {
+        HornerBatchArg h = {};
+        const uint64_t* poly[PB_JOBS] = {w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6), w.Z, w.PI};       // the order of the evaluations, then PI
+        const size_t len[PB_JOBS] = {n + 2, n + 2, n + 2, n, n, n + 3, n};
+        for (int j = 0; j < PB_JOBS; ++j) { h.coeffs[j] = poly[j]; h.len[j] = (uint32_t)len[j]; h.zslot[j] = PB_ZETA; }
+        h.zslot[E_ZW] = PB_ZETA_W;                             // apply_w_to_polynomial(z)(zeta) = z(w zeta)
+        h.own = 0x67u;                                         // A, B, C, Z, PI are the proof's; sigma_1, sigma_2 the key's
+        h.vstride = (uint32_t)L.hb;
+        const uint32_t nb = (uint32_t)((n + 3 + per_block - 1) / per_block);
+        {
+            ProfScope ps(c, "plonk_batch_evaluate", 32.0 * 7.0 * (double)n * bc);
+            hipLaunchKernelGGL(horner_batch_scan_kernel<false>, dim3(nb, PB_JOBS, bc), dim3(HS_T), 0, c->stream, h, par, hv, (const uint64_t*)nullptr,
+                               (uint64_t*)nullptr, ws);
+            hipLaunchKernelGGL(horner_batch_top_kernel, dim3(PB_JOBS, bc), dim3(1024), 0, c->stream, h, par, (const uint64_t*)hv, hc, w.out, ws);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpy2DAsync(pin + L.p_out, PB_JOBS * 32, w.out, L.per, PB_JOBS * 32, bc, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    each([&](uint32_t b) {
+        std::memcpy(pr[b].ev, pin + L.p_out + (size_t)b * PB_JOBS * 32, sizeof pr[b].ev);
+        for (int e = 0; e < N_EVALS; ++e) pr[b].tr.append_scalar("fourth_round", pr[b].ev[e]);
+        pr[b].ch[C_NU] = pr[b].tr.challenge("nu");
+        HFr c0;
+        round5_scalars(k, pr[b].ch, pr[b].ev, &slot(b, PB_LIN), &c0);
+        slot(b, PB_C0) = c0;
+    });
+    // ---- round 5: the linearisation and the two opening quotients
+    ZK_TRY(upload_par());
+    {
+        PlonkLinBatchArg lin = {};
+        const uint64_t* ptr[PLONK_LIN_TERMS] = {k.col_coeff(0), k.col_coeff(1), k.col_coeff(2), k.col_coeff(3), k.col_coeff(4), w.Z, k.col_coeff(7),
+                                                w.TL, w.TM, w.TH, w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6)};
+        for (int j = 0; j < PLONK_LIN_TERMS; ++j) lin.p[j] = ptr[j];
+        lin.own = (1u << 5) | (0x3fu << 7);                    // z, the three parts of t, the three wires
+        {
+            ProfScope ps(c, "plonk_batch_linearise", 32.0 * 16.0 * (double)n * bc);
+            hipLaunchKernelGGL(plonk_batch_linearise_kernel, dim3(mle_grid_stream(n + 6), bc), dim3(MLE_BLOCK), 0, c->stream, lin, n + 6, par, w.W, ws);
+        }
+        HornerBatchArg h = {};
+        h.coeffs[0] = w.W; h.len[0] = (uint32_t)(n + 6); h.zslot[0] = PB_ZETA; h.quotient[0] = w.Q1;
+        h.coeffs[1] = w.Z; h.len[1] = (uint32_t)(n + 3); h.zslot[1] = PB_ZETA_W; h.quotient[1] = w.Q2;
+        h.own = 3u;
+        h.vstride = (uint32_t)L.hb;
+        const uint32_t nb = (uint32_t)((n + 6 + per_block - 1) / per_block);
+        {
+            ProfScope ps(c, "plonk_batch_divide", 96.0 * 2.0 * (double)n * bc);
+            hipLaunchKernelGGL(horner_batch_scan_kernel<false>, dim3(nb, 2, bc), dim3(HS_T), 0, c->stream, h, par, hv, (const uint64_t*)nullptr, (uint64_t*)nullptr, ws);
+            hipLaunchKernelGGL(horner_batch_top_kernel, dim3(2, bc), dim3(1024), 0, c->stream, h, par, (const uint64_t*)hv, hc, (uint64_t*)nullptr, ws);
+            hipLaunchKernelGGL(horner_batch_scan_kernel<true>, dim3(nb, 2, bc), dim3(HS_T), 0, c->stream, h, par, (uint64_t*)nullptr, (const uint64_t*)hc, w.out, ws);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_TRY(copy_flags());
+        uint64_t* polys[2] = {w.Q1, w.Q2};
+        const size_t lens[2] = {n + 5, n + 2};
+        ZK_TRY(commit(polys, lens, 2, P_WZ));
+    }
+    each([&](uint32_t b) {
+        for (int p = P_WZ; p <= P_WZW; ++p) pr[b].tr.append_point("fifth_round", point(b, p), is_inf(b, p));
+        pr[b].ch[C_MU] = pr[b].tr.challenge("mu");
+    });
+    return ZKHIP_OK;
+}
+
+}  // namespace
+
+extern "C" uint32_t zkhip_plonk_batch_chunk(const zkhip_plonk_key* key) { return key ? batch_chunk_for(*key, PLONK_BATCH_CHUNK) : 0; }
+
+extern "C" int zkhip_plonk_prove_batch(zkhip_plonk_key* key, uint32_t batch, const uint64_t* const* h_a_ptrs, const uint64_t* const* h_b_ptrs,
+                                       const uint64_t* const* h_c_ptrs, const uint64_t* const* h_public_ptrs, const uint64_t* h_blinding,
+                                       uint64_t* h_points_xy, uint8_t* h_points_inf, uint64_t* h_evals, uint64_t* h_challenges, int32_t* h_status) {
+    if (!key) return ZKHIP_ERR_ARG;
+    if (!batch) return ZKHIP_OK;
+    if (!h_a_ptrs || !h_b_ptrs || !h_c_ptrs || !h_public_ptrs || !h_blinding || !h_points_xy || !h_points_inf || !h_evals || !h_status) return ZKHIP_ERR_ARG;
+    if (batch > 65535) return ZKHIP_ERR_SHAPE;
+    for (uint32_t b = 0; b < batch; ++b) if (!h_a_ptrs[b] || !h_b_ptrs[b] || !h_c_ptrs[b] || !h_public_ptrs[b]) return ZKHIP_ERR_ARG;
+    zkhip_plonk_key& k = *key;
+    zkhip_ctx* c = k.ctx;
+    ZK_TRY(c->activate());
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;             // a commit or a split-phase session holds the context's workspace
+    const uint32_t chunk = batch_chunk_for(k, batch);
+    if (chunk > 1 && chunk > k.batch_chunk) {                   // the first batch call, or a larger chunk than any before
+        ZK_HIP(c, hipStreamSynchronize(c->stream));            // nothing of an earlier batch may still read the old area
+        const BatchLayout L = batch_layout(k, chunk);
+        DevMem dev; PinMem pin;
+        if (dev_alloc(dev, L.dev_bytes) != hipSuccess || pin_alloc(pin, L.pin_bytes) != hipSuccess) { (void)hipGetLastError(); return ZKHIP_ERR_NOMEM; }
+        k.batch_work = std::move(dev); k.batch_pin = std::move(pin); k.batch_chunk = chunk;
+    }
+    bool any_refused = false, pre_ready = false;
+    for (uint32_t b0 = 0; b0 < batch; b0 += chunk) {
+        const uint32_t bc = std::min(chunk, batch - b0);
+        uint64_t* xy = h_points_xy + 12 * (size_t)N_POINTS * b0;
+        uint8_t* inf = h_points_inf + (size_t)N_POINTS * b0;
+        uint64_t* evals = h_evals + 4 * (size_t)N_EVALS * b0;
+        uint64_t* chal = h_challenges ? h_challenges + 4 * (size_t)N_CHALLENGES * b0 : nullptr;
+        std::vector<uint8_t> refused(bc, 0);
+        if (bc == 1) {                                         // a chunk of one proof is the single prover
+            const int rc = zkhip_plonk_prove(key, h_a_ptrs[b0], h_b_ptrs[b0], h_c_ptrs[b0], h_public_ptrs[b0], h_blinding + 44 * (size_t)b0, xy, inf, evals, chal);
+            if (rc != ZKHIP_OK && rc != ZKHIP_ERR_ARG) return rc;
+            refused[0] = rc == ZKHIP_ERR_ARG;
+        } else {
+            BatchRun run{k, c, batch_layout(k, k.batch_chunk), bc};
+            run.dev = (char*)k.batch_work.get(); run.pin = (char*)k.batch_pin.get();
+            work_layout(k, run.dev + run.L.o_areas, false, &run.w);
+            run.hv = (uint64_t*)(run.dev + run.L.o_areas + run.L.o_hv); run.hc = (uint64_t*)(run.dev + run.L.o_areas + run.L.o_hc);
+            run.par = (const uint64_t*)(run.dev + run.L.o_par); run.h_par = (HFr*)(run.pin + run.L.p_par);
+            run.pr.resize(bc);
+            run.xy = xy; run.inf = inf;
+            std::memset(run.h_par, 0, (size_t)bc * PB_SLOTS * 32);
+            for (uint32_t b = 0; b < bc; ++b) {
+                const uint64_t* bl = h_blinding + 44 * (size_t)(b0 + b);
+                for (int i = 0; i < 11; ++i) if (zkhost::fr_geq_p(bl + 4 * i)) run.pr[b].refused = true;     // an unreduced blinding scalar
+                if (!run.pr[b].refused) std::memcpy(&run.slot(b, PB_BLIND), bl, 11 * 32);
+            }
+            std::memset(xy, 0, 96 * (size_t)N_POINTS * bc);
+            std::memset(inf, 0, (size_t)N_POINTS * bc);
+            std::vector<const uint64_t*> cols(4 * (size_t)bc);
+            pack_columns(h_a_ptrs, h_b_ptrs, h_c_ptrs, h_public_ptrs, b0, bc, cols.data());
+            const int rc = run.rounds(cols.data(), &pre_ready);
+            if (rc != ZKHIP_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+            for (uint32_t b = 0; b < bc; ++b) {
+                refused[b] = run.pr[b].refused;
+                if (refused[b]) continue;
+                std::memcpy(evals + 4 * (size_t)N_EVALS * b, run.pr[b].ev, 32 * N_EVALS);
+                if (chal) std::memcpy(chal + 4 * (size_t)N_CHALLENGES * b, run.pr[b].ch, 32 * N_CHALLENGES);
+            }
+        }
+        for (uint32_t b = 0; b < bc; ++b) {
+            h_status[b0 + b] = refused[b] ? ZKHIP_ERR_ARG : ZKHIP_OK;
+            if (!refused[b]) continue;
+            any_refused = true;                                // its outputs are zero; every other proof is what it would be without it
+            std::memset(xy + 12 * (size_t)N_POINTS * b, 0, 96 * N_POINTS);
+            std::memset(inf + (size_t)N_POINTS * b, 0, N_POINTS);
+            std::memset(evals + 4 * (size_t)N_EVALS * b, 0, 32 * N_EVALS);
+            if (chal) std::memset(chal + 4 * (size_t)N_CHALLENGES * b, 0, 32 * N_CHALLENGES);
+        }
+    }
+    return any_refused ? ZKHIP_ERR_ARG : ZKHIP_OK;
 }
 
 // compute_verifier_challenges (protocol/utils.rs:56-96): host only, no GPU

@@ -547,6 +547,62 @@ class PlonkProver:
         _replay(self.transcript, proof)
         return proof
 
+    def prove_batch(self, witnesses, blindings=None, allow_failures=False):
+        """-> list[PlonkProof], proof for proof what prove(witness, blinding) returns, in one call (zkhip_plonk_prove_batch): every round
+        of all proofs before the next round of any.  `blindings`: 11 scalars per witness (default: fresh ones from `secrets`).  A witness
+        that does not satisfy the circuit, or a blinding scalar that is not below the field's modulus, is refused: the call raises
+        ZkhipError naming the indices -- or, with allow_failures=True, returns None at them; the other proofs are what they would be
+        without the refused ones.  Touches neither self.transcript nor self.random_number: a batch has no one transcript to leave behind."""
+        witnesses = list(witnesses)
+        batch = len(witnesses)
+        if blindings is None:
+            blindings = [[secrets.randbelow(R_MOD) for _ in range(11)] for _ in range(batch)]
+        blindings = [list(b) for b in blindings]
+        if len(blindings) != batch or any(len(b) != 11 for b in blindings):
+            raise AssertionError("blindings: 11 scalars (6 + 3 + 2) per witness")
+        if batch == 0:
+            return []
+        key = _key_for(self.preprocessed_input, self.srs)
+        cols = [[_column(v) for v in (w.a, w.b, w.c, w.public_poly)] for w in witnesses]
+        for t in (t for row in cols for t in row):
+            if t.shape[0] != key.n:
+                raise AssertionError("a witness column does not have group_order entries")
+        ptrs = [(C.c_void_p * batch)(*[row[j].data_ptr() for row in cols]) for j in range(4)]
+        bl = np.zeros((batch, 11, 4), dtype=np.uint64)
+        for b, scalars in enumerate(blindings):                 # limbs as given: an unreduced scalar refuses its proof, not the call
+            for i, v in enumerate(scalars):
+                v = int(v)
+                if not 0 <= v < 1 << 256:
+                    raise AssertionError("blinding: a scalar does not fit 256 bits")
+                bl[b, i] = Fr.from_int(v) if v < R_MOD else [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+        xy, inf = np.zeros((batch, 9, 12), dtype=np.uint64), np.zeros((batch, 9), dtype=np.uint8)
+        ev, ch = np.zeros((batch, 6, 4), dtype=np.uint64), np.zeros((batch, 6, 4), dtype=np.uint64)
+        status = np.zeros(batch, dtype=np.int32)
+        key.ctx.sync_stream()
+        st = N.lib().zkhip_plonk_prove_batch(key.handle, C.c_uint32(batch), ptrs[0], ptrs[1], ptrs[2], ptrs[3], bl.ctypes.data_as(_vp),
+                                             xy.ctypes.data_as(_vp), inf.ctypes.data_as(_vp), ev.ctypes.data_as(_vp), ch.ctypes.data_as(_vp),
+                                             status.ctypes.data_as(_vp))
+        refused = [b for b in range(batch) if status[b] != N.ZKHIP_OK]
+        if st != N.ERR_ARG or not refused:
+            N.check(st, "plonk prove_batch")
+        if refused and not allow_failures:
+            raise N.ZkhipError("plonk prove_batch: refused witnesses (they do not satisfy the circuit, or a blinding scalar is not reduced) "
+                               "at indices %s" % refused, N.ERR_ARG)
+        proofs = []
+        for b in range(batch):
+            if status[b] != N.ZKHIP_OK:
+                proofs.append(None)
+                continue
+            fields = {f: G1Affine(xy[b, i], inf[b, i]) for i, f in enumerate(PROOF_POINTS)}
+            fields.update(zip(PROOF_SCALARS, Fr.to_ints(ev[b])))
+            proofs.append(PlonkProof(**fields))
+        return proofs
+
+    def batch_chunk(self):
+        """diagnostics (zkhip_plonk_batch_chunk): how many proofs of this circuit prove_batch runs side by side"""
+        return int(N.lib().zkhip_plonk_batch_chunk(_key_for(self.preprocessed_input, self.srs).handle))
+
+
 
 def _replay(t, proof):
     t.first_round(proof.as_commitment, proof.bs_commitment, proof.cs_commitment)
