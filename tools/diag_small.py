@@ -13,6 +13,7 @@ t = torch.randint(0, 2 ** 62, (n, 4), dtype=torch.int64, device="cuda")
 poly = zk.Multilinear(t)
 for _ in range(3):
     sc = zk.Sumcheck(poly); sc.poly_sum(); sc.prove()
+torch.cuda.synchronize()   # prove() returns on the sequence word, ahead of the last kernel's end
 buf = np.zeros((64, 8), dtype=np.uint64)
 N.lib().zkhip_debug_read_stamps(N.Context.get().handle, buf.ctypes.data_as(C.c_void_p))
 tick = 1.0 / 2400.0   # us per s_memtime tick: the counter runs at the 2.4 GHz core clock of an otherwise idle chip (calibrated: a steady round = 5.4 us)
@@ -26,4 +27,5 @@ for r in range(log_n):
 for r0 in range(24):
     s = buf[40 + r0].astype(np.int64)
     if s[0]:
-        print("kernel starting at round %2d: prologue %6.2f us, rounds %6.2f us" % (r0, (s[1] - s[0]) * tick, (s[2] - s[1]) * tick))
+        word = ", sequence word stored %.2f us after the rounds" % ((s[3] - s[2]) * tick) if s[3] else ""     # the launch that delivers the proof
+        print("kernel starting at round %2d: prologue %6.2f us, rounds %6.2f us%s" % (r0, (s[1] - s[0]) * tick, (s[2] - s[1]) * tick, word))

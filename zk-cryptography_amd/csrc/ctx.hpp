@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
 #include <deque>
 #include <functional>
 #include <memory>
@@ -302,13 +303,39 @@ struct zkhip_ctx {
     }
     // result slots of the basic prover: pinned copies of [state .. round polynomials] + the event their copy completes at;
     // proof_pending[k] = n_vars of the proof in flight in slot k (0: free)
+    // Behind the mirrored span every slot has a SEQUENCE WORD: the proof's last kernel stores proof_seq[k] there (a system-scope release)
+    // once the mirror is complete, and the synchronous call's collector spins on it (wait_proof) instead of on the event, which is
+    // signalled only after the kernel's epilogue and end-of-kernel write-back (proofs in flight are collected by their event:
+    // sumcheck_collect).  proof_seq[k] counts the proofs enqueued into slot k and is never reset, so no
+    // earlier proof's word -- collected, abandoned or still to come on the slot's stream -- can pass for this one's.
+    static constexpr size_t PROOF_PIN_WORDS = (ZK_SMALL_ROUNDPOLYS - ZK_SMALL_STATE) + 8 * ZK_MAX_ROUNDS;
     zk::PinMem proof_pin[PROOF_SLOTS];
     zk::Event proof_ev[PROOF_SLOTS];
     uint32_t proof_pending[PROOF_SLOTS] = {};
+    uint64_t proof_seq[PROOF_SLOTS] = {};
+    uint64_t* proof_word(int k) { return (uint64_t*)proof_pin[k].get() + PROOF_PIN_WORDS; }
     int ensure_proof_slot(int k) {
         if (zk::ensure_event(proof_ev[k]) != hipSuccess) return ZKHIP_ERR_HIP;
-        if (!proof_pin[k] && zk::pin_alloc(proof_pin[k], ((ZK_SMALL_ROUNDPOLYS - ZK_SMALL_STATE) + 8 * ZK_MAX_ROUNDS) * 8) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        if (!proof_pin[k]) {
+            if (zk::pin_alloc(proof_pin[k], (PROOF_PIN_WORDS + 8) * 8) != hipSuccess) return ZKHIP_ERR_NOMEM;
+            *proof_word(k) = 0;                 // below every value of the counter
+        }
         return ZKHIP_OK;
+    }
+    // Host wait for the proof in slot k: the sequence word for as long as wait_event would poll, then the event -- a faulted kernel or
+    // a lost device never writes the word and is reported by the event exactly as before.  With the library's profile on, the event
+    // alone: the timeline's events are then complete when the call returns.
+    int wait_proof(int k) {
+        if (!profiling) {
+            const volatile uint64_t* word = proof_word(k);
+            const uint64_t want = proof_seq[k];
+            const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);      // wait_event's ~2 ms of polling
+            do {
+                for (int spin = 0; spin < 256; ++spin)
+                    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return ZKHIP_OK;
+            } while (std::chrono::steady_clock::now() < give_up);
+        }
+        return wait_event(proof_ev[k].get());
     }
     // proofs still in flight write their results into the pinned slots from their lanes' streams, and no buffer may go away under a
     // kernel: zkhip_ctx_destroy waits for the caller's stream and for every stream the context created

@@ -127,9 +127,14 @@ struct SmallArgs {
     uint64_t* weights_out;  // nullable: 2^n_rounds fold weights eq_b(r) * 2^32 (Montgomery form)
     uint64_t* final_out;    // nullable: the table left after n_rounds folds
     // The LAST kernel of a proof delivers it: host_delta != 0 is the distance (in u64) from the device span [state .. round polynomials] to
-    // its pinned host mirror -- the rounds of earlier kernels are copied there at entry, this kernel's own outputs are stored twice -- so
-    // no hipMemcpyAsync (8 us with its launch gap) follows the last round.  The host waits for the kernel's completion event.
+    // its pinned host mirror -- the rounds of earlier kernels are copied there by the output wave, this kernel's own outputs are stored
+    // twice -- so no hipMemcpyAsync (8 us with its launch gap) follows the last round.
     long long host_delta;
+    // ... and says so: once everything the host reads from the mirror has been stored, `seq` goes into the pinned word `seq_word` (a
+    // system-scope release), ahead of the epilogue, the end-of-kernel write-back and the completion event.  The host spins on the word
+    // and falls back to the event (sumcheck_collect).  Null for launches that deliver nothing (and for the sharded prover's).
+    uint64_t seq;
+    uint64_t* seq_word;
 };
 
 constexpr int SMALL_BLOCK = 512;   // 8 waves: the transcript wave, two schedule waves, five waves for the trees and weights
@@ -167,12 +172,6 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
     Fr* scratch = w0 + w_all + w_all / 2 + 1;           // SMALL_BLOCK entries, only in the grouped mode
     Fr* e_sh = scratch + (grouped ? SMALL_BLOCK : 0);   // 2 x 2: to_mont(level-2 differences) of tree0 / tree1
     Fr* r_sh = e_sh + 4;                                // 2: canonical challenge, double-buffered
-    if (a.host_delta && a.round0) {   // what earlier kernels of this proof recorded: sum, round polynomials and challenges of rounds < round0
-        for (uint32_t i = threadIdx.x; i < 12 * a.round0 + 4; i += SMALL_BLOCK) {
-            const uint64_t* p = i < 4 ? st->sum + i : i < 4 + 8 * a.round0 ? round_polys + (i - 4) : challenges + (i - 4 - 8 * a.round0);
-            *const_cast<uint64_t*>(p + a.host_delta) = *p;
-        }
-    }
     // ---- leaves (sums are taken as they come -- the conversion to canonical integers is linear -- then converted once)
     if (a.group == 0) {
         for (uint32_t j = threadIdx.x; j < n; j += SMALL_BLOCK) {
@@ -181,13 +180,19 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
         }
     } else if (a.stride != 0) {   // partial tables (blockfold_kernel's term ranges, or all-gathered per-rank block sums in rank order)
         for (uint32_t j = threadIdx.x; j < n; j += SMALL_BLOCK) {
-            Fr s = load_fr(a.src, j);
-            for (uint32_t g = 1; g < a.group; g += 8) {      // up to 8 loads in flight (the serial kernel's prologue is latency)
+            // every partial of an entry in ONE batch of 8 loads (the serial kernel's prologue is latency; blockfold_kernel leaves <= 8
+            // tables).  No load hangs on a branch: a slot past the last partial reads the last one again and is not added.
+            Fr s;
+            for (uint32_t g = 0; g < a.group; g += 8) {
                 Fr v[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) if (g + u < a.group) v[u] = load_fr(a.src, (size_t)(g + u) * a.stride + j);
+                for (int u = 0; u < 8; ++u) {
+                    const uint32_t gu = g + u < a.group ? g + u : a.group - 1;
+                    v[u] = load_fr(a.src, (size_t)gu * a.stride + j);
+                }
+                if (g == 0) s = v[0];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) if (g + u < a.group) s = s + v[u];
+                for (int u = 0; u < 8; ++u) if (g + u < a.group && g + u != 0) s = s + v[u];
             }
             tree0[n + j] = a.canon ? s : fr_from_mont_outlined(s);
         }
@@ -295,7 +300,17 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
     // where every instruction it issues is one the hash waits for: it only records the round's outputs, which nobody in this
     // kernel reads, and at the lowest priority.
     constexpr uint32_t FIRST_HELPER = 192, N_HELPERS = SMALL_BLOCK - FIRST_HELPER - 64, OUT_WAVE = 4;
-    if (wave == OUT_WAVE) __builtin_amdgcn_s_setprio(0);
+    if (wave == OUT_WAVE) {
+        __builtin_amdgcn_s_setprio(0);
+        // what earlier kernels of this proof recorded -- sum, round polynomials and challenges of rounds < round0 -- goes to the pinned
+        // mirror from here: no wave on the path issues these stores (they cross PCIe) or waits behind them
+        if (a.host_delta && a.round0) {
+            for (uint32_t i = threadIdx.x - 64 * OUT_WAVE; i < 12 * a.round0 + 4; i += 64) {
+                const uint64_t* p = i < 4 ? st->sum + i : i < 4 + 8 * a.round0 ? round_polys + (i - 4) : challenges + (i - 4 - 8 * a.round0);
+                *const_cast<uint64_t*>(p + a.host_delta) = *p;
+            }
+        }
+    }
     for (uint32_t it = 0; it < a.n_rounds; ++it) {
         Fr* told = (it & 1) ? tree1 : tree0;
         Fr* tnew = (it & 1) ? tree0 : tree1;
@@ -402,7 +417,13 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
         ++round;
     }
     ZK_STAMP_AT(0, 40 + a.round0, 2);                   // rounds done
+    // the output wave alone wrote to the mirror: its stores are out (system scope) before the barrier, the word follows behind it
+    if (a.seq_word && wave == OUT_WAVE) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
     __syncthreads();
+    if (a.seq_word && threadIdx.x == 64 * OUT_WAVE) {
+        __hip_atomic_store(a.seq_word, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        ZK_STAMP_AT(64 * OUT_WAVE, 40 + a.round0, 3);   // the proof is the host's
+    }
     if (threadIdx.x == 0 && a.n_rounds) {   // what FiatShamirTranscript holds after a challenge(): fresh hasher + the digest
         Transcript tr;
         tr.init();

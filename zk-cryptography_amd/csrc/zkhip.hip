@@ -749,6 +749,8 @@ struct ProofRun {
     SumcheckDev* st;
     uint64_t *d_rp, *d_ch, *d_fin;
     long long host_delta;                    // the proof leaves through the LAST serial kernel: it writes [sum .. round polynomials] into the pinned slot itself (SmallArgs::host_delta)
+    uint64_t seq;                            // ... and then stores `seq` into the slot's sequence word, which the collector spins on (zkhip_ctx::wait_proof)
+    uint64_t* seq_word;
     uint32_t round;                          // rounds enqueued so far
     const uint64_t *h_claimed, *d_claimed;   // read by the launch of round 0 only (the host's pointer is the caller's: dead in a deferred half)
     // the next k rounds of the proof, on a working table of 2^k entries
@@ -761,7 +763,7 @@ struct ProofRun {
     // ... which are the last ones
     SmallArgs closing_rounds(const uint64_t* src, uint32_t group, uint32_t stride, uint32_t canon, uint32_t k) {
         SmallArgs a = rounds(src, group, stride, canon, k, nullptr);
-        a.final_out = d_fin; a.host_delta = host_delta;
+        a.final_out = d_fin; a.host_delta = host_delta; a.seq = seq; a.seq_word = seq_word;
         return a;
     }
 };
@@ -792,6 +794,8 @@ static int proof_setup(zkhip_ctx* c, size_t n, bool overlap, const uint64_t* h_c
     p.d_fin = small + ZK_SMALL_RES;
     ZK_TRY(c->ensure_proof_slot(slot));
     p.host_delta = ((long long)(intptr_t)c->proof_pin[slot].get() - (long long)(intptr_t)(small + ZK_SMALL_STATE)) / 8;
+    p.seq = ++c->proof_seq[slot];               // per enqueued proof, never reset: a proof that fails to enqueue just leaves a value nobody stores
+    p.seq_word = c->proof_word(slot);
     p.h_claimed = h_claimed_sum; p.d_claimed = d_claimed_sum;
     return ZKHIP_OK;
 }
@@ -936,8 +940,17 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
     if (lane < 0 && tail_stream != c->stream) ZK_HIP(c, hipStreamWaitEvent(c->stream, c->proof_ev[slot].get(), 0));
     return ZKHIP_OK;
 }
-static int sumcheck_collect(zkhip_ctx* c, int slot, uint32_t n_vars, uint64_t* h_sum, uint64_t* h_round_polys, uint64_t* h_challenges) {
-    const int wrc = c->wait_event(c->proof_ev[slot].get());
+// by_word: the synchronous call, whose caller waits for THIS proof and nothing else.  A proof in flight is collected by its event as
+// before: prove_end joins the caller's stream to the proof right after (hipStreamWaitEvent), and with the event not yet signalled that
+// join becomes a real barrier in front of the next tables' streaming passes -- measured, 0.2018 against 0.1969 ms per proof with six
+// in flight (profiles/serial_path/NOTES.md).
+static int sumcheck_collect(zkhip_ctx* c, int slot, uint32_t n_vars, uint64_t* h_sum, uint64_t* h_round_polys, uint64_t* h_challenges, bool by_word) {
+    // The sequence word says the mirror is complete while the last kernel may still be writing its transcript state and final table and
+    // its event is not signalled yet.  Nothing below or after this call relies on that kernel being over: the coarse sums were read by
+    // the proof's FIRST serial kernel, which the last one follows; the device scratch, the workspace and the mirror are reused in stream
+    // order only (the caller's stream waits for proof_ev, a lane's next proof begins behind it, a growing workspace synchronises its
+    // streams first), and zkhip_ctx_synchronize / zkhip_ctx_destroy drain the streams themselves.
+    const int wrc = by_word ? c->wait_proof(slot) : c->wait_event(c->proof_ev[slot].get());
     c->release_coarse(slot);                    // the proof's kernels are done with their coarse sums (or the device is lost)
     ZK_TRY(wrc);
     const uint64_t* pin = (const uint64_t*)c->proof_pin[slot].get();
@@ -973,7 +986,7 @@ extern "C" int zkhip_sumcheck_prove(zkhip_ctx* c, const uint64_t* d_evals, size_
         return ZKHIP_OK;
     }
     ZK_TRY(sumcheck_enqueue(c, d_evals, n, h_claimed_sum, d_claimed_sum, d_block_sums, log_blocks, 0, -1));
-    return sumcheck_collect(c, 0, n_vars, h_sum, h_round_polys, h_challenges);
+    return sumcheck_collect(c, 0, n_vars, h_sum, h_round_polys, h_challenges, true);
 }
 // Sumcheck::prove in flight: begin enqueues the whole proof and returns a ticket, end waits for it and delivers the outputs of
 // zkhip_sumcheck_prove.  Up to eight proofs of tables with >= 2 entries may be in flight, each on streams and buffers of its own
@@ -1009,7 +1022,7 @@ extern "C" int zkhip_sumcheck_prove_end(zkhip_ctx* c, uint32_t ticket, uint64_t*
         }
     }
     if (rc == ZKHIP_OK) {
-        if (h_sum && h_round_polys && h_challenges) rc = sumcheck_collect(c, (int)ticket, n_vars, h_sum, h_round_polys, h_challenges);
+        if (h_sum && h_round_polys && h_challenges) rc = sumcheck_collect(c, (int)ticket, n_vars, h_sum, h_round_polys, h_challenges, false);
         else { rc = c->wait_event(c->proof_ev[ticket].get()); c->release_coarse((int)ticket); }   // abandoned: just wait it out
         if (hipStreamWaitEvent(c->stream, c->proof_ev[ticket].get(), 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // the caller's stream is ordered behind the proof again
     }
