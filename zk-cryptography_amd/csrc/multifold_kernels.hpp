@@ -19,6 +19,7 @@
 #pragma once
 #include "sumcheck_kernels.hpp"
 #include "wide_acc.hpp"
+#include "affine_step.hpp"
 
 namespace zk {
 
@@ -148,12 +149,18 @@ constexpr int SMALL_BLOCK = 512;   // 8 waves: the transcript wave, two schedule
 // node is independent work.
 // The tree is kept in CANONICAL (non-Montgomery) form: the transcript absorbs canonical bytes, so (lo, hi) need no
 // conversion, and a product of a Montgomery-form challenge with a canonical difference is again canonical.
-// Wave 0 runs nothing but the transcript chain plus ONE product per round (challenge_canonical * E, where
-// E = to_mont(hi' - lo') was prepared a round earlier); waves 1 and 2 prepare the message schedules of the next round's
-// two SHA-256 blocks and nothing else (with tree work on top they were the last to reach the barrier); waves 3-7 convert
-// the challenge, fold the rest of the tree and the k-variable fold weights, and write the outputs (Montgomery form).
-// One barrier per round; the trees, E and the challenge slot are double-buffered.  (Stamps of a 2^24 prove,
-// tools/diag_small.py: a round = 2 x 2.1 us of state rounds + 0.9 us for the product + 0.3 us to publish.)
+// Wave 0 runs nothing but the transcript chain plus the round's closing step lo' = t[4] + c * (t[6] - t[4]).  That step is no
+// Montgomery product any more: twenty lanes of the last helper wave have spent the round on a table of the digit multiples
+// (t[6] - t[4]) * 2^(28 k), and behind the digest one limb per lane is ten multiply-adds, one quotient word and a carry resolved by
+// ballots (affine_step.hpp); the digest is published raw, and whoever needs the challenge as a field element reduces it for itself.
+// The table's operand is itself one challenge old: D = X + c Y with X, Y from level 3 of the old tree, so the builders need two
+// products behind the barrier and none of them waits for a conversion of c.  Waves 1 and 2 take the same step for their copies
+// of lo' / hi' and prepare the message schedules of the next round's two SHA-256 blocks and nothing else (with tree work on top
+// they were the last to reach the barrier); waves 3, 5, 6, 7 fold the tree and the k-variable fold weights; wave 4 writes the
+// outputs (Montgomery form; three conversions on three lanes).  The first round of a launch has no table and multiplies by
+// E = to_mont(t[6] - t[4]) from the prologue.  One barrier per round; the trees, the tables and the digest slot are double-buffered.
+// (Stamps of a 2^24 prove, tools/diag_small.py, measured: a steady round = 1.50 + 1.46 us of state rounds + 0.53 us for the step
+// (was 0.94 for the product) + 0.23 us to publish and pass the barrier = 3.87 us, was 4.53; profiles/serial_rounds/NOTES.md.)
 static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(SmallArgs a, SumcheckDev* st,
                                                                             uint64_t* __restrict__ round_polys,
                                                                             uint64_t* __restrict__ challenges) {
@@ -170,8 +177,7 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
     Fr* w1 = w0 + ((a.n_rounds & 1) ? w_all / 2 : w_all);
     const bool grouped = a.group != 0 && a.stride == 0;
     Fr* scratch = w0 + w_all + w_all / 2 + 1;           // SMALL_BLOCK entries, only in the grouped mode
-    Fr* e_sh = scratch + (grouped ? SMALL_BLOCK : 0);   // 2 x 2: to_mont(level-2 differences) of tree0 / tree1
-    Fr* r_sh = e_sh + 4;                                // 2: canonical challenge, double-buffered
+    Fr* e_sh = scratch + (grouped ? SMALL_BLOCK : 0);   // 2: to_mont(level-2 differences) of tree0, for the first round's product
     // ---- leaves (sums are taken as they come -- the conversion to canonical integers is linear -- then converted once)
     if (a.group == 0) {
         for (uint32_t j = threadIdx.x; j < n; j += SMALL_BLOCK) {
@@ -254,10 +260,12 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
     // (sha256_schedule_to_lds), both from their own copy of lo / hi, one round ahead of the hash.
     const uint32_t wave = threadIdx.x >> 6;
     const bool wave0 = wave == 0;
-    uint32_t* kw1 = reinterpret_cast<uint32_t*>(r_sh + 2);      // 64 words
+    uint32_t* kw1 = reinterpret_cast<uint32_t*>(e_sh + 2);      // 64 words
     uint32_t* kw2 = kw1 + 64;                                   // 64 words
     uint32_t* dig_sh = kw2 + 64;                                // 2 x 8: raw digest of the last challenge, double-buffered
-    uint32_t* flags = dig_sh + 16;                              // [0]: kw1 progress, [1]: kw2 progress
+    uint32_t* flags = dig_sh + 16;                              // [0]: kw1 progress, [1]: kw2 progress (+ 2 words of padding)
+    uint32_t* aff_sh = flags + 4;                               // 2 x 2 tables of digit multiples (affine_step.hpp), double-buffered
+    Fr* aff_stage = reinterpret_cast<Fr*>(aff_sh + 4 * AFF_TABLE_WORDS);   // 2 x 10: the builders' X * 2^(28 k), one wave's own exchange
     if (threadIdx.x >= 64 && threadIdx.x < 66 && a.log_n >= 2)
         e_sh[threadIdx.x - 64] = (tree0[6 + threadIdx.x - 64] - tree0[4 + threadIdx.x - 64]).to_mont();
     if (threadIdx.x == 0) {
@@ -277,23 +285,41 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
         for (int i = 0; i < 8; ++i) dig_sh[8 + i] = pre[i];     // slot (it - 1) & 1 for it = 0
     }
     __syncthreads();
-    Fr lo = tree0[2], hi = tree0[3];     // canonical
+    // the round polynomial's lo (canonical) as the hash wave keeps it: limbs in registers that no lane-indexed read ever touches (an
+    // element read through fr_limb_by_lane lives in scratch, and a round trip through scratch per round was on the path)
+    uint32_t low[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) low[i] = tree0[2].l[i];
     uint32_t depth = a.log_n, round = a.round0, n_w = 1;
     ZK_STAMP_AT(0, 40 + a.round0, 1);                   // prologue done
     // schedules of round 0 (waves 1 and 2)
     // (a word per lane: lane i of every row holds word i of the block -- sha256_schedule_rows_to_lds)
     const uint32_t word = threadIdx.x & 15;
-    auto schedule_block1 = [&](const uint32_t* prefix, const Fr& lo_c, uint32_t it) {
-        const uint32_t w = word < 8 ? prefix[word] : fr_limb_by_lane(lo_c, 15 - word);
+    // (lo_w: lanes 8 .. 15 of a row hold limb 15 - word of lo; hi_w: lanes 0 .. 7 hold limb 7 - word of hi)
+    auto schedule_block1_words = [&](const uint32_t* prefix, uint32_t lo_w, uint32_t it) {
+        const uint32_t w = word < 8 ? prefix[word] : lo_w;
         sha256_schedule_rows_to_lds(w, kw1, flags, 4 * it, 1, threadIdx.x < 64 + 16);
     };
-    auto schedule_block2 = [&](const Fr& hi_c, uint32_t it) {
-        const uint32_t w = word < 8 ? fr_limb_by_lane(hi_c, 7 - word) : (word == 8 ? 0x80000000u : word == 15 ? 96u * 8u : 0u);
+    auto schedule_block2_words = [&](uint32_t hi_w, uint32_t it) {
+        const uint32_t w = word < 8 ? hi_w : (word == 8 ? 0x80000000u : word == 15 ? 96u * 8u : 0u);
         sha256_schedule_rows_to_lds(w, kw2, flags + 1, 4 * it, 0, threadIdx.x < 128 + 16);
     };
+    auto schedule_block1 = [&](const uint32_t* prefix, const Fr& lo_c, uint32_t it) {
+        schedule_block1_words(prefix, fr_limb_by_lane(lo_c, 15 - word), it);
+    };
+    auto schedule_block2 = [&](const Fr& hi_c, uint32_t it) { schedule_block2_words(fr_limb_by_lane(hi_c, 7 - word), it); };
+    AffineLane aff;                                     // this lane's limb of r and of 2^256 - r, for the rounds' closing step
+    aff.init();
+    // The table builders: lanes of the last helper wave, per value (lo', hi': b_v2) and digit (b_k) one lane of each half wave.  The
+    // first half's lanes take the part of the table that waits for the challenge, the second half's the part that does not; every
+    // builder keeps its one constant (a power of 2^28 in the Montgomery form its part needs) in registers for the whole launch.
+    const uint32_t bl = threadIdx.x - (SMALL_BLOCK - 64);
+    const bool builder = bl < 64 && (bl & 31) < 2 * AFF_DIGITS;
+    const uint32_t b_free = bl >> 5, b_v2 = (bl & 31) >= (uint32_t)AFF_DIGITS ? 1u : 0u, b_k = (bl & 31) - AFF_DIGITS * b_v2;
+    const Fr b_pow = affine_pow_mont(builder ? b_k + AFF_DIGITS * (1 - b_free) : 0u);
     if (a.n_rounds) {
-        if (wave == 1) schedule_block1(dig_sh + 8, lo, 0);
-        if (wave == 2) schedule_block2(hi, 0);
+        if (wave == 1) schedule_block1_words(dig_sh + 8, tree0[2].l[(15 - word) & 7], 0);
+        if (wave == 2) schedule_block2_words(tree0[3].l[(7 - word) & 7], 0);
     }
     uint32_t digest[8];
     // Waves 3, 5, 6, 7 fold the trees and the weights.  Wave 4 sits on the transcript wave's SIMD (waves go round the four SIMDs),
@@ -316,8 +342,10 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
         Fr* tnew = (it & 1) ? tree0 : tree1;
         Fr* wold = (it & 1) ? w1 : w0;
         Fr* wnew = (it & 1) ? w0 : w1;
-        Fr* eold = e_sh + 2 * (it & 1);
-        Fr* enew = e_sh + 2 * ((it & 1) ^ 1);
+        // the tables of digit multiples of this round's level-2 differences were built a round ago (never for the first round here)
+        uint32_t* tbl_old = aff_sh + 2 * AFF_TABLE_WORDS * (it & 1);
+        uint32_t* tbl_new = aff_sh + 2 * AFF_TABLE_WORDS * ((it & 1) ^ 1);
+        const bool tabled = it != 0;
         const bool absorb_sum = a.first && it == 0;
         if (wave0) {
             ZK_STAMP_AT(0, round, 0);
@@ -325,7 +353,7 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
             uint32_t blk[16];
             const uint32_t* pre = dig_sh + 8 * ((it + 1) & 1);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { blk[i] = pre[i]; blk[8 + i] = lo.l[7 - i]; }
+            for (int i = 0; i < 8; ++i) { blk[i] = pre[i]; blk[8 + i] = low[7 - i]; }
             ShaSplit sp;                                              // the state rounds on six lanes (transcript.hpp)
             sp.init();
             uint32_t hs[4];
@@ -337,70 +365,111 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
             ZK_STAMP_AT(0, round, 2);
 #pragma unroll
             for (int i = 0; i < 8; ++i) digest[i] = h[i];
-            Fr c;                                                    // from_be_bytes_mod_order, still canonical
-#pragma unroll
-            for (int i = 0; i < 8; ++i) c.l[i] = h[7 - i];
-            c.reduce_once();
-            c.reduce_once();
-            if (threadIdx.x == 0) {
-                r_sh[it & 1] = c;
+            if (threadIdx.x == 0) {   // the raw digest: whoever needs the challenge (from_be_bytes_mod_order) reduces it for itself
 #pragma unroll
                 for (int i = 0; i < 8; ++i) dig_sh[8 * (it & 1) + i] = h[i];
             }
         }
         ZK_STAMP_AT(0, round, 3);
-        ZK_STAMP_AT(SMALL_BLOCK - 1, round, 6);      // the last helper arrives at the barrier
+        ZK_STAMP_AT(SMALL_BLOCK - 1, round, 6);      // the last helper -- the wave that builds the tables -- arrives at the barrier
         ZK_STAMP_AT(64, round, 7);                   // the first schedule wave arrives
-        __syncthreads();   // challenge and digest published; tree `told` and `eold` complete
+        __syncthreads();   // digest published; tree `told` and the tables `tbl_old` complete
         ZK_STAMP_AT(0, round, 4);
-        const Fr c = r_sh[it & 1];
+        // the digest as an integer (little-endian limbs): wave 0 has it in registers, everybody else reads the slot
+        uint32_t dl[8];
         if (wave0) {
-            if (depth >= 2) {   // next round polynomial straight from level 2 of the old tree: lo' = t[4] + c * (t[6] - t[4])
-                const uint32_t q = threadIdx.x & 1;
-                Fr v = told[4 + q] + fr_mul_outlined(c, eold[q]);
-                lo = shfl_fr(v, 0);
-                hi = shfl_fr(v, 1);
-            }
-            ZK_STAMP_AT(0, round, 5);
-        } else if (wave <= 2) {
-            // schedules of the NEXT round (its hash is already waiting for them)
-            if (it + 1 < a.n_rounds && depth >= 2) {
-                const uint32_t q = wave - 1;                         // wave 1: lo', wave 2: hi'
-                const Fr v = told[4 + q] + fr_mul_outlined(c, eold[q]);
-                if (wave == 1) schedule_block1(dig_sh + 8 * (it & 1), v, it + 1);
-                else schedule_block2(v, it + 1);
-            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dl[i] = digest[7 - i];
         } else {
-            const Fr r = fr_to_mont_outlined(c);       // every helper wave converts for itself (no extra sync)
-            const uint32_t helper = wave == OUT_WAVE ? N_HELPERS : wave < OUT_WAVE ? threadIdx.x - FIRST_HELPER : threadIdx.x - FIRST_HELPER - 64;
-            if (threadIdx.x == 64 * OUT_WAVE) {   // outputs of this round, in Montgomery form as the reference holds them
-                Fr lo_m = told[2].to_mont(), hi_m = told[3].to_mont();
-                if (absorb_sum) {
-                    Fr sum_m = (a.first == 2) ? fr_from_arg(a.claimed) : (a.first == 3) ? load_fr(a.d_claimed, 0) : lo_m + hi_m;
-                    store_fr(st->sum, 0, sum_m);
-                    if (a.host_delta) store_fr(st->sum + a.host_delta, 0, sum_m);
-                }
-                store_fr(round_polys, 2 * (size_t)round, lo_m);
-                store_fr(round_polys, 2 * (size_t)round + 1, hi_m);
-                store_fr(challenges, round, r);
-                if (a.host_delta) {
-                    store_fr(round_polys + a.host_delta, 2 * (size_t)round, lo_m);
-                    store_fr(round_polys + a.host_delta, 2 * (size_t)round + 1, hi_m);
-                    store_fr(challenges + a.host_delta, round, r);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dl[i] = dig_sh[8 * (it & 1) + 7 - i];
+        }
+        auto challenge_canonical = [&]() {
+            Fr c;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c.l[i] = dl[i];
+            c.reduce_once();
+            c.reduce_once();
+            return c;
+        };
+        if (wave <= 2) {
+            // Next round polynomial straight from level 2 of the old tree: lo' = t[4] + c * (t[6] - t[4]), hi' likewise from t[5], t[7].
+            // Wave 0 (the next block 1's words 8 .. 15) and wave 1 (its schedule) take lo', wave 2 hi' (block 2's schedule; its hash is
+            // already waiting for them).  One limb per lane from the table (affine_step.hpp); the first round of a launch, which has no
+            // table, multiplies as before.
+            const uint32_t q = wave == 2 ? 1u : 0u;
+            if (depth >= 2 && (wave0 || it + 1 < a.n_rounds)) {
+                if (tabled) {
+                    uint32_t dg[AFF_DIGITS];
+                    affine_digits(dl, dg);
+                    const uint32_t limb = affine_step_rows(aff, told[4 + q].l[word & 7], tbl_old + AFF_TABLE_WORDS * q, dg);
+                    if (wave0) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) low[i] = __builtin_amdgcn_readlane(limb, i);
+                    } else if (wave == 1) {
+                        schedule_block1_words(dig_sh + 8 * (it & 1), aff_row_mirror(limb), it + 1);
+                    } else {
+                        schedule_block2_words(aff_row_half_mirror(limb), it + 1);
+                    }
+                } else {
+                    const Fr v = told[4 + q] + fr_mul_outlined(challenge_canonical(), e_sh[q]);
+                    if (wave0) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) low[i] = v.l[i];
+                    } else {
+                        const Fr vs = v;                             // the copy the lane-indexed reads go to
+                        if (wave == 1) schedule_block1(dig_sh + 8 * (it & 1), vs, it + 1);
+                        else schedule_block2(vs, it + 1);
+                    }
                 }
             }
+            if (wave0) ZK_STAMP_AT(0, round, 5);
+        } else {
+            const Fr c = challenge_canonical();
+            const uint32_t helper = wave == OUT_WAVE ? N_HELPERS : wave < OUT_WAVE ? threadIdx.x - FIRST_HELPER : threadIdx.x - FIRST_HELPER - 64;
             const uint32_t nodes = 1u << (depth - 1);   // the new tree has nodes 1 .. 2*nodes - 1
-            if (helper >= N_HELPERS - 2 && helper < N_HELPERS && depth >= 3) {
-                // the last two lanes of the last helper wave: new level 2 pair (q, q+2) and the product wave 0 will need next round
-                const uint32_t q = 4 + (helper - (N_HELPERS - 2));
-                Fr va = told[q + 4] + r * (told[q + 8] - told[q + 4]);           // new[q],   p = 4
-                Fr vb = told[q + 6] + r * (told[q + 10] - told[q + 6]);          // new[q+2], p = 4
-                tnew[q] = va;
-                tnew[q + 2] = vb;
-                enew[helper - (N_HELPERS - 2)] = (vb - va).to_mont();
+            // every helper wave converts the challenge for itself (no extra sync) -- if one of its lanes has a use for it
+            Fr r = c;
+            if (helper < N_HELPERS && (1 + helper < 2 * nodes || (a.weights_out && helper < n_w))) r = fr_to_mont_outlined(c);
+            if (wave == OUT_WAVE) {
+                // Outputs of this round, in Montgomery form as the reference holds them: the challenge, lo and hi, one conversion each on
+                // three lanes side by side -- one product's worth of issue slots on the hash wave's SIMD, not three (with the rounds
+                // shorter, three made this wave the last at the barrier).
+                const uint32_t ol = threadIdx.x - 64 * OUT_WAVE;
+                Fr m = ol == 1 ? told[2] : ol == 2 ? told[3] : c;
+                if (ol < 3) m = fr_to_mont_outlined(m);
+                if (absorb_sum) {
+                    const Fr hi_m = shfl_fr(m, 2);
+                    if (ol == 1) {
+                        Fr sum_m = (a.first == 2) ? fr_from_arg(a.claimed) : (a.first == 3) ? load_fr(a.d_claimed, 0) : m + hi_m;
+                        store_fr(st->sum, 0, sum_m);
+                        if (a.host_delta) store_fr(st->sum + a.host_delta, 0, sum_m);
+                    }
+                }
+                if (ol < 3) {
+                    uint64_t* dst = ol == 0 ? challenges + 4 * (size_t)round : round_polys + 4 * (2 * (size_t)round + ol - 1);
+                    store_fr(dst, 0, m);
+                    if (a.host_delta) store_fr(dst + a.host_delta, 0, m);
+                }
+            }
+            if (builder && depth >= 3) {
+                // The tables the closing step of the NEXT round reads: digit multiples of D = new[q+2] - new[q], the new tree's level-2
+                // difference.  With new[q] = old[q+4] + c (old[q+8] - old[q+4]) and new[q+2] = old[q+6] + c (old[q+10] - old[q+6]),
+                //     D = X + c Y,  X = old[q+6] - old[q+4],  Y = (old[q+10] - old[q+8]) - X      (level 3 of the old tree),
+                // so T_k = X 2^(28 k) + mont(c, to_mont(Y 2^(28 k))): one round of products for both parts side by side (the lanes of the
+                // two half waves), one more for the part with c -- the canonical c: no conversion in front -- and the table is complete two
+                // product latencies behind the barrier, half a round before the digest that it meets.
+                const uint32_t q = 4 + b_v2;
+                const Fr x = told[q + 6] - told[q + 4];
+                const Fr y = (told[q + 10] - told[q + 8]) - x;
+                const Fr p1 = (b_free ? x : y) * b_pow;
+                Fr* slot = aff_stage + (bl & 31);
+                if (b_free) *slot = p1;
+                const Fr w = c * p1;                                              // (the first half's lanes' is the one that counts)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");           // lanes read what other lanes of the wave wrote
+                if (!b_free) affine_table_store(tbl_new + AFF_TABLE_WORDS * b_v2, b_k, *slot + w);
             }
             for (uint32_t q = 1 + helper; q < 2 * nodes && helper < N_HELPERS; q += N_HELPERS) {
-                if (depth >= 3 && q >= 4 && q < 8) continue;                     // done above
                 const uint32_t p = 1u << (31 - __builtin_clz(q));
                 tnew[q] = told[q + p] + r * (told[q + 2 * p] - told[q + p]);
             }
@@ -442,10 +511,10 @@ static __global__ __launch_bounds__(SMALL_BLOCK) void sumcheck_small_kernel(Smal
     }
 }
 // dynamic LDS of the kernel above: trees (3 x 2^log_n), weights (1.5 x 2^weight_rounds; weight_rounds < 0: none), the
-// grouped mode's scratch, the small shared slots
+// grouped mode's scratch, the small shared slots, the four tables of digit multiples and their builders' exchange
 __host__ __device__ constexpr size_t small_lds_bytes(uint32_t log_n, int weight_rounds, bool grouped) {
     return ((size_t)3 * ((size_t)1 << log_n) + (weight_rounds >= 0 ? 3 * ((size_t)1 << weight_rounds) / 2 : 0u) + 1 +
-            (grouped ? SMALL_BLOCK : 0) + 4 + 2) * 32 + (64 + 64 + 16 + 2) * 4;
+            (grouped ? SMALL_BLOCK : 0) + 2 + 2 * AFF_DIGITS) * 32 + (64 + 64 + 16 + 4 + 4 * AFF_TABLE_WORDS) * 4;
 }
 
 // Fold weights of k known points (MultilinearTrait::evaluation folds variable 0 repeatedly, evaluation_form.rs:162-175):
