@@ -257,6 +257,22 @@ int zkhip_sumcheck_prove_begin(zkhip_ctx *ctx, const uint64_t *d_evals, size_t n
                                const uint64_t *d_claimed_sum, const uint64_t *d_block_sums, uint32_t log_blocks, uint32_t *ticket);
 int zkhip_sumcheck_prove_end(zkhip_ctx *ctx, uint32_t ticket, uint64_t *h_sum, uint64_t *h_round_polys, uint64_t *h_challenges);
 
+/* Sumcheck::prove of `batch` tables of n entries each in one call: h_table_ptrs is a HOST array of `batch` DEVICE pointers (a pointer
+ * may repeat; the tables are only read).  h_claimed_sums[batch][4]: what each transcript absorbs first, as given (zeros reproduce
+ * prove() without poly_sum()); NULL = every proof absorbs its true sum, as after poly_sum().  Outputs per proof as
+ * zkhip_sumcheck_prove, proof after proof: h_sums[batch][4], h_round_polys[batch][n_vars][2][4], h_challenges[batch][n_vars][4];
+ * proof b is bit for bit what zkhip_sumcheck_prove returns for table b and that sum.  n == 1: no rounds, the sums only.
+ * Checks and status codes as zkhip_sumcheck_prove, applied once and before anything is launched or written (ZKHIP_ERR_BUSY while
+ * proofs are in flight or a split-phase session holds the workspace); batch == 0 is ZKHIP_OK and touches nothing.
+ * Tables of 2 .. 2^16 entries: chunks of up to 1024 proofs, each ONE launch of one workgroup per proof
+ * (csrc/sumcheck_batch_kernels.hpp), one copy of the results and one synchronisation on the context's stream.  Tables above 2^12
+ * entries run their first rounds in global memory on a slab of n / 2 entries per proof from the context's workspace; a chunk then
+ * holds as many proofs as 256 MiB of slabs allow, never fewer than 256.  Fewer proofs than that kernel measured faster for (3 up to
+ * 2^6 entries, 4 up to 2^12, 6 up to 2^14, 16 up to 2^16) run as up to eight proofs in flight (zkhip_sumcheck_prove_begin / _end)
+ * inside the call; one proof, tables of one entry and tables above 2^16 entries run zkhip_sumcheck_prove, table after table. */
+int zkhip_sumcheck_prove_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_table_ptrs, size_t n,
+                               const uint64_t *h_claimed_sums, uint64_t *h_sums, uint64_t *h_round_polys, uint64_t *h_challenges);
+
 /* ---- the same prover, split per phase, for a table SHARDED over several GPUs ---------------------
  * The N = n_local * world entries are partitioned by their low index bits: rank g holds entry i = j*world + g
  * at local index j.  Rounds fold variable 0 (the most significant index bit), so every fold is local; per
@@ -330,6 +346,16 @@ int zkhip_composed_element_wise(zkhip_ctx *ctx, int op, const uint64_t *const *h
  * 0..=k per round), h_challenges[n_vars*4]. */
 int zkhip_composed_prove(zkhip_ctx *ctx, const uint64_t *const *h_table_ptrs, uint32_t k, size_t n,
                          uint64_t *h_round_polys, uint64_t *h_challenges);
+/* ComposedSumcheck::prove of `batch` products of k tables of n entries each in one call: h_table_ptrs[batch][k] device pointers (a
+ * pointer may repeat, across proofs and within one; the tables are only read).  Outputs proof after proof in the layouts of
+ * zkhip_composed_prove: h_round_polys[batch][n_vars][k+1][4], h_challenges[batch][n_vars][4]; proof b is bit for bit what
+ * zkhip_composed_prove returns for its tables.  Checks and status codes as zkhip_composed_prove, applied once and before anything is
+ * launched or written; batch == 0 is ZKHIP_OK and touches nothing, and so is n == 1 (no rounds).  k * n <= 2^16 entries run on
+ * the batch kernel, chunked as zkhip_sumcheck_prove_batch (resident from the first round up to k * n = 2^12, a slab of k * n / 2
+ * entries per proof above), from 2 proofs on for k = 2, from 3 for every other k, from 6 above 2^15 entries; everything else runs
+ * zkhip_composed_prove per proof. */
+int zkhip_composed_prove_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_table_ptrs, uint32_t k, size_t n,
+                               uint64_t *h_round_polys, uint64_t *h_challenges);
 /* MultiComposedSumcheckProver::calculate_poly_sum (multi_composed_sumcheck.rs:36-45) */
 int zkhip_multi_composed_sum(zkhip_ctx *ctx, const uint64_t *const *h_table_ptrs, const uint32_t *h_term_sizes,
                              uint32_t n_terms, size_t n, uint64_t *h_sum);

@@ -211,6 +211,26 @@ class Sumcheck {
         ch.resize(nv);
         return {std::move(proof), std::move(ch)};
     }
+    // the proofs of tables of one length in one call (zkhip_sumcheck_prove_batch), each as from prove(); claimed_sums: one per table,
+    // absorbed as given (NULL: every proof absorbs its table's true sum, as poly_sum() + prove() does)
+    static std::vector<std::pair<SumcheckProof, std::vector<Fr>>> prove_batch(const std::vector<Multilinear>& polys, const std::vector<Fr>* claimed_sums = nullptr) {
+        std::vector<std::pair<SumcheckProof, std::vector<Fr>>> out;
+        if (polys.empty()) return out;
+        const size_t B = polys.size(), nv = polys[0].n_vars, m = nv ? nv : 1;
+        for (auto& p : polys) if (p.len() != polys[0].len()) throw Panic("the tables of a batch share their length");
+        if (claimed_sums && claimed_sums->size() != B) throw Panic("one claimed sum per table");
+        std::vector<const uint64_t*> ptrs;
+        for (auto& p : polys) ptrs.push_back(p.device());
+        std::vector<Fr> s(B), rp(2 * m * B), ch(m * B);
+        check(zkhip_sumcheck_prove_batch(ctx(), (uint32_t)B, ptrs.data(), polys[0].len(), claimed_sums ? (*claimed_sums)[0].l : nullptr, s[0].l, rp[0].l, ch[0].l),
+              "sumcheck_prove_batch");
+        for (size_t b = 0; b < B; ++b) {
+            SumcheckProof proof{polys[b], s[b], {}};
+            for (size_t i = 0; i < nv; ++i) proof.univariate_poly.emplace_back(std::vector<Fr>{rp[2 * (b * nv + i)], rp[2 * (b * nv + i) + 1]});
+            out.emplace_back(std::move(proof), std::vector<Fr>(ch.begin() + b * nv, ch.begin() + (b + 1) * nv));
+        }
+        return out;
+    }
   private:
     Multilinear poly_;
     Fr sum_;
@@ -325,6 +345,26 @@ class ComposedSumcheck {
         for (size_t r = 0; r < nv; ++r) proof.round_polys.emplace_back(rp.begin() + r * (k + 1), rp.begin() + (r + 1) * (k + 1));
         ch.resize(nv);
         return {std::move(proof), std::move(ch)};
+    }
+    // the proofs of products of one K and one length in one call (zkhip_composed_prove_batch), each as from prove()
+    static std::vector<std::pair<ComposedSumcheckProof, std::vector<Fr>>> prove_batch(const std::vector<ComposedMultilinear>& polys) {
+        std::vector<std::pair<ComposedSumcheckProof, std::vector<Fr>>> out;
+        if (polys.empty()) return out;
+        if (polys[0].polys.empty()) throw Panic("index out of bounds: the len is 0 but the index is 0");
+        const size_t B = polys.size(), k = polys[0].polys.size(), nv = polys[0].n_vars(), n = polys[0].polys[0].len(), m = nv ? nv : 1;
+        std::vector<const uint64_t*> ptrs;
+        for (auto& p : polys) {
+            if (p.polys.size() != k) throw Panic("the products of a batch share their number of tables");
+            for (auto& t : p.polys) { if (t.len() != n) throw Panic("the tables of a batch share their length"); ptrs.push_back(t.device()); }
+        }
+        std::vector<Fr> rp((k + 1) * m * B), ch(m * B);
+        check(zkhip_composed_prove_batch(ctx(), (uint32_t)B, ptrs.data(), (uint32_t)k, n, rp[0].l, ch[0].l), "composed_prove_batch");
+        for (size_t b = 0; b < B; ++b) {
+            ComposedSumcheckProof proof;
+            for (size_t r = 0; r < nv; ++r) proof.round_polys.emplace_back(rp.begin() + (b * nv + r) * (k + 1), rp.begin() + (b * nv + r + 1) * (k + 1));
+            out.emplace_back(std::move(proof), std::vector<Fr>(ch.begin() + b * nv, ch.begin() + (b + 1) * nv));
+        }
+        return out;
     }
 };
 

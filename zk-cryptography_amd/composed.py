@@ -107,6 +107,29 @@ class ComposedSumcheck:
                                              ch.ctypes.data_as(C.c_void_p)), "composed_prove")
         return ComposedSumcheckProof(self.poly, rp[:nv]), ch[:nv]
 
+    @staticmethod
+    def prove_batch(polys):
+        """The proofs of a list of ComposedMultilinear of one K and one length in one call (zkhip_composed_prove_batch)
+        -> [(ComposedSumcheckProof, challenges)], each as from prove()."""
+        polys = list(polys)
+        if not polys:
+            return []
+        first = polys[0].polys[0]               # (an empty table list: IndexError, as prove() raises)
+        k, nv, n, dev = len(polys[0].polys), first.n_vars, len(first), first.evaluations.device
+        for p in polys:
+            assert len(p.polys) == k, "the products of a batch share their number of tables"
+            assert all(len(t) == n for t in p.polys), "the tables of a batch share their length"
+            assert all(t.evaluations.device == dev for t in p.polys), "the tables of a batch live on one device"
+        B, m = len(polys), max(nv, 1)
+        if B == 1:
+            return [ComposedSumcheck(polys[0]).prove()]
+        rp = np.empty((B, m, k + 1, 4), dtype=np.uint64)
+        ch = np.empty((B, m, 4), dtype=np.uint64)
+        ctx = N.Context.get(dev.index)
+        N.check(N.lib().zkhip_composed_prove_batch(ctx.handle, C.c_uint32(B), _ptr_array([a for p in polys for a in p._ptrs()]), C.c_uint32(k),
+                                                   C.c_size_t(n), rp.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p)), "composed_prove_batch")
+        return [(ComposedSumcheckProof(polys[b], rp[b, :nv]), ch[b, :nv]) for b in range(B)]
+
 
 class SparseUnivariatePolynomial:
     """polynomial/src/univariate/sparse_univariate.rs:12-20: monomials (coeff, pow), both Montgomery uint64[4]."""

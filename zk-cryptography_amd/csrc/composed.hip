@@ -705,6 +705,28 @@ extern "C" int zkhip_composed_prove(zkhip_ctx* c, const uint64_t* const* ptrs, u
                                     uint64_t* h_challenges) {
     return composed_prove_impl(c, ptrs, &k, 1, n, 0, nullptr, 1, nullptr, h_round_polys, h_challenges);
 }
+// ComposedSumcheck::prove of `batch` groups of k tables of one length (include/zkhip.h).  What the batch kernel does not serve
+// (zk_sumcheck_batch_serves: one proof, groups above 2^16 entries) goes through zkhip_composed_prove one after another.
+extern "C" int zkhip_composed_prove_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* ptrs, uint32_t k, size_t n,
+                                          uint64_t* h_round_polys, uint64_t* h_challenges) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!ptrs || k < 1 || k > CMP_MAX_K) return ZKHIP_ERR_ARG;
+    for (size_t q = 0; q < (size_t)batch * k; ++q) if (!ptrs[q]) return ZKHIP_ERR_ARG;
+    if (!is_pow2(n)) return ZKHIP_ERR_SHAPE;
+    const uint32_t n_vars = log2_exact(n);
+    if (n_vars > ZK_MAX_ROUNDS) return ZKHIP_ERR_SHAPE;
+    if (n_vars == 0) return ZKHIP_OK;   // `for _ in 0..n_vars` never runs
+    if (!h_round_polys || !h_challenges) return ZKHIP_ERR_ARG;
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // a split-phase session holds the workspace
+    ZK_TRY(c->activate());
+    if (!zk_sumcheck_batch_serves(batch, false, k, n)) {
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_composed_prove(c, ptrs + (size_t)b * k, k, n, h_round_polys + 4 * (size_t)b * n_vars * (k + 1), h_challenges + 4 * (size_t)b * n_vars));
+        return ZKHIP_OK;
+    }
+    return zk_sumcheck_batch_run(c, batch, ptrs, k, n, false, nullptr, nullptr, h_round_polys, h_challenges);
+}
 extern "C" int zkhip_multi_composed_prove(zkhip_ctx* c, const uint64_t* const* ptrs, const uint32_t* term_sizes,
                                           uint32_t n_terms, size_t n, const uint64_t* h_sum, int partial,
                                           uint32_t* h_lens, uint64_t* h_round_polys, uint64_t* h_challenges) {

@@ -392,6 +392,10 @@ struct ProfScope {
 
 // cross-unit internals (C++ linkage, not part of the C ABI)
 int zk_ntt_scaled_transform(zkhip_ctx* c, const uint64_t* d_src, size_t n_src, const uint64_t* d_mul, uint64_t* d_dst, uint32_t log_n);   // ntt.hip
+// zkhip.hip: a batch of basic (k = 1, absorb_sum) or composed sumcheck proofs through sumcheck_batch_kernels.hpp (see there)
+int zk_sumcheck_batch_run(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_table_ptrs, uint32_t k, size_t n, bool absorb_sum,
+                          const uint64_t* h_claimed_sums, uint64_t* h_sums, uint64_t* h_round_polys, uint64_t* h_challenges);
+bool zk_sumcheck_batch_serves(uint32_t batch, bool basic, uint32_t k, size_t n);   // false: the batched entry points run the single provers
 // msm.hip: one round's commits of a chunk of PLONK proofs on the short path (see there)
 bool zk_msm_commit_batch_serves(size_t n_points, size_t longest);
 int zk_msm_commit_batch(zkhip_ctx* c, const void* d_table_with_header, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_scalars,

@@ -16,6 +16,7 @@
 #include "host_util.hpp"
 #include "mle_kernels.hpp"
 #include "sumcheck_kernels.hpp"
+#include "sumcheck_batch_kernels.hpp"
 #include "multifold_kernels.hpp"
 #include "mfma_fold.hpp"
 #include "tunables.hpp"
@@ -1027,6 +1028,121 @@ extern "C" int zkhip_sumcheck_prove_end(zkhip_ctx* c, uint32_t ticket, uint64_t*
         if (hipStreamWaitEvent(c->stream, c->proof_ev[ticket].get(), 0) != hipSuccess && rc == ZKHIP_OK) rc = ZKHIP_ERR_HIP;   // the caller's stream is ordered behind the proof again
     }
     c->proof_pending[ticket] = 0;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------
+// a batch of proofs in one launch (sumcheck_batch_kernels.hpp): both provers' batched entry points end here
+// ---------------------------------------------------------------------------------------
+// Proofs b0 .. of `batch` tables (basic: k = 1, absorb_sum) or table groups (composed), chunk after chunk.  A chunk is one upload
+// of its table pointers (and claimed sums), one launch of one workgroup per proof, one copy of all results and one synchronisation.
+//   chunk = SCB_CHUNK proofs; with rounds in global memory as many as SCB_SLAB_BYTES of slabs allow, never fewer than SCB_MIN_CHUNK.
+// The caller has checked the arguments: n a power of two >= 2, 1 <= k <= 5, k * n <= SCB_MAX_ENTRIES, batch >= 1.
+bool zk_sumcheck_batch_serves(uint32_t batch, bool basic, uint32_t k, size_t n) {
+    return n >= 2 && (size_t)k * n <= SCB_MAX_ENTRIES && batch >= scb_min_batch(basic, k, n);
+}
+int zk_sumcheck_batch_run(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_table_ptrs, uint32_t k, size_t n, bool absorb_sum,
+                          const uint64_t* h_claimed_sums, uint64_t* h_sums, uint64_t* h_round_polys, uint64_t* h_challenges) {
+    if (k < 1 || k > 5 || n < 2 || (size_t)k * n > SCB_MAX_ENTRIES || (absorb_sum && k != 1)) return ZKHIP_ERR_ARG;
+    const uint32_t n_vars = log2_exact(n);
+    const uint32_t resident_len = scb_resident_len(k, n);
+    const size_t slab_per = resident_len < n ? (size_t)k * (n / 2) * 32 : 0;
+    uint32_t chunk = SCB_CHUNK;
+    if (slab_per) chunk = (uint32_t)std::max<size_t>(SCB_MIN_CHUNK, std::min<size_t>(SCB_CHUNK, SCB_SLAB_BYTES / slab_per));
+    const uint32_t bc_max = std::min(batch, chunk);
+    const uint32_t out_words = scb_out_words(k, n_vars, absorb_sum);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // workspace: [table pointers | claimed sums] (uploaded) [results] [slabs]; pinned: [results] [table pointers | claimed sums]
+    const size_t o_claim = al((size_t)bc_max * k * 8), stage_bytes = o_claim + (h_claimed_sums ? al((size_t)bc_max * 32) : 0);
+    const size_t out_bytes = al((size_t)bc_max * out_words * 8), o_slab = stage_bytes + out_bytes;
+    ZK_TRY(c->reserve_ws(o_slab + (size_t)bc_max * slab_per));
+    ZK_TRY(c->reserve_msm_pin(0, out_bytes + stage_bytes));
+    char* ws = (char*)c->ws.ptr;
+    char* pin = (char*)c->msm_pin[0].ptr;
+    void (*fn)(SumcheckBatchArgs) = nullptr;
+    switch (k) {
+        case 1: fn = absorb_sum ? sumcheck_batch_kernel<1, true> : sumcheck_batch_kernel<1, false>; break;
+        case 2: fn = sumcheck_batch_kernel<2, false>; break;
+        case 3: fn = sumcheck_batch_kernel<3, false>; break;
+        case 4: fn = sumcheck_batch_kernel<4, false>; break;
+        default: fn = sumcheck_batch_kernel<5, false>; break;
+    }
+    const size_t lds = scb_lds_bytes(k, resident_len);
+    ZK_TRY(c->allow_big_lds((const void*)fn, lds > 64 * 1024 ? SCB_MAX_LDS_BYTES : lds));   // raised once per kernel, to the family's largest request
+    SumcheckBatchArgs a = {};
+    a.tables = (const uint64_t* const*)ws;
+    a.claimed = h_claimed_sums ? (const uint64_t*)(ws + o_claim) : nullptr;
+    a.out = (uint64_t*)(ws + stage_bytes);
+    a.slab = (uint64_t*)(ws + o_slab);
+    a.n = (uint32_t)n; a.resident_len = resident_len; a.out_words = out_words;
+    const int block = scb_block(k, n);
+    const size_t rp_words = 4 * (size_t)n_vars * (k + 1), ch_words = 4 * (size_t)n_vars;
+    for (uint32_t b0 = 0; b0 < batch; b0 += bc_max) {
+        const uint32_t bc = std::min(bc_max, batch - b0);
+        // (the previous chunk's upload has ended: every chunk ends in a synchronisation)
+        std::memcpy(pin + out_bytes, h_table_ptrs + (size_t)b0 * k, (size_t)bc * k * 8);
+        if (h_claimed_sums) std::memcpy(pin + out_bytes + o_claim, h_claimed_sums + 4 * (size_t)b0, (size_t)bc * 32);
+        ZK_HIP(c, hipMemcpyAsync(ws, pin + out_bytes, h_claimed_sums ? o_claim + (size_t)bc * 32 : (size_t)bc * k * 8, hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, "sumcheck_batch", 32.0 * (double)k * (double)n * bc);
+            hipLaunchKernelGGL(fn, dim3(bc), dim3(block), lds, c->stream, a);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(pin, a.out, (size_t)bc * out_words * 8, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        for (uint32_t p = 0; p < bc; ++p) {
+            const uint64_t* w = (const uint64_t*)pin + (size_t)p * out_words;
+            if (absorb_sum) { std::memcpy(h_sums + 4 * (size_t)(b0 + p), w, 32); w += 4; }
+            std::memcpy(h_round_polys + (size_t)(b0 + p) * rp_words, w, 8 * rp_words);
+            std::memcpy(h_challenges + (size_t)(b0 + p) * ch_words, w + rp_words, 8 * ch_words);
+        }
+    }
+    return ZKHIP_OK;
+}
+
+// Sumcheck::prove of `batch` tables of one length (include/zkhip.h).  What the batch kernel does not serve (zk_sumcheck_batch_serves:
+// fewer proofs than scb_min_batch, a table of one entry -- no rounds --, tables above SCB_MAX_ENTRIES entries) goes through
+// zkhip_sumcheck_prove one after another.
+extern "C" int zkhip_sumcheck_prove_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_table_ptrs, size_t n,
+                                          const uint64_t* h_claimed_sums, uint64_t* h_sums, uint64_t* h_round_polys, uint64_t* h_challenges) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!h_table_ptrs || !h_sums) return ZKHIP_ERR_ARG;
+    for (uint32_t b = 0; b < batch; ++b) ZK_TRY(sumcheck_check_args(c, h_table_ptrs[b], n));
+    const uint32_t n_vars = log2_exact(n);
+    if (n_vars && (!h_round_polys || !h_challenges)) return ZKHIP_ERR_ARG;
+    for (int s = 0; s < zkhip_ctx::PROOF_SLOTS; ++s) if (c->proof_pending[s]) return ZKHIP_ERR_BUSY;     // proofs in flight own the result slots
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;                                                      // a split-phase session holds the workspace
+    ZK_TRY(c->activate());
+    if (zk_sumcheck_batch_serves(batch, true, 1, n))
+        return zk_sumcheck_batch_run(c, batch, h_table_ptrs, 1, n, true, h_claimed_sums, h_sums, h_round_polys, h_challenges);
+    auto claimed = [&](uint32_t b) { return h_claimed_sums ? h_claimed_sums + 4 * (size_t)b : nullptr; };
+    auto rp = [&](uint32_t b) { return n_vars ? h_round_polys + 8 * (size_t)n_vars * b : nullptr; };
+    auto ch = [&](uint32_t b) { return n_vars ? h_challenges + 4 * (size_t)n_vars * b : nullptr; };
+    if (batch == 1 || n == 1 || n > SCB_MAX_ENTRIES) {     // one after another
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_sumcheck_prove(c, h_table_ptrs[b], n, claimed(b), nullptr, nullptr, 0, h_sums + 4 * (size_t)b, rp(b), ch(b)));
+        return ZKHIP_OK;
+    }
+    // a few proofs of a batchable size: up to PROOF_SLOTS of them in flight, collected in order -- what measured faster than the batch
+    // kernel below scb_min_batch proofs, and faster than one after another from two proofs on
+    constexpr uint32_t W = (uint32_t)zkhip_ctx::PROOF_SLOTS;
+    uint32_t ticket[W], begun = 0, ended = 0;
+    int rc = ZKHIP_OK;
+    while (begun < batch && rc == ZKHIP_OK) {
+        if (begun - ended == W) {
+            rc = zkhip_sumcheck_prove_end(c, ticket[ended % W], h_sums + 4 * (size_t)ended, rp(ended), ch(ended));
+            ++ended;
+            if (rc != ZKHIP_OK) break;
+        }
+        rc = zkhip_sumcheck_prove_begin(c, h_table_ptrs[begun], n, claimed(begun), nullptr, nullptr, 0, &ticket[begun % W]);
+        if (rc == ZKHIP_OK) ++begun;
+    }
+    for (; ended < begun; ++ended) {       // after an error: the proofs still in flight are waited for and dropped
+        const int r = rc == ZKHIP_OK ? zkhip_sumcheck_prove_end(c, ticket[ended % W], h_sums + 4 * (size_t)ended, rp(ended), ch(ended))
+                                     : zkhip_sumcheck_prove_end(c, ticket[ended % W], nullptr, nullptr, nullptr);
+        if (rc == ZKHIP_OK) rc = r;
+    }
     return rc;
 }
 

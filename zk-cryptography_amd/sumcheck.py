@@ -142,3 +142,39 @@ class Sumcheck:
                                           self._log_blocks, base, base + 32, base + 32 + 64 * max(nv, 1))
         N.check(st, "sumcheck_prove")
         return SumcheckProof(self.poly, s, rp), ch
+
+    BATCH_CHUNK = 1024          # csrc/sumcheck_batch_kernels.hpp SCB_CHUNK: proofs per launch of the batch kernel
+
+    @staticmethod
+    def prove_batch(polys, sums=None):
+        """The proofs of a list of tables of one length in one call (zkhip_sumcheck_prove_batch) -> [(SumcheckProof, challenges)],
+        each as from prove().  sums=None: every proof absorbs its table's true sum, as poly_sum() + prove() does; otherwise one
+        claimed sum per table, uint64 [B, 4], absorbed as given (zeros: prove() without poly_sum())."""
+        polys = [p if isinstance(p, Multilinear) else Multilinear(p) for p in polys]
+        if not polys:
+            return []
+        evs = [p.evaluations for p in polys]
+        n, nv, dev = evs[0].shape[0], polys[0].n_vars, evs[0].device
+        assert all(e.shape[0] == n for e in evs), "the tables of a batch share their length"
+        assert all(e.device == dev for e in evs), "the tables of a batch live on one device"
+        B, m = len(polys), max(nv, 1)
+        claimed = None
+        if sums is not None:
+            claimed = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1, 4)
+            assert claimed.shape[0] == B, "one claimed sum per table"
+        if B == 1:      # the single prover, by the single call's own path (both claimed-sum arguments NULL: the true sum)
+            s, rp, ch, base = _proof_buffers(nv)
+            N.check(N.lib().zkhip_sumcheck_prove(polys[0]._ctx.handle, evs[0].data_ptr(), n, claimed.ctypes.data if claimed is not None else None,
+                                                 None, None, 0, base, base + 32, base + 32 + 64 * m), "sumcheck_prove")
+            return [(SumcheckProof(polys[0], s, rp), ch)]
+        s = np.empty((B, 4), dtype=np.uint64)
+        rp = np.empty((B, m, 2, 4), dtype=np.uint64)
+        ch = np.empty((B, m, 4), dtype=np.uint64)
+        ptrs = (C.c_void_p * B)(*[e.data_ptr() for e in evs])
+        st = N.lib().zkhip_sumcheck_prove_batch(polys[0]._ctx.handle, C.c_uint32(B), ptrs, C.c_size_t(n),
+                                                claimed.ctypes.data_as(C.c_void_p) if claimed is not None else None,
+                                                s.ctypes.data_as(C.c_void_p), rp.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p))
+        N.check(st, "sumcheck_prove_batch")
+        if nv:      # (the C layout is [B][n_vars][...]: m == n_vars)
+            return [(SumcheckProof(polys[b], s[b], rp[b]), ch[b]) for b in range(B)]
+        return [(SumcheckProof(polys[b], s[b], rp[b, :0]), ch[b, :0]) for b in range(B)]
