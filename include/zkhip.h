@@ -657,12 +657,14 @@ int zkhip_srs_univariate_g2(zkhip_ctx *ctx, const uint64_t *h_tau, size_t max_de
 /* Prepared second arguments: the 68 Miller-loop line coefficients of each G2 point, zkhip_g2_prepared_bytes(n) bytes for n points.
  *   zkhip_g2_prepare : entry i = point i (for zkhip_pairing_prepared);
  *   zkhip_kzg_prepare: entry 0 = the generator G2, entry i = point i - 1 (n + 1 entries; what the verifiers below take).
- * Both check every finite point: off the twist or outside the prime-order subgroup -> ZKHIP_ERR_ARG.  Synchronous. */
+ * Both check every finite point: off the twist, outside the prime-order subgroup or with an unreduced coordinate (a limb vector that is
+ * not below p) -> ZKHIP_ERR_ARG.  The coordinates of a point flagged at infinity are ignored.  Synchronous. */
 size_t zkhip_g2_prepared_bytes(size_t n);
 int zkhip_g2_prepare(zkhip_ctx *ctx, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, void *d_prepared);
 int zkhip_kzg_prepare(zkhip_ctx *ctx, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, void *d_prepared);
 /* n independent pairings e(P_k, Q_k) -> d_out_gt[72 k] (device).  A point at infinity on either side gives 1; a finite input off its
- * curve or outside the subgroup -> ZKHIP_ERR_ARG.  _prepared takes Q_k as zkhip_g2_prepare's entry k.  Synchronous. */
+ * curve, outside the subgroup or with an unreduced coordinate -> ZKHIP_ERR_ARG (every encoding the call accepts is the canonical one;
+ * the coordinates of a point flagged at infinity are ignored).  _prepared takes Q_k as zkhip_g2_prepare's entry k.  Synchronous. */
 int zkhip_pairing(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy,
                   const uint8_t *d_g2_inf, size_t n, uint64_t *d_out_gt);
 int zkhip_pairing_prepared(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const void *d_prepared, size_t n,
@@ -674,14 +676,18 @@ int zkhip_pairing_prepared(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_
  * The reference's check e(C - v G1, G2) == prod e(pi_i, tau_i G2 - z_i G2) is computed as the equivalent
  *   e(C - v G1 + sum z_i pi_i, G2) * prod e(-pi_i, tau_i G2) == 1:
  * n + 1 Miller loops per opening, one lane each, a product tree and one final exponentiation per opening.
- * n_g2 != n_vars -> ZKHIP_ERR_SHAPE (utils.rs:49-50); a commitment or proof off the curve or outside the subgroup -> ZKHIP_ERR_ARG. */
+ * n_g2 != n_vars -> ZKHIP_ERR_SHAPE (utils.rs:49-50); a finite commitment or proof off the curve, outside the subgroup or with an unreduced
+ * coordinate; an evaluation or point that is not a reduced field element -> ZKHIP_ERR_ARG.  With that status h_ok[b] = 0 for every opening
+ * that holds such an input and h_ok of every other opening is its verdict, as a call without the refused openings returns it.  A refused
+ * SRS point (d_prepared NULL) or a HIP error leaves h_ok all zero; a null argument or ZKHIP_ERR_SHAPE leaves it untouched.  The coordinates
+ * of a point flagged at infinity are ignored. */
 int zkhip_kzg_verify_batch(zkhip_ctx *ctx, size_t batch, uint32_t n_vars, const uint64_t *h_commits_xy,
                            const uint8_t *h_commits_inf, const uint64_t *h_evals, const uint64_t *h_points,
                            const uint64_t *h_proofs_xy, const uint8_t *h_proofs_inf, const uint64_t *d_g2_xy,
                            const uint8_t *d_g2_inf, size_t n_g2, const void *d_prepared, uint8_t *h_ok);
 /* UnivariateKZGInterface::verify (univariate_kzg.rs:83-104), the same shape with one point and one proof per opening:
  * e(C - v G1 + z pi, G2) * e(-pi, tau G2) == 1, tau G2 = powers_of_tau_in_g2[1]; d_prepared = zkhip_kzg_prepare of that one point.
- * n_g2 < 2 -> ZKHIP_ERR_INDEX (the reference indexes [1]). */
+ * n_g2 < 2 -> ZKHIP_ERR_INDEX (the reference indexes [1]); inputs are refused, and h_ok is left, as by zkhip_kzg_verify_batch. */
 int zkhip_univariate_kzg_verify_batch(zkhip_ctx *ctx, size_t batch, const uint64_t *h_commits_xy, const uint8_t *h_commits_inf,
                                       const uint64_t *h_evals, const uint64_t *h_points, const uint64_t *h_proofs_xy,
                                       const uint8_t *h_proofs_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf,

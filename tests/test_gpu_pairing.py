@@ -7,7 +7,11 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pairing_cases as PC  # noqa: E402
 import pairing_model as PM  # noqa: E402
+from pairing_cases import g1_not_in_subgroup as _g1_not_in_subgroup  # noqa: E402
+from pairing_cases import off_twist as _off_twist  # noqa: E402
+from pairing_cases import twist_not_in_subgroup as _twist_not_in_subgroup  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -91,66 +95,6 @@ def test_g2_srs_matches_model(zk):
     assert zk.TrustedSetup.setup(zk.Fr.from_ints(tau)).powers_of_tau_in_g2 is None
 
 
-def _off_twist():
-    q = ((1, 0), (1, 0))                          # 1 != 1 + 4 (u + 1)
-    assert not PM.g2_on_curve(q)
-    return q
-
-
-def _twist_not_in_subgroup():
-    """a point of the twist E'(Fq2) outside the order-r subgroup: try x = i, i + 1, ... until x^3 + b is a square in Fq2"""
-    P = PM.P
-    for i in range(1, 200):
-        x = (i, 1)
-        rhs = PM.f2_add(PM.f2_mul(PM.f2_mul(x, x), x), PM.B2)
-        # sqrt in Fq2 (p = 3 mod 4): a = rhs, alpha = a^((p-3)/4) ...
-        a = rhs
-        a1 = _f2_pow(a, (P - 3) // 4)
-        alpha = PM.f2_mul(a1, PM.f2_mul(a1, a))
-        x0 = PM.f2_mul(a1, a)
-        if alpha == ((P - 1) % P, 0):
-            y = PM.f2_mul((0, 1), x0)
-        else:
-            b = _f2_pow(PM.f2_add((1, 0), alpha), (P - 1) // 2)
-            y = PM.f2_mul(b, x0)
-        if PM.f2_mul(y, y) != rhs:
-            continue
-        q = (x, y)
-        if PM.g2_mul_raw(q, PM.R) is not None:
-            return q
-    raise AssertionError("no point found")
-
-
-def _f2_pow(a, e):
-    r = (1, 0)
-    while e:
-        if e & 1:
-            r = PM.f2_mul(r, a)
-        a = PM.f2_mul(a, a)
-        e >>= 1
-    return r
-
-
-def _g1_not_in_subgroup():
-    P = PM.P
-    for x in range(1, 100):
-        rhs = (x ** 3 + 4) % P
-        y = pow(rhs, (P + 1) // 4, P)
-        if y * y % P == rhs and _g1_mul_raw((x, y), PM.R) is not None:
-            return x, y
-    raise AssertionError("no point found")
-
-
-def _g1_mul_raw(pt, k):
-    acc = None
-    while k:
-        if k & 1:
-            acc = M.g1_add(acc, pt)
-        pt = M.g1_add(pt, pt)
-        k >>= 1
-    return acc
-
-
 def test_invalid_inputs_are_refused(zk):
     from zk_cryptography_amd import kzg as K
     bad2 = [g2(zk, _off_twist()), g2(zk, _twist_not_in_subgroup())]
@@ -165,3 +109,59 @@ def test_invalid_inputs_are_refused(zk):
             zk.pairing([p], [g2(zk, PM.G2)])
     with pytest.raises(AssertionError):
         zk.pairing([g1(zk, M.G1)] * 2, [g2(zk, PM.G2)])
+
+
+def _plus_p(limbs):
+    """the same residue under a second encoding: the limb integer plus p (p < 2^381, so it still fits six words)"""
+    v = sum(int(w) << (64 * k) for k, w in enumerate(limbs)) + PM.P
+    assert v < 1 << 384
+    return [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(6)]
+
+
+def _unreduced(zk, point, coord):
+    """`point` (zk.G1Affine / zk.G2Affine) with coordinate number `coord` stored as c + p"""
+    xy = point.xy.copy()
+    xy[6 * coord: 6 * coord + 6] = _plus_p(xy[6 * coord: 6 * coord + 6])
+    return type(point)(xy, point.infinity)
+
+
+def test_small_order_points_are_refused(zk):
+    """points of order 3 and 11 on E(Fq), 13 and 23 on the twist: on the curve, and what walks the subgroup check through the doubling
+    and inverse branches of the mixed additions (tests/test_pairing_cases_cpu.py)"""
+    from zk_cryptography_amd import kzg as K
+    for pt in PC.g1_small_order_points().values():
+        with pytest.raises(ValueError):
+            zk.pairing([g1(zk, pt)], [g2(zk, PM.G2)])
+        with pytest.raises(ValueError):                       # in a batch, whatever its place
+            zk.pairing([g1(zk, M.G1), g1(zk, pt), g1(zk, None)], [g2(zk, PM.G2)] * 3)
+    for q in PC.g2_small_order_points().values():
+        with pytest.raises(ValueError):
+            zk.pairing([g1(zk, M.G1)], [g2(zk, q)])
+        with pytest.raises(ValueError):
+            K.g2_prepare([g2(zk, PM.G2), g2(zk, q)])
+
+
+def test_unreduced_coordinates_are_refused(zk):
+    """x + p is the same residue as x and would pass the curve equation: refused, so that every point has one accepted encoding"""
+    from zk_cryptography_amd import kzg as K
+    p, q = g1(zk, M.g1_mul(M.G1, 3)), g2(zk, PM.g2_mul(PM.G2, 5))
+    want = zk.pairing([p], [q])
+    for coord in range(2):
+        with pytest.raises(ValueError):
+            zk.pairing([_unreduced(zk, p, coord)], [q])
+        with pytest.raises(ValueError):
+            zk.pairing([_unreduced(zk, p, coord)], prepared=K.g2_prepare([q]))
+    for coord in range(4):
+        with pytest.raises(ValueError):
+            zk.pairing([p], [_unreduced(zk, q, coord)])
+        with pytest.raises(ValueError):
+            K.g2_prepare([_unreduced(zk, q, coord)])
+    full = np.full(12, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)       # 2^384 - 1: far outside what the field product is stated for
+    with pytest.raises(ValueError):
+        zk.pairing([zk.G1Affine(full, False)], [q])
+    # the coordinates of a point flagged at infinity are ignored: still the neutral element, still no error
+    one = [1] + [0] * 11
+    assert zk.gt_ints(zk.pairing([zk.G1Affine(full, True)], [q])[0]) == one
+    assert zk.gt_ints(zk.pairing([p], [zk.G2Affine(np.concatenate([full, full]), True)])[0]) == one
+    K.g2_prepare([zk.G2Affine(np.concatenate([full, full]), True)])
+    assert np.array_equal(zk.pairing([p], [q]), want)

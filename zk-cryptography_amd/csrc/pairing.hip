@@ -47,7 +47,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void g2_power_scalars_kernel(const uint
 }
 
 // The 68 Miller-loop lines of each G2 point (entry i of `prep`, PREP_STRIDE_U64 words).  gen_first: entry 0 is the generator's and
-// entry i >= 1 that of input point i - 1 (the layout zkhip_kzg_prepare writes).  bad[i] = 1: off the twist or not in the subgroup.
+// entry i >= 1 that of input point i - 1 (the layout zkhip_kzg_prepare writes).  bad[i] = 1: finite and not a valid G2 element (g2_point_valid).
 __global__ __launch_bounds__(PAIR_BLOCK) void g2_prepare_kernel(const uint64_t* __restrict__ xy, const uint8_t* __restrict__ inf,
                                                                 size_t n_entries, int gen_first, uint64_t* __restrict__ prep,
                                                                 uint8_t* __restrict__ bad) {
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void g2_prepare_kernel(const uint64_t* 
         const size_t j = gen_first ? i - 1 : i;
         at_inf = inf && inf[j];
         q = load_g2(xy, j);
-        if (!at_inf) ok = g2_on_curve(q) && g2_in_subgroup(q);
+        if (!at_inf) ok = g2_point_valid(q);
     }
     bad[i] = ok ? 0 : 1;
     out[PAIR_LINES * PREP_LINE_U64] = at_inf || !ok ? 1 : 0;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void g2_prepare_kernel(const uint64_t* 
     }
 }
 
-// G1 / G2 inputs of zkhip_pairing: bad[i] = 1 when a finite point is off its curve or outside the subgroup
+// G1 / G2 inputs of zkhip_pairing: bad[i] = 1 when a finite point is off its curve, outside the subgroup or has an unreduced coordinate
 __global__ __launch_bounds__(PAIR_BLOCK) void pairing_check_kernel(const uint64_t* __restrict__ g1_xy, const uint8_t* __restrict__ g1_inf,
                                                                    const uint64_t* __restrict__ g2_xy, const uint8_t* __restrict__ g2_inf,
                                                                    size_t n, uint8_t* __restrict__ bad) {
@@ -89,11 +89,11 @@ __global__ __launch_bounds__(PAIR_BLOCK) void pairing_check_kernel(const uint64_
     bool ok = true;
     if (!(g1_inf && g1_inf[i])) {
         const G1Affine p = load_affine(g1_xy, i);
-        ok = g1_on_curve(p) && g1_in_subgroup(p);
+        ok = g1_point_valid(p);
     }
     if (ok && g2_xy && !(g2_inf && g2_inf[i])) {
         const G2Affine q = load_g2(g2_xy, i);
-        ok = g2_on_curve(q) && g2_in_subgroup(q);
+        ok = g2_point_valid(q);
     }
     bad[i] = ok ? 0 : 1;
 }
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(PAIR_BLOCK) void final_exp_kernel(const uint64_t* _
 }
 
 // Per opening b and term j (m = n + 1 terms):  j = 0: C - v G1;  j >= 1: z_j pi_j (XYZZ, summed by kzg_combine_kernel), and the
-// pairing's G1 argument -pi_j of that term.  bad[b m + j] = 1: C / pi_j off the curve or outside the subgroup.
+// pairing's G1 argument -pi_j of that term.  bad[b m + j] = 1: C / pi_j finite and off the curve, outside the subgroup or with an unreduced
+// coordinate, or v / z_j not a reduced field element.  A refused term contributes the identity: none of its limbs reaches a product.
 __global__ __launch_bounds__(PAIR_BLOCK) void kzg_terms_kernel(const uint64_t* __restrict__ commits, const uint8_t* __restrict__ commits_inf,
                                                                const uint64_t* __restrict__ evals, const uint64_t* __restrict__ points,
                                                                const uint64_t* __restrict__ proofs, const uint8_t* __restrict__ proofs_inf,
@@ -158,21 +159,20 @@ __global__ __launch_bounds__(PAIR_BLOCK) void kzg_terms_kernel(const uint64_t* _
     const size_t b = t / m, j = t % m;
     const bool at_inf = j == 0 ? commits_inf[b] != 0 : proofs_inf[b * n + j - 1] != 0;
     const G1Affine pt = j == 0 ? load_affine(commits, b) : load_affine(proofs, b * n + j - 1);
-    const bool ok = at_inf || (g1_on_curve(pt) && g1_in_subgroup(pt));
+    const Fr k = j == 0 ? load_fr(evals, b) : load_fr(points, b * n + j - 1);
+    const bool ok = fr_is_reduced(k) && (at_inf || g1_point_valid(pt));
     bad[t] = ok ? 0 : 1;
     G1Xyzz acc = G1Xyzz::identity();
     if (j == 0) {
-        const Fr v = load_fr(evals, b).from_mont();
-        acc = g1_mul<8>(g1_generator(), v.l, true);             // -v G1
-        if (!at_inf) g1_madd(acc, pt, false);
-    } else {
-        if (!at_inf) {
-            const Fr z = load_fr(points, b * n + j - 1).from_mont();
-            acc = g1_mul<8>(pt, z.l, false);
+        if (ok) {
+            acc = g1_mul<8>(g1_generator(), k.from_mont().l, true);     // -v G1
+            if (!at_inf) g1_madd(acc, pt, false);
         }
-        store_fq(pair_xy + 12 * t, pt.x);
-        store_fq(pair_xy + 12 * t + 6, pt.y.neg());
-        pair_inf[t] = at_inf ? 1 : 0;
+    } else {
+        if (ok && !at_inf) acc = g1_mul<8>(pt, k.from_mont().l, false);
+        store_fq(pair_xy + 12 * t, ok ? pt.x : Fq::zero());
+        store_fq(pair_xy + 12 * t + 6, ok ? pt.y.neg() : Fq::zero());
+        pair_inf[t] = at_inf || !ok ? 1 : 0;
     }
     store_xyzz(terms, t, acc);
 }
@@ -244,6 +244,7 @@ int verify_batch(zkhip_ctx* c, size_t batch, size_t n, const uint64_t* h_commits
                  const uint64_t* h_evals, const uint64_t* h_points, const uint64_t* h_proofs_xy, const uint8_t* h_proofs_inf,
                  const uint64_t* d_g2_xy, const uint8_t* d_g2_inf, const void* d_prepared, uint8_t* h_ok) {
     if (!batch) return ZKHIP_OK;
+    std::memset(h_ok, 0, batch);              // an error before the verdicts are known leaves none standing
     ZK_TRY(c->activate());
     const size_t m = n + 1, np = batch * m;
     size_t off = 0;
@@ -281,8 +282,15 @@ int verify_batch(zkhip_ctx* c, size_t batch, size_t n, const uint64_t* h_commits
     uint8_t* d_ok = (uint8_t*)(ws + o_ok);
     ZK_TRY(pairing_groups(c, pair_xy, pair_inf, nullptr, nullptr, prep, m, batch, m, (uint64_t*)(ws + o_f), nullptr, d_ok));
     ZK_HIP(c, hipMemcpyAsync(h_ok, d_ok, batch, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint8_t> h_bad(np);
+    ZK_HIP(c, hipMemcpyAsync(h_bad.data(), bad, np, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
     bool any = false;
-    ZK_TRY(any_flag(c, bad, np, &any));
+    for (size_t t = 0; t < np; ++t) {
+        if (!h_bad[t]) continue;
+        any = true;
+        h_ok[t / m] = 0;                      // an opening with a refused input never verifies; the others keep their verdicts
+    }
     return any ? ZKHIP_ERR_ARG : ZKHIP_OK;
 }
 

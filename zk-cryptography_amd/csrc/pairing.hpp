@@ -282,7 +282,21 @@ __device__ __forceinline__ bool g2_to_affine(const G2Jac& p, G2Affine& out) {
     return true;
 }
 
-// ---- G1 checks for verifier inputs ----------------------------------------------------------------------------------
+// ---- checks for verifier inputs -------------------------------------------------------------------------------------
+// limbs as the caller wrote them: below the modulus, or not a field element.  The arithmetic above is stated for reduced operands
+// only, so this comes before any product of an input.
+template <class P>
+__device__ __forceinline__ bool fp_is_reduced(const Fp<P>& a) {
+    bool lt = false, decided = false;
+#pragma unroll
+    for (int i = Fp<P>::N - 1; i >= 0; --i) {
+        const uint32_t p = P::p(i);
+        if (!decided && a.l[i] != p) { lt = a.l[i] < p; decided = true; }
+    }
+    return lt;
+}
+__device__ __forceinline__ bool fq_is_reduced(const Fq& a) { return fp_is_reduced(a); }
+__device__ __forceinline__ bool fr_is_reduced(const Fr& a) { return fp_is_reduced(a); }
 __device__ __forceinline__ bool g1_on_curve(const G1Affine& a) {
     return fq_sqr(a.y) == fq_mul(fq_sqr(a.x), a.x) + fq_from(PAIR_FOUR);
 }
@@ -304,6 +318,15 @@ __device__ __forceinline__ bool g1_in_subgroup(const G1Affine& p) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) r[i] = PAIR_R[i];
     return g1_mul<8>(p, r, false).is_identity();
+}
+// finite points only: coordinates reduced, on y^2 = x^3 + 4, of order r
+__device__ __forceinline__ bool g1_point_valid(const G1Affine& p) {
+    return fq_is_reduced(p.x) && fq_is_reduced(p.y) && g1_on_curve(p) && g1_in_subgroup(p);
+}
+// finite points only: the four coordinates reduced, on the twist, of order r
+__device__ __forceinline__ bool g2_point_valid(const G2Affine& q) {
+    return fq_is_reduced(q.x.c0) && fq_is_reduced(q.x.c1) && fq_is_reduced(q.y.c0) && fq_is_reduced(q.y.c1) && g2_on_curve(q) &&
+           g2_in_subgroup(q);
 }
 
 // ---- Miller loop ----------------------------------------------------------------------------------------------------

@@ -35,21 +35,6 @@ constexpr int PV_PI_T = 128;              // lanes per workgroup of the PI pass
 constexpr int PV_PI_E = 8;                // consecutive rows per lane: one inversion (~380 products) for the eight denominators
 constexpr int PV_PI_ROWS = PV_PI_T * PV_PI_E;
 
-// a coordinate as the caller wrote it: below p, or not a field element
-__device__ __forceinline__ bool fq_is_reduced(const Fq& a) {
-    bool lt = false, decided = false;
-#pragma unroll
-    for (int i = 11; i >= 0; --i) {
-        const uint32_t p = FqParams::p(i);
-        if (!decided && a.l[i] != p) { lt = a.l[i] < p; decided = true; }
-    }
-    return lt;
-}
-// finite points only: coordinates reduced, on y^2 = x^3 + 4, of order r
-__device__ __forceinline__ bool g1_point_valid(const G1Affine& p) {
-    return fq_is_reduced(p.x) && fq_is_reduced(p.y) && g1_on_curve(p) && g1_in_subgroup(p);
-}
-
 // bad[i] = 1: point i is finite and not a valid G1 element
 static __global__ __launch_bounds__(PV_BLOCK) void plonk_points_check_kernel(const uint64_t* __restrict__ xy, const uint8_t* __restrict__ inf, size_t n,
                                                                             uint8_t* __restrict__ bad) {

@@ -94,7 +94,8 @@ def g2_prepare(g2_points):
 
 def _check_points(st, what):
     if st == N.ERR_ARG:
-        raise ValueError("%s: a point is off its curve or outside the prime-order subgroup" % what)
+        raise ValueError("%s: a point is off its curve, outside the prime-order subgroup or has an unreduced coordinate, or a scalar is "
+                         "not a reduced field element" % what)
     N.check(st, what)
 
 
