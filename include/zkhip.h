@@ -22,6 +22,40 @@
  *   - While a split-phase session (zkhip_sc_begin / zkhip_mc_begin .. finish / abort) is alive its tables live in the
  *     context's workspace: every other entry point that needs that workspace returns ZKHIP_ERR_BUSY until the session
  *     ends (a second zkhip_sc_begin gets an allocation of its own instead).
+ *   - CALLS BESIDE WORK IN FLIGHT.  A holder is work the caller has begun on a context and not yet collected: proofs in flight
+ *     (zkhip_sumcheck_prove_begin), commits in flight (zkhip_kzg_commit_begin), a split-phase session (zkhip_sc_begin, zkhip_mc_begin*).
+ *     While a holder is live every other entry point of the context does one of two things.  It REFUSES: ZKHIP_ERR_BUSY, checked
+ *     before anything else the call would do to the device or the context -- nothing is launched or copied, no buffer of the context
+ *     is reserved, freed or moved, nothing the holder will read is written, and no output is written.  Or it SERVES: it delivers,
+ *     bit for bit, what it delivers on an idle context.  Either way the holder's results are what they would have been, the refused
+ *     call succeeds once the holder has ended, and the context keeps no trace of the refusal.  (Argument and shape errors that depend
+ *     on the arguments alone are reported first, as on an idle context.)
+ *     Proofs in flight hold the result slots of the basic prover and nothing else: zkhip_sumcheck_prove and
+ *     zkhip_sumcheck_prove_batch refuse, every other entry point serves (a proof in flight runs on streams, workspace and scratch of
+ *     its own).  Commits in flight and sessions hold the WORKSPACE: every entry point that takes any of it refuses, at every size --
+ *     also where a small input would not have needed scratch -- and the others serve.  (Two inputs leave a user nothing to do that
+ *     needs the workspace, and are served: zkhip_univariate_kzg_open of at most one coefficient, whose quotient is empty, and
+ *     zkhip_circuit_add_mult_mle without gates, which clears its two tables.)
+ *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
+ *     zkhip_circuit_add_mult_mle, zkhip_gkr_prove, zkhip_gkr_prove_circuit, zkhip_gkr_prove_sharded, zkhip_sumcheck_prove,
+ *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_mc_begin,
+ *     zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
+ *     zkhip_srs_univariate_g1, zkhip_srs_multilinear_g2, zkhip_srs_univariate_g2, zkhip_srs_fold_levels, zkhip_srs_level_tables,
+ *     zkhip_kzg_open, zkhip_kzg_open_tables, zkhip_kzg_open_batch, zkhip_univariate_kzg_open, zkhip_g2_prepare, zkhip_kzg_prepare,
+ *     zkhip_pairing, zkhip_pairing_prepared, zkhip_kzg_verify_batch, zkhip_univariate_kzg_verify_batch, zkhip_ntt, zkhip_domain_transform,
+ *     zkhip_univariate_multiply, zkhip_domain_transform_batch, zkhip_univariate_multiply_batch, zkhip_plonk_key_create, zkhip_plonk_prove,
+ *     zkhip_plonk_prove_batch, zkhip_plonk_verify, zkhip_plonk_verify_batch.
+ *     (zkhip_kzg_commit_begin: the first commit of a group takes the loan itself; a second and third join it.  A sharded prover that is
+ *     refused on one rank still enters the exchanges its peers make, see zkhip_comm_create.)
+ *     NO WORKSPACE: zkhip_ctx_synchronize, zkhip_mle_partial_evaluation, zkhip_mle_half_sums, zkhip_mle_add_distinct,
+ *     zkhip_mle_mul_distinct, zkhip_mle_elementwise, zkhip_mle_add_to_front, zkhip_mle_add_to_back, zkhip_mle_to_bytes,
+ *     zkhip_mle_block_sums, zkhip_mle_block_sums_deferred, zkhip_mle_block_sums_total, zkhip_composed_sum, zkhip_multi_composed_sum,
+ *     zkhip_composed_element_wise, zkhip_circuit_create, zkhip_gkr_prove_batch, zkhip_gkr_layer_tables, zkhip_srs_fingerprint,
+ *     zkhip_table_release, zkhip_dense_evaluate, zkhip_dense_degree, zkhip_sc_begin, zkhip_plonk_vkey_create,
+ *     zkhip_plonk_key_destroy.
+ *     (zkhip_gkr_prove_batch proves on lanes with a workspace each.  zkhip_sc_begin takes an allocation of its own while the workspace
+ *     is lent.  zkhip_mle_block_sums* need none at the granularity zkhip_sumcheck_plan_log_blocks asks for; with more than 2^15 chunks of
+ *     4096 entries, or fine blocks of more than 256 entries, they take a buffer from it and are then refused like the users above.)
  */
 #ifndef ZKHIP_H
 #define ZKHIP_H
@@ -159,7 +193,10 @@ int zkhip_circuit_add_mult_mle(zkhip_ctx *ctx, const uint8_t *h_gate_type, const
  *   h_sums[k*4]; h_n_rounds[k]; h_round_poly_lens[k*R + r]; h_round_polys[(k*R + r)*7*8] (coeff[4], pow[4] pairs as
  *   zkhip_multi_composed_prove); h_wb[k*4], h_wc[k*4] (GKRProof::wb_s / wc_s); h_w0[8] = w_0_mle = [output, 0];
  *   h_challenges (nullable) [(k*R + r)*4]: the sumcheck challenges of every layer (b = first half, c = second half;
- *   SuccintGKRProtocol::prove opens the input layer at the last layer's b and c, succint_protocol.rs:133-152). */
+ *   SuccintGKRProtocol::prove opens the input layer at the last layer's b and c, succint_protocol.rs:133-152).
+ * Every layer length is held against the circuit's before anything is staged (ZKHIP_ERR_SHAPE, no output written -- also on a lane of
+ * zkhip_gkr_prove_batch that replays its recorded graph); the layers' sumchecks are sessions in the context's workspace: while it is lent
+ * the call is refused with ZKHIP_ERR_BUSY before it reserves, stages or writes anything (h_w0 included). */
 int zkhip_gkr_prove(zkhip_ctx *ctx, uint32_t n_layers, const size_t *h_n_gates, const uint8_t *h_gate_type,
                     const uint32_t *h_in0, const uint32_t *h_in1, const uint64_t *const *h_layer_ptrs,
                     const size_t *h_layer_len, uint64_t *h_sums, uint32_t *h_n_rounds, uint32_t *h_round_poly_lens,
@@ -602,7 +639,9 @@ int zkhip_srs_univariate_g1(zkhip_ctx *ctx, const uint64_t *h_tau, size_t max_de
  *                           sum per digit bit, two launches for all rounds); zkhip_srs_level_tables builds such an SRS's tables in a few ms.
  * Outputs (host): h_evaluation[4]; h_proofs_xy[n_vars*12], h_proofs_inf[n_vars] (affine, as zkhip_kzg_commit).
  * Shape errors as in the reference: n_points != n (multilinear_kzg.rs:36-41), n_eval_points != n_vars
- * (evaluation_form.rs:163-167), n_vars < 2 (`variable_index - 1` underflows at :73) -> ZKHIP_ERR_SHAPE. */
+ * (evaluation_form.rs:163-167), n_vars < 2 (`variable_index - 1` underflows at :73) -> ZKHIP_ERR_SHAPE.  Every round's commit needs the
+ * workspace: while it is lent zkhip_kzg_open / _open_tables / _open_batch return ZKHIP_ERR_BUSY after these checks and before the quotient
+ * area is reserved, anything is launched or an output is written. */
 int zkhip_srs_fold_levels(zkhip_ctx *ctx, const uint64_t *d_points_xy, const uint8_t *d_points_inf, size_t n_points,
                           uint64_t *d_out_xy, uint8_t *d_out_inf);
 int zkhip_kzg_open(zkhip_ctx *ctx, const uint64_t *d_evals, size_t n, const uint64_t *h_points, size_t n_eval_points,
@@ -632,7 +671,9 @@ int zkhip_kzg_open_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *
  * proof = commitment to the quotient of (poly - z) / (x - z) (divide_with_q_and_r, dense_univariate.rs:88-124) against
  * the first n_coeffs - 1 SRS points.  Evaluation and quotient come from one Horner suffix scan on the device.
  * n_coeffs - 1 > n_points is the index panic at :75 -> ZKHIP_ERR_INDEX (checked on the coefficient count as given;
- * the reference would first drop zero leading coefficients).  Outputs (host): h_evaluation[4], h_proof_xy[12], *h_proof_inf. */
+ * the reference would first drop zero leading coefficients).  Outputs (host): h_evaluation[4], h_proof_xy[12], *h_proof_inf.
+ * The quotient's commit needs the workspace: while it is lent the call returns ZKHIP_ERR_BUSY (n_coeffs > 1) before the scan is launched;
+ * a refused call -- that one, and every argument or shape error -- writes no output. */
 int zkhip_univariate_kzg_open(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *h_z,
                               const uint64_t *d_points_xy, const uint8_t *d_points_inf, size_t n_points,
                               uint64_t *h_evaluation, uint64_t *h_proof_xy, uint8_t *h_proof_inf);
@@ -679,8 +720,8 @@ int zkhip_pairing_prepared(zkhip_ctx *ctx, const uint64_t *d_g1_xy, const uint8_
  * n_g2 != n_vars -> ZKHIP_ERR_SHAPE (utils.rs:49-50); a finite commitment or proof off the curve, outside the subgroup or with an unreduced
  * coordinate; an evaluation or point that is not a reduced field element -> ZKHIP_ERR_ARG.  With that status h_ok[b] = 0 for every opening
  * that holds such an input and h_ok of every other opening is its verdict, as a call without the refused openings returns it.  A refused
- * SRS point (d_prepared NULL) or a HIP error leaves h_ok all zero; a null argument or ZKHIP_ERR_SHAPE leaves it untouched.  The coordinates
- * of a point flagged at infinity are ignored. */
+ * SRS point (d_prepared NULL) or a HIP error leaves h_ok all zero; a null argument, ZKHIP_ERR_SHAPE or ZKHIP_ERR_BUSY (the workspace lent)
+ * leaves it untouched.  The coordinates of a point flagged at infinity are ignored. */
 int zkhip_kzg_verify_batch(zkhip_ctx *ctx, size_t batch, uint32_t n_vars, const uint64_t *h_commits_xy,
                            const uint8_t *h_commits_inf, const uint64_t *h_evals, const uint64_t *h_points,
                            const uint64_t *h_proofs_xy, const uint8_t *h_proofs_inf, const uint64_t *d_g2_xy,
@@ -763,7 +804,9 @@ int zkhip_univariate_multiply_batch(zkhip_ctx *ctx, uint32_t batch, const uint64
  *   The four `/ zh_poly` quotients of third_round (:191-226) are taken as ONE exact division on the coset g <w_D>.  A witness that does
  *   not satisfy the circuit -- a row that breaks the gate identity, a vanishing denominator of the grand product, an accumulator that
  *   does not close, a numerator Z_H does not divide -- yields no proof: ZKHIP_ERR_ARG (the reference returns a proof that does not
- *   verify).  Commits run three in flight (zkhip_kzg_commit_begin): the context's workspace must be free.  h_challenges may be NULL.
+ *   verify).  Commits run three in flight (zkhip_kzg_commit_begin): the context's workspace must be free -- ZKHIP_ERR_BUSY otherwise,
+ *   before the work area or an output is touched (zkhip_plonk_key_create and zkhip_plonk_verify likewise: nothing allocated, *h_ok
+ *   untouched).  h_challenges may be NULL.
  * zkhip_plonk_challenges: compute_verifier_challenges (protocol/utils.rs:56-96).  HOST ONLY, no GPU and no context.  The transcript is
  *   the reference's byte for byte: SHA-256 over "Merlin Transcript" || "plonk_protocol"; append_message = label || len as 8 bytes LE ||
  *   message; a scalar is its 32-byte LE canonical form, a point the UTF-8 of "(x, y)" in decimal ("infinity" for the identity);

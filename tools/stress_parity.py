@@ -258,7 +258,64 @@ def case_in_flight():
     return ok, ("in_flight", depth, logs)
 
 
-cases = [case_multi_k2, case_multifold, case_in_flight, case_open, case_uni_open, case_table_ops, case_sumcheck, case_fold_eval, case_composed, case_multi, case_commit, case_ntt, case_gkr, case_gkr_batch]
+_hsrs = {}
+def case_beside_in_flight():
+    """1-8 Sumcheck proofs or 1-3 commits in flight on the context, ONE other case beside them -- it serves (its own comparison with the
+    oracle holds) or is refused with ZKHIP_ERR_BUSY (include/zkhip.h, "Calls beside work in flight") -- then the holder's results
+    against the oracle, and the refused case once more on the idle context"""
+    from zk_cryptography_amd._native import ERR_BUSY, ZkhipError
+    other = rng.choice([c for c in all_cases if c not in (case_beside_in_flight, case_in_flight)])      # (whatever the command line selected)
+    if rng.random() < 0.5:
+        logs = [rng.choice([3, 9, 12, 16, 18]) for _ in range(rng.randint(1, 8))]
+        tabs = [ora.random_fr(1 << l, rng.randrange(1 << 30)) for l in logs]
+        pend = []
+        for t in tabs:
+            sc = zk.Sumcheck(zk.Multilinear(t)); sc.poly_sum()
+            pend.append(sc.prove_begin())
+        held = ("proofs", logs)
+        def collect():
+            ok = True
+            for t, h in zip(tabs, pend):
+                (proof, ch), (ws, wrp, wch) = h.wait(), ora.sumcheck_prove(t)
+                ok = ok and np.array_equal(proof.sum, ws) and np.array_equal(proof.univariate_poly, wrp) and np.array_equal(ch, wch)
+            return ok
+    else:
+        nv, table = rng.randint(3, 10), rng.random() < 0.5
+        if (nv, table) not in _hsrs:
+            tau = ora.random_fr(nv, 2000 + nv)
+            srs = zk.TrustedSetup.setup(tau)
+            _hsrs[(nv, table)] = (srs.precompute() if table else srs, ora.kzg_multilinear_srs_g1(tau))
+        srs, osrs = _hsrs[(nv, table)]
+        vals = [ora.random_fr(1 << nv, rng.randrange(1 << 30)) for _ in range(rng.randint(1, 3))]
+        pend = [zk.MultilinearKZG.commitment_begin(zk.Multilinear(v), srs) for v in vals]
+        held = ("commits", nv, table, len(vals))
+        def collect():
+            ok = True
+            for v, h in zip(vals, pend):
+                com, want = h.wait(), ora.g1_to_affine(ora.kzg_commitment(v, osrs, True))
+                ok = ok and (bool(want[12]) == com.infinity) and (com.infinity or np.array_equal(com.xy, want[:12]))
+            return ok
+    state = rng.getstate()
+    try:
+        try:
+            res = other()
+        except ZkhipError as e:
+            if e.status != ERR_BUSY: raise
+            res = "busy"
+    finally:
+        held_ok = collect()
+    if res == "busy":                       # the same case, with the same draws, now that the holder has ended
+        rng.setstate(state)
+        res = other()
+    if res == "skip":
+        return held_ok, ("beside_in_flight", held, other.__name__, "skip")
+    ok, what = res
+    return ok and held_ok, ("beside_in_flight", held, "holder ok" if held_ok else "HOLDER WRONG", what)
+
+
+cases = [case_multi_k2, case_multifold, case_in_flight, case_open, case_uni_open, case_table_ops, case_sumcheck, case_fold_eval, case_composed, case_multi, case_commit, case_ntt, case_gkr, case_gkr_batch,
+         case_beside_in_flight]
+all_cases = list(cases)
 if len(sys.argv) > 3:
     cases = [c for c in cases if c.__name__ in sys.argv[3:]]
 t0 = time.time()

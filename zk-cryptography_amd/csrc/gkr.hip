@@ -684,6 +684,15 @@ static int gkr_prove_circuit_on(zkhip_ctx* c, zkhip_circuit* cir, const uint64_t
     if (h_layer_len[0] != 1) return ZKHIP_ERR_SHAPE;              // w_0 = [output.., 0] must have 2^k entries; the wiring of layer 0 has one gate bit
     for (uint32_t k = 1; k <= n_layers; ++k)
         if (!is_pow2(h_layer_len[k])) return ZKHIP_ERR_SHAPE;  // Multilinear::new (evaluation_form.rs:16-20)
+    // The layer lengths against the circuit's, BEFORE anything is staged: a lane that replays its graph never reaches the per-layer check of
+    // the plain chain (layer_enqueue_device / layer_prove), and a shorter table would be staged short and proved as if it were whole.  Layer
+    // after layer, up to the first one with a label out of range: that one is reported where the prover reaches it, as before.
+    for (uint32_t k = 1; k <= n_layers && !cir->layers[k - 1].bad_label; ++k)
+        if (h_layer_len[k] != cir->layers[k - 1].w_len) return ZKHIP_ERR_SHAPE;
+    // Every layer's sumcheck is a composed session in the context's workspace: while that is lent (a commit in flight, a split-phase
+    // session) the proof is refused HERE -- before the scratch, the first layer's values and the pinned proof block are touched.  The
+    // proof block is msm_pin[0], where the commit in flight in slot 0 keeps its terms until zkhip_kzg_commit_end reads them.
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
     ZK_TRY(c->activate());
     // The lanes of a batch run on threads of their own, and since proofs are handed out one by one they are no longer in step: a lane's first
     // proof of a circuit allocates (workspace, pinned slots, the lane's copy of the layer values), its second RECORDS the chain -- and a
@@ -1068,7 +1077,39 @@ extern "C" int zkhip_gkr_prove_sharded(zkhip_circuit* cir, zkhip_comm* comm, con
     if (h_layer_len[0] != 1) return ZKHIP_ERR_SHAPE;
     for (uint32_t k = 1; k <= n_layers; ++k)
         if (!is_pow2(h_layer_len[k])) return ZKHIP_ERR_SHAPE;     // Multilinear::new (evaluation_form.rs:16-20)
+    for (uint32_t k = 1; k <= n_layers && !cir->layers[k - 1].bad_label; ++k)      // as zkhip_gkr_prove_circuit: before anything is staged
+        if (h_layer_len[k] != cir->layers[k - 1].w_len) return ZKHIP_ERR_SHAPE;   // (values every rank holds: all ranks return at once)
     ZK_TRY(c->activate());
+    // The sessions of every layer live in the context's workspace.  While it is lent (a commit in flight, a split-phase session) this rank
+    // is refused before it reserves the scratch, stages w_0 or writes an output -- but it is a failing rank of a collective call: it still
+    // enters the exchanges its peers make (walk_failed below), as it did when the first session's begin found the workspace lent.
+    uint32_t n_ex = 0;
+    // A rank that fails must not hang its peers (shard_protocol.hpp): it enters every exchange the healthy ranks still make, with poison
+    // records, up to the end of the first layer that has any; the healthy ranks read the sticky flag where they wait for the GPU anyway
+    // (the end of each layer) and return ZKHIP_ERR_PEER there.  sessions_left: how many of layer li_from's two sessions are still to come.
+    auto walk_failed = [&](uint32_t li_from, int sessions_left, int fail_rc) {
+        for (uint32_t li = li_from; li <= n_layers; ++li, sessions_left = 2) {
+            const size_t w_len = h_layer_len[li];
+            if (w_len < 2 * (size_t)world || world == 1) continue;              // a narrow layer runs whole on every rank: no exchange
+            const uint32_t sizes[2] = {2, 2};
+            const bool stages = use_stages >= 0 ? use_stages != 0 : true;
+            for (int sess = 2 - sessions_left; sess < 2; ++sess) {
+                zkshard::HipMcEngine e{nullptr, comm};
+                if (e.shape(sizes, 2, sess == 0 ? 1u : 0u, w_len / world) != ZKHIP_OK) return;
+                uint32_t ex = 0;
+                (void)zkshard::composed_prove(e, *comm, stages, &ex, fail_rc);
+                n_ex += ex;
+            }
+            break;                                                                // the peers look at the flag behind this layer
+        }
+        (void)c->wait_stream();
+        (void)comm->take_peer_failure();
+    };
+    if (c->ws_loans.lent()) {
+        walk_failed(1, 2, ZKHIP_ERR_BUSY);        // refused in front of the first layer's first session
+        if (exchanges) *exchanges = n_ex;
+        return ZKHIP_ERR_BUSY;
+    }
     // aux layout: w_0 (2 entries) | the table builders' scratch | 8 tables of this rank's rows of the widest layer
     size_t max_rows = 1, max_scratch = 0;
     for (uint32_t l = 0; l < n_layers; ++l) {
@@ -1084,7 +1125,6 @@ extern "C" int zkhip_gkr_prove_sharded(zkhip_circuit* cir, zkhip_comm* comm, con
     for (int q = 0; q < 8; ++q) tab[q] = (uint64_t*)(aux + o_tab + (size_t)q * tb);
     zkhip_comm* solo = comm->solo_comm();                         // narrow layers run whole on every rank: a one-rank exchange (no transport)
     if (!solo) return ZKHIP_ERR_NOMEM;
-    uint32_t n_ex = 0;
     const uint32_t stride = 2 * n_layers;
 
     // w_0 = circuit_evaluation[0] padded with a zero (protocol.rs:30-33); commit its bytes, draw n_r
@@ -1116,27 +1156,6 @@ extern "C" int zkhip_gkr_prove_sharded(zkhip_circuit* cir, zkhip_comm* comm, con
     }
     zkhost::Fr alpha = zkhost::fr_one(), beta = zkhost::fr_zero();
 
-    // A rank that fails must not hang its peers (shard_protocol.hpp): it enters every exchange the healthy ranks still make, with poison
-    // records, up to the end of the first layer that has any; the healthy ranks read the sticky flag where they wait for the GPU anyway
-    // (the end of each layer) and return ZKHIP_ERR_PEER there.  sessions_left: how many of layer li_from's two sessions are still to come.
-    auto walk_failed = [&](uint32_t li_from, int sessions_left, int fail_rc) {
-        for (uint32_t li = li_from; li <= n_layers; ++li, sessions_left = 2) {
-            const size_t w_len = h_layer_len[li];
-            if (w_len < 2 * (size_t)world || world == 1) continue;              // a narrow layer runs whole on every rank: no exchange
-            const uint32_t sizes[2] = {2, 2};
-            const bool stages = use_stages >= 0 ? use_stages != 0 : true;
-            for (int sess = 2 - sessions_left; sess < 2; ++sess) {
-                zkshard::HipMcEngine e{nullptr, comm};
-                if (e.shape(sizes, 2, sess == 0 ? 1u : 0u, w_len / world) != ZKHIP_OK) return;
-                uint32_t ex = 0;
-                (void)zkshard::composed_prove(e, *comm, stages, &ex, fail_rc);
-                n_ex += ex;
-            }
-            break;                                                                // the peers look at the flag behind this layer
-        }
-        (void)c->wait_stream();
-        (void)comm->take_peer_failure();
-    };
     int rc = ZKHIP_OK;
     uint32_t fail_layer = 0;     // where this rank failed: the layer, and how many of its sessions the peers still run
     int fail_sessions_left = 0;
@@ -1230,6 +1249,7 @@ extern "C" int zkhip_gkr_prove(zkhip_ctx* c, uint32_t n_layers, const size_t* h_
     if (h_layer_len[0] != 1) return ZKHIP_ERR_SHAPE;
     for (uint32_t k = 1; k <= n_layers; ++k)
         if (!is_pow2(h_layer_len[k]) || h_layer_len[k] != ((size_t)2 << (k - 1))) return ZKHIP_ERR_SHAPE;   // shapes before labels, as the reference panics
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // before the circuit is uploaded for a proof that would be refused
     zkhip_circuit* cir = nullptr;
     ZK_TRY(zkhip_circuit_create(c, n_layers, h_n_gates, h_gate_type, h_in0, h_in1, &cir));
     const int rc = zkhip_gkr_prove_circuit(cir, h_layer_ptrs, h_layer_len, h_sums, h_n_rounds, h_round_poly_lens, h_round_polys, h_wb, h_wc,

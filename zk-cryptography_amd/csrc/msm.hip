@@ -507,6 +507,7 @@ extern "C" int zkhip_srs_precompute(zkhip_ctx* c, const uint64_t* d_points_xy, c
     if (n == 0) return ZKHIP_OK;
     const MsmLevelWidths lw = msm_table_widths(n);
     if (n * lw.W >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;   // entry index + sign bit in 32 bits
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // before the address is forgotten as a table: a refused rebuild leaves the old one in use
     ZK_TRY(c->activate());
     table_forget(c, d_table);
     ZK_TRY(build_shift_table(c, d_points_xy, d_points_inf, n, lw.hi, lw.W, (uint32_t*)((char*)d_table + ZK_TABLE_HEADER_BYTES), lw.n_hi));
@@ -535,6 +536,7 @@ extern "C" int zkhip_srs_level_tables(zkhip_ctx* c, const uint64_t* d_folded_xy,
     if (!c || !d_folded_xy || !d_folded_inf || !d_tables_with_header) return ZKHIP_ERR_ARG;
     if (n_points < 2 || !is_pow2(n_points)) return ZKHIP_ERR_SHAPE;
     if (zkhip_srs_level_tables_bytes(n_points) / 128 >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // (as zkhip_srs_precompute)
     ZK_TRY(c->activate());
     table_forget(c, d_tables_with_header);
     void* d_tables = (char*)d_tables_with_header + ZK_TABLE_HEADER_BYTES;
@@ -762,6 +764,9 @@ static int kzg_open_check(zkhip_ctx* c, size_t n, size_t n_eval_points, size_t n
     if (n_vars < 2) return ZKHIP_ERR_SHAPE;                // :73 `variable_index - 1` underflows
     if (n >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;
     if ((d_folded_xy == nullptr) != (d_folded_inf == nullptr)) return ZKHIP_ERR_ARG;
+    // every round's commit needs the workspace: an opening beside a commit in flight or a split-phase session is refused here, before the
+    // quotient area is reserved (which may move it), the quotient chain is launched and the SRS is folded
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
     ZK_TRY(c->activate());
     *d_level_tables = nullptr;
     if (d_level_tables_with_header) {
@@ -1183,8 +1188,8 @@ extern "C" int zkhip_univariate_kzg_open(zkhip_ctx* c, const uint64_t* d_coeffs,
                                          const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points,
                                          uint64_t* h_evaluation, uint64_t* h_proof_xy, uint8_t* h_proof_inf) {
     if (!c || !h_z || !h_evaluation || !h_proof_xy || !h_proof_inf || (n && !d_coeffs)) return ZKHIP_ERR_ARG;
-    std::memset(h_proof_xy, 0, 96);
     if (n == 0) {                                   // the zero polynomial: evaluate() = 0; numerator [z] has degree 0 < 1 -> quotient zero
+        std::memset(h_proof_xy, 0, 96);
         std::memset(h_evaluation, 0, 32);
         *h_proof_inf = 1;
         return ZKHIP_OK;
@@ -1192,6 +1197,10 @@ extern "C" int zkhip_univariate_kzg_open(zkhip_ctx* c, const uint64_t* d_coeffs,
     if (n - 1 > n_points) return ZKHIP_ERR_INDEX;  // srs.powers_of_tau_in_g1[i] out of bounds (univariate_kzg.rs:75)
     if (n >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;
     if (n > 1 && !d_points_xy) return ZKHIP_ERR_ARG;
+    // the quotient's commit needs the workspace: refused before the scan is launched and before an output is written (the evaluation
+    // used to be delivered, and the proof cleared, in front of the commit's ZKHIP_ERR_BUSY)
+    if (n > 1 && c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
+    std::memset(h_proof_xy, 0, 96);
     ZK_TRY(c->activate());
     const size_t per_block = (size_t)HS_T * HS_L;
     const uint32_t n_blocks = (uint32_t)((n + per_block - 1) / per_block);

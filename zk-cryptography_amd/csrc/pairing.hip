@@ -244,6 +244,7 @@ int verify_batch(zkhip_ctx* c, size_t batch, size_t n, const uint64_t* h_commits
                  const uint64_t* h_evals, const uint64_t* h_points, const uint64_t* h_proofs_xy, const uint8_t* h_proofs_inf,
                  const uint64_t* d_g2_xy, const uint8_t* d_g2_inf, const void* d_prepared, uint8_t* h_ok) {
     if (!batch) return ZKHIP_OK;
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // refused like a null argument: nothing launched, h_ok untouched
     std::memset(h_ok, 0, batch);              // an error before the verdicts are known leaves none standing
     ZK_TRY(c->activate());
     const size_t m = n + 1, np = batch * m;

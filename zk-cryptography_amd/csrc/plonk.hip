@@ -345,6 +345,7 @@ extern "C" int zkhip_plonk_key_create(zkhip_ctx* c, size_t n, const uint64_t* co
     while (D < 3 * n + 6) D <<= 1;
     if (log2_exact(D) > 30) return ZKHIP_ERR_SHAPE;
     if (n_points < n + 6) return ZKHIP_ERR_INDEX;                  // powers_of_tau_in_g1[i] out of bounds (univariate_kzg.rs:53) at t_high
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;                 // the columns' transforms and the eight commits need the workspace: nothing allocated or copied
     ZK_TRY(c->activate());
     std::unique_ptr<zkhip_plonk_key> k(new (std::nothrow) zkhip_plonk_key());
     if (!k) return ZKHIP_ERR_NOMEM;
@@ -409,6 +410,8 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
         bl[i] = h_load(h_blinding + 4 * i);
         if (zkhost::fr_geq_p(bl[i].l)) return ZKHIP_ERR_ARG;
     }
+    // the transforms and the commits need the context's workspace: refused before the work area is cleared and the outputs are zeroed
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
     std::memset(h_points_xy, 0, 96 * N_POINTS);
     std::memset(h_points_inf, 0, N_POINTS);
     uint64_t* xy[N_POINTS]; uint8_t* inf[N_POINTS];
@@ -932,12 +935,14 @@ extern "C" int zkhip_plonk_verify(zkhip_ctx* c, size_t n, const uint64_t* h_vk_x
                                   const uint8_t* h_points_inf, const uint64_t* h_evals, const uint64_t* d_public, const uint64_t* d_g2_xy,
                                   const uint8_t* d_g2_inf, size_t n_g2, uint8_t* h_ok) {
     if (!c || !h_vk_xy || !h_vk_inf || !h_points_xy || !h_points_inf || !h_evals || !d_public || !d_g2_xy || !d_g2_inf || !h_ok) return ZKHIP_ERR_ARG;
+    const uint8_t was = *h_ok;
     *h_ok = 0;
     if (!is_pow2(n) || n < 4 || log2_exact(n) > 28) return ZKHIP_ERR_SHAPE;
     if (n_g2 < 2) return ZKHIP_ERR_INDEX;                          // powers_of_tau_in_g2[1] (verifier.rs:34)
     for (int e = 0; e < N_EVALS; ++e) if (zkhost::fr_geq_p(h_evals + 4 * e)) return ZKHIP_ERR_ARG;
     for (int p = 0; p < N_POINTS; ++p) if (!h_points_inf[p] && !g1_valid(h_points_xy + 12 * p)) return ZKHIP_ERR_ARG;
     for (int p = 0; p < 8; ++p) if (!h_vk_inf[p] && !g1_valid(h_vk_xy + 12 * p)) return ZKHIP_ERR_ARG;
+    if (c->ws_loans.lent()) { *h_ok = was; return ZKHIP_ERR_BUSY; }      // PI(zeta) and the pairing need the workspace: nothing allocated or launched, *h_ok as it was
     ZK_TRY(c->activate());
     HFr ch[N_CHALLENGES];
     absorb_challenges_from_proof(h_points_xy, h_points_inf, h_evals, ch);

@@ -501,6 +501,7 @@ extern "C" int zkhip_circuit_add_mult_mle(zkhip_ctx* c, const uint8_t* h_gate_ty
         const size_t idx = (g << (2 * shift)) | ((size_t)h_in0[g] << shift) | h_in1[g];
         if (idx >= size) return ZKHIP_ERR_INDEX;     // add_evaluations[gate_decimal] out of bounds
     }
+    if (n_gates && c->ws_loans.lent()) return ZKHIP_ERR_BUSY;    // the gate list goes through the workspace: refused before the tables are cleared
     ZK_TRY(c->activate());
     ZK_HIP(c, hipMemsetAsync(d_add, 0, 32 * size, c->stream));   // F::zero() is all-zero limbs
     ZK_HIP(c, hipMemsetAsync(d_mul, 0, 32 * size, c->stream));
