@@ -8,7 +8,8 @@ from collections import defaultdict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the sources of the streaming kernels whose traffic is reported: bench.py compares this fingerprint with the tree it runs from
 # (`roofline.traffic_age`), so that a rebuilt kernel does not silently keep an old ratio
-STREAMING_KERNEL_SOURCES = ("mle_kernels.hpp", "multifold_kernels.hpp", "mfma_fold.hpp", "fp.hpp", "fp_mul_gen.hpp", "wide_acc.hpp")
+STREAMING_KERNEL_SOURCES = ("mle_kernels.hpp", "multifold_kernels.hpp", "mfma_fold.hpp", "mfma_fold_tile_body.hpp", "fold_rounds.hpp", "fp.hpp",
+                            "fp_mul_gen.hpp", "wide_acc.hpp")
 
 
 def kernel_sources_fingerprint(root=ROOT):

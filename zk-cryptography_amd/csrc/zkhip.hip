@@ -19,6 +19,7 @@
 #include "sumcheck_batch_kernels.hpp"
 #include "multifold_kernels.hpp"
 #include "mfma_fold.hpp"
+#include "fold_rounds.hpp"
 #include "tunables.hpp"
 
 using namespace zk;
@@ -204,6 +205,7 @@ extern "C" int zkhip_mle_partial_evaluation(zkhip_ctx* c, const uint64_t* d_eval
     return launch_fold(c, d_evals, n, d_r, h_r, var_index, d_out, false, nullptr, nullptr);
 }
 
+static inline int multifold_cfg() { static const int v = (int)zk::env::read(zk::env::MF); return v; }   // (ZKHIP_MF, read once: below)
 // the k-variable fold of a cn-entry table in the shape that suits its output size; returns the per-workgroup sums' count
 static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cur, size_t cn, uint32_t k, const uint64_t* d_w,
                             uint64_t* dst, uint64_t* pdst, uint32_t* n_parts) {
@@ -213,7 +215,7 @@ static int launch_multifold(zkhip_ctx* c, hipStream_t stream, const uint64_t* cu
     // the term order (tile T starts at term r * T mod 2^k; the default 1 -- 3 and 5 measured the same, 0 = every wave at term 0: 108 vs 112 us
     // before the aligned planes); ZKHIP_MF_OCC=n caps the workgroups per CU through the LDS request (all 1024 workgroups are resident at once as it is, 4 per CU; capped at 2 per CU
     // or with 36-78 KiB requested per workgroup the pass takes the same 83-85 us, alone and beside the proofs in flight: round 6)
-    static const int mf_cfg = (int)zk::env::read(zk::env::MF);
+    const int mf_cfg = multifold_cfg();
     if (m >= 8192 && k >= 4 && mf_cfg != 0) {   // streaming shape, limb products on the matrix cores (mfma_fold.hpp)
         out_per_wg = 64;
         ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
@@ -563,6 +565,31 @@ static int launch_small(zkhip_ctx* c, const SmallArgs& a, SumcheckDev* st, uint6
     return ZKHIP_OK;
 }
 
+// The synchronous overlapped proof (lane < 0) takes its big fold and the rounds beside it as one launch (fold_rounds.hpp) wherever that
+// fold has its matrix-core form: k1 >= 4 and 2^13 outputs or more, which in this plan is from 2^22 entries on.  Below that (the vector
+// form, k1 = 3) and for every proof in flight the fork stays as it is.
+static inline bool fold_rounds_plan(size_t n, int lane) {
+    if (lane >= 0 || !overlapped_plan(n)) return false;
+    const uint32_t k2 = overlapped_k2(n), k1 = log2_exact(n) - 8 - k2;
+    return multifold_cfg() != 0 && fold_rounds_serves(n >> k1, k1, small_lds_bytes(k2, (int)k2, false));
+}
+// serial rounds `a` (sumcheck_small_kernel's arguments) as workgroup 0 and the k-variable fold of `cur` (cn entries) into dst as the
+// other workgroups of one launch.  Recorded as the fold it contains -- the bytes are the fold's -- and a second time under the form's name.
+static int launch_fold_rounds(zkhip_ctx* c, hipStream_t stream, const SmallArgs& a, SumcheckDev* st, uint64_t* d_rp, uint64_t* d_ch,
+                              const uint64_t* cur, size_t cn, uint32_t k, const uint64_t* d_w, uint64_t* dst) {
+    const size_t m = cn >> k;
+    if (a.log_n > (uint32_t)TREE_MAX_LOG || a.n_rounds > a.log_n) return ZKHIP_ERR_SHAPE;
+    if (!fold_rounds_serves(m, k, small_lds_bytes(a.log_n, a.weights_out ? (int)a.n_rounds : -1, a.group != 0 && a.stride == 0)))
+        return ZKHIP_ERR_SHAPE;
+    ZK_TRY(c->allow_big_lds((const void*)fold_rounds_kernel, 158 * 1024));   // (~0.5 KiB of static LDS on top)
+    ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
+    ProfScope form(c, "multifold_rounds", 0.0, stream);   // (a second record of the same launch: which form it was)
+    hipLaunchKernelGGL(fold_rounds_kernel, dim3(1 + fold_rounds_workgroups(m)), dim3(SMALL_BLOCK), FOLD_ROUNDS_LDS, stream, a, st, d_rp, d_ch,
+                       cur, m, k, d_w, dst, (uint32_t)multifold_cfg());
+    ZK_HIP(c, hipGetLastError());
+    return ZKHIP_OK;
+}
+
 // the arguments of a serial launch: n_rounds rounds from round0 on, on this source; every other field zero (the transcript continues)
 static SmallArgs small_rounds(const uint64_t* src, uint32_t group, uint32_t stride, uint32_t canon, uint32_t log_n, uint32_t n_rounds,
                               uint32_t round0, uint64_t* weights_out) {
@@ -780,6 +807,8 @@ static int proof_setup(zkhip_ctx* c, size_t n, bool overlap, const uint64_t* h_c
     if (lane < 0) {
         ZK_TRY(c->reserve_ws(ws_need));
         ws = (uint64_t*)c->ws.ptr; small = (uint64_t*)c->d_small.get(); p.S = c->stream;
+        // (The fused launch of fold_rounds_plan uses neither the fold stream nor the events.  The streams are created all the same: the
+        // order in which a context's streams come into being decides which hardware queues the lanes of later proofs in flight get.)
         if (overlap) { ZK_TRY(c->ensure_fold_stream()); p.F = c->fold_stream.get(); p.fork_ev = c->fork_ev.get(); p.serial_ev = c->serial_ev.get(); }
     } else {
         ZK_TRY(c->ensure_lane(lane, ws_need));
@@ -808,10 +837,10 @@ static int proof_last_stage(zkhip_ctx* c, ProofRun p, hipStream_t stream, uint32
     ZK_TRY(launch_blockfold(c, stream, p.tabA, 256, k2, p.w2, p.p2, &ny));
     return launch_small(c, p.closing_rounds(p.p2, ny, 256, 1, 8), p.st, p.d_rp, p.d_ch, 0, stream);
 }
-// The overlapped plan (above stage_k).  *tail: the stream the proof ends on, or null when its second half was held back (three or more
-// proofs in flight), which then records the proof's event itself.
+// The overlapped plan (above stage_k).  *tail: the stream the proof ends on (the caller's may be the null stream: a null pointer says
+// nothing).  *held_back: the proof's second half was kept for later (three or more proofs in flight) and records the proof's event itself.
 static int proof_overlapped(zkhip_ctx* c, ProofRun& p, const uint64_t* d_evals, size_t n, const uint64_t* d_block_sums, uint32_t log_blocks,
-                            int slot, int lane, int in_flight, hipStream_t* tail) {
+                            int slot, int lane, int in_flight, hipStream_t* tail, bool* held_back) {
     const uint32_t g = log2_exact(n) - 8, k2 = overlapped_k2(n), k1 = g - k2;
     const hipStream_t S = p.S;
     const uint64_t* fine = d_block_sums;
@@ -849,6 +878,15 @@ static int proof_overlapped(zkhip_ctx* c, ProofRun& p, const uint64_t* d_evals, 
     // the small fold, the big fold filled every CU first and the serial kernel waited for one to drain (~60 us).
     uint32_t ny = 0, n_parts = 0;
     ZK_TRY(launch_blockfold(c, S, fine, 1u << k2, k1, p.w, p.p1, &ny));
+    if (fold_rounds_plan(n, lane)) {
+        // The synchronous proof where the fold has its matrix-core form (2^22 entries and more): no fork at all.  The big fold and the
+        // serial rounds beside it are workgroups of ONE launch on the caller's stream (fold_rounds.hpp) -- workgroup 0, dispatched
+        // first, is the serial kernel -- and the last stage follows in stream order: no fold stream, no event, no join.
+        const SmallArgs fused = p.rounds(p.p1, ny, 1u << k2, 1, k2, p.w2);
+        ZK_TRY(launch_fold_rounds(c, S, fused, p.st, p.d_rp, p.d_ch, d_evals, n, k1, p.w, p.tabA));
+        *tail = S;
+        return proof_last_stage(c, p, S, k2);
+    }
     ZK_HIP(c, hipEventRecord(p.fork_ev, S));
     const SmallArgs b = p.rounds(p.p1, ny, 1u << k2, 1, k2, p.w2);
     if (lane >= 0 && in_flight < 3) { ZK_TRY(c->ensure_lane_fold(lane)); p.F = c->lanes[lane].fold; }
@@ -876,7 +914,7 @@ static int proof_overlapped(zkhip_ctx* c, ProofRun& p, const uint64_t* d_evals, 
         // (a second half that cannot be enqueued is its OWN proof's failure -- recorded in deferred_rc, reported by that proof's prove_end --
         // not this proof's: this one's second half is in the queue now and the ticket must reach the caller)
         (void)c->flush_deferred((size_t)std::min(3, std::max(1, in_flight - 3)));
-        *tail = nullptr;
+        *held_back = true;
         return ZKHIP_OK;
     }
     ZK_HIP(c, hipStreamWaitEvent(p.F, p.fork_ev, 0));
@@ -930,8 +968,9 @@ static int sumcheck_enqueue(zkhip_ctx* c, const uint64_t* d_evals, size_t n, con
     ZK_TRY(proof_setup(c, n, overlap, h_claimed_sum, d_claimed_sum, slot, lane, p));
     hipStream_t tail_stream = p.S;            // where the last kernels of the proof run (the overlapped plan ends on its fold stream)
     if (overlap) {
-        ZK_TRY(proof_overlapped(c, p, d_evals, n, d_block_sums, log_blocks, slot, lane, in_flight, &tail_stream));
-        if (!tail_stream) return ZKHIP_OK;
+        bool held_back = false;
+        ZK_TRY(proof_overlapped(c, p, d_evals, n, d_block_sums, log_blocks, slot, lane, in_flight, &tail_stream, &held_back));
+        if (held_back) return ZKHIP_OK;
     } else {
         ZK_TRY(proof_stages(c, p, d_evals, n, d_block_sums, log_blocks));
     }
