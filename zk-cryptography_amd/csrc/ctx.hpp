@@ -265,6 +265,18 @@ struct zkhip_ctx {
         if (e != hipSuccess) { last_hip = (int)e; return ZKHIP_ERR_HIP; }
         return ZKHIP_OK;
     }
+    // compute units of the device, read once: what a launch that keeps its workgroups resident sizes its grid by
+    uint32_t cu_count = 0;
+    int compute_units(uint32_t* cus) {
+        if (!cu_count) {
+            int v = 0;
+            hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
+            if (e != hipSuccess || v <= 0) { last_hip = (int)e; return ZKHIP_ERR_HIP; }
+            cu_count = (uint32_t)v;
+        }
+        *cus = cu_count;
+        return ZKHIP_OK;
+    }
     std::set<const void*> big_lds_done;
     // kernels that carve more than 64 KiB of the CU's 160 KiB LDS need the attribute raised once per function
     int allow_big_lds(const void* fn, size_t bytes) {

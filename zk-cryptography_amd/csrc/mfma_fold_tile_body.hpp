@@ -1,6 +1,6 @@
 // mfma_fold_tile_body.hpp -- NOT a header: one wave's tile of multifold_mfma_kernel (mfma_fold.hpp, which describes it), as text: from
-// the first loads to the 17 unreduced limbs x[] of this lane's output.  Included inside that kernel and inside the fold workgroups of
-// fold_rounds_kernel (fold_rounds.hpp).  It reads, and expects in scope where it is included, exactly: the constants WAVES and DEPTH;
+// the first loads to the 17 unreduced limbs x[] of this lane's output.  Included inside that kernel alone (the fold workgroups of
+// fold_rounds_kernel, fold_rounds.hpp, loop over tiles and have the same steps as code of their own).  It reads, and expects in scope where it is included, exactly: the constants WAVES and DEPTH;
 // the kernel arguments in, m, weights, rot; the LDS pointers and arrays qd, q_lds, d_lds, kc_lds, kv_lds; tid, n, h, n_terms; tile.
 // It declares row, p, chunk, plane, qa, start, last, term_in_chunk, term_of, da, db, acc00 .. acc11, x and carry, and contains the
 // workgroup's barriers: every wave of the workgroup must pass through it.  Text and not a __device__ function for the reason given in sumcheck_small_body.hpp:

@@ -582,9 +582,13 @@ static int launch_fold_rounds(zkhip_ctx* c, hipStream_t stream, const SmallArgs&
     if (!fold_rounds_serves(m, k, small_lds_bytes(a.log_n, a.weights_out ? (int)a.n_rounds : -1, a.group != 0 && a.stride == 0)))
         return ZKHIP_ERR_SHAPE;
     ZK_TRY(c->allow_big_lds((const void*)fold_rounds_kernel, 158 * 1024));   // (~0.5 KiB of static LDS on top)
+    uint32_t cus = 0;
+    ZK_TRY(c->compute_units(&cus));
+    // one resident fold workgroup on every CU beside the serial workgroup's: no second generation, no tail (fold_schedule.hpp)
+    const uint32_t fold_wgs = fold_schedule_workgroups(m / 64, cus);
     ProfScope ps(c, "multifold", 32.0 * (double)cn + 32.0 * (double)m, stream);
     ProfScope form(c, "multifold_rounds", 0.0, stream);   // (a second record of the same launch: which form it was)
-    hipLaunchKernelGGL(fold_rounds_kernel, dim3(1 + fold_rounds_workgroups(m)), dim3(SMALL_BLOCK), FOLD_ROUNDS_LDS, stream, a, st, d_rp, d_ch,
+    hipLaunchKernelGGL(fold_rounds_kernel, dim3(1 + fold_wgs), dim3(SMALL_BLOCK), FOLD_ROUNDS_LDS, stream, a, st, d_rp, d_ch,
                        cur, m, k, d_w, dst, (uint32_t)multifold_cfg());
     ZK_HIP(c, hipGetLastError());
     return ZKHIP_OK;
