@@ -233,7 +233,10 @@ int zkhip_gkr_prove_batch(zkhip_circuit *circuit, uint32_t n_proofs, uint32_t ma
  * Layer `layer` (0 = output layer) of a device-resident circuit, d_w = the layer's input values (w_len = 2^(layer+1)).
  *   phase 0 (the rounds over b):  d_out[0] = Ha0, d_out[1] = Ha1, d_out[2] = Hm  (w_len entries each, caller-allocated); the
  *            claim's terms are [Ha0, W] + Ha1 (additive table) and [Hm, W].  h_rb / h_rc: the points the wiring is bound at
- *            (n = max(layer, 1) field elements each; h_rc NULL for the first layer proof), h_alpha / h_beta their weights.
+ *            (n = max(layer, 1) field elements each; h_rc NULL for the first layer proof), h_alpha / h_beta their weights:
+ *            w_g = alpha eq_g(r_b) + beta eq_g(r_c).  With h_rc NULL there is one point and NO weight: w_g = eq_g(r_b), and
+ *            h_alpha / h_beta are ignored (they must still point at a field element each) -- the first layer's claim is
+ *            w_0(n_r) itself (gkr/src/utils.rs:12-56).
  *   phase 1 (the rounds over c):  reads the s = layer + 1 challenges of phase 0 where the context recorded them;
  *            d_out[0] = Aa, d_out[1] = W(u) + W, d_out[2] = Am, d_out[3] = W(u) W; h_wu[4] = W(u) (= w_b of the proof).
  * zkhip_gkr_layer_tables_sharded is what a rank of a sharded proof calls (gkr/src/protocol.rs:61-108 with the evaluation tables

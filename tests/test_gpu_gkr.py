@@ -226,8 +226,10 @@ def test_gkr_device_circuit_reused_across_inputs(zk, ora):
 @pytest.mark.parametrize("stages", [False, True])
 @pytest.mark.parametrize("depth", [1, 2, 4, 8, 12])
 def test_gkr_prove_sharded_world_1_matches_prove(zk, ora, depth, stages):
-    """The sharded prover's code path (layer tables from zkhip_gkr_layer_tables, the rounds over b and over c as two zkhip_mc_*
-    sessions with an additive table and a continued transcript) on one rank: the proof must be zkhip_gkr_prove's, bit for bit."""
+    """The sharded prover's code path (zkhip_gkr_prove_sharded: the layer tables from the builder behind zkhip_gkr_layer_tables_sharded,
+    enqueued inside the library, the rounds over b and over c as two zkhip_mc_* sessions with an additive table and a continued
+    transcript) on one rank: the proof must be zkhip_gkr_prove's, bit for bit.  The public table entry points themselves are held to an
+    integer model in tests/test_gpu_gkr_layer_tables.py."""
     layers = random_circuit(depth)
     circuit = zk.Circuit.from_tuples(layers)
     inp = ora.random_fr(2 ** depth, 800 + depth)

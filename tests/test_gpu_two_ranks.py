@@ -56,9 +56,8 @@ def _worker(rank, world, port, q):
         got = [zk.SparseUnivariatePolynomial(c, p).monomials() for c, p in rps]
         res["multi_composed"] = bool(got == [p.monomials() for p in wproof.round_polys] and np.array_equal(ch, wch))
         # GKRProtocol::prove with every layer's sumcheck sharded (narrow layers run whole on every rank)
-        for depth in (5, 9, 20):      # 20 = BASELINE configs[3]'s width (2^20-value layers)
-            circuit = zk.Circuit.random(depth)
-            ev = circuit.evaluation(zk.Fr.random(2 ** depth, 300 + depth))
+        def sharded_is_the_single_gpu_proof(circuit, inp):
+            ev = circuit.evaluation(inp)
             want = zk.GKRProtocol.prove(circuit, ev)
             got = zk.GKRProtocol.prove_sharded(circuit, ev, world, rank, None, shim)
             ok = len(got.sumcheck_proofs) == len(want.sumcheck_proofs) and got._exchanges > 0
@@ -66,9 +65,20 @@ def _worker(rank, world, port, q):
                 ok = ok and np.array_equal(a.sum, b.sum) and a.to_bytes() == b.to_bytes()
             ok = ok and all(np.array_equal(a, b) for a, b in zip(got.wb_s, want.wb_s)) and all(np.array_equal(a, b) for a, b in zip(got.wc_s, want.wc_s))
             ok = ok and all(np.array_equal(a, b) for a, b in zip(got._challenges, want._challenges))
-            res["gkr_depth_%d" % depth] = bool(ok)
+            return bool(ok), got
+
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from gkr_cases import scrambled_circuit
+        # scrambled wiring: CSR rows of uneven length, inputs shared between gates, b == c, every rank owns live rows of both phases
+        # (Circuit::random's rows hold at most one gate, all of them on rank 0 in the rounds over b).  12: the widest layer whose eq tables are
+        # still chains over the index bits; 14: gate weights (13 bits) and eq(u) (13, 14 bits) built from halves on the sharded path
+        for depth, seed in ((9, 31), (12, 32), (14, 33)):
+            ok, _ = sharded_is_the_single_gpu_proof(zk.Circuit.from_tuples(scrambled_circuit(depth, seed)), zk.Fr.random(2 ** depth, 500 + depth))
+            res["gkr_scrambled_depth_%d" % depth] = ok
+        for depth in (5, 9, 20):      # 20 = BASELINE configs[3]'s width (2^20-value layers)
+            ok, got = sharded_is_the_single_gpu_proof(zk.Circuit.random(depth), zk.Fr.random(2 ** depth, 300 + depth))
+            res["gkr_depth_%d" % depth] = ok
             if depth < 20 or rank == 0:   # and against the CPU oracle's sparse-container restatement of the reference prover (15 s at depth 20)
-                sys.path.insert(0, os.path.join(ROOT, "tests"))
                 from gkr_cases import gkr_proof_mismatches, random_circuit
                 from oracle import oracle as ora
                 layers = random_circuit(depth)
