@@ -294,12 +294,12 @@ static __global__ __launch_bounds__(MLE_BLOCK) void open_steps_small_batch_kerne
 // writes the quotient / the evaluation.
 constexpr int HS_L = 8;
 constexpr int HS_T = 256;
+// The arithmetic of both passes is written once, as bodies over resolved pointers: the kernels below run one polynomial, those of
+// plonk_batch_kernels.hpp a list of jobs per proof.
 template <bool APPLY>
-static __global__ __launch_bounds__(HS_T) void horner_scan_kernel(const uint64_t* __restrict__ coeffs, size_t n, FrArg z_val,
-                                                           uint64_t* __restrict__ block_vals, const uint64_t* __restrict__ carries,
-                                                           uint64_t* __restrict__ quotient, uint64_t* __restrict__ evaluation) {
+__device__ __forceinline__ void horner_scan_body(const uint64_t* __restrict__ coeffs, size_t n, const Fr& z, uint64_t* __restrict__ block_vals,
+                                                 const uint64_t* __restrict__ carries, uint64_t* __restrict__ quotient, uint64_t* __restrict__ evaluation) {
     __shared__ Fr a_lds[HS_T];
-    const Fr z = fr_from_arg(z_val);
     const uint32_t t = threadIdx.x;
     const size_t s = ((size_t)blockIdx.x * HS_T + t) * HS_L;
     Fr c[HS_L];
@@ -340,15 +340,23 @@ static __global__ __launch_bounds__(HS_T) void horner_scan_kernel(const uint64_t
         else if (i < n) store_fr(quotient, i - 1, v);
     }
 }
+template <bool APPLY>
+static __global__ __launch_bounds__(HS_T) void horner_scan_kernel(const uint64_t* __restrict__ coeffs, size_t n, FrArg z_val,
+                                                           uint64_t* __restrict__ block_vals, const uint64_t* __restrict__ carries,
+                                                           uint64_t* __restrict__ quotient, uint64_t* __restrict__ evaluation) {
+    horner_scan_body<APPLY>(coeffs, n, fr_from_arg(z_val), block_vals, carries, quotient, evaluation);
+}
 // carries[b] = V at the base of workgroup b + 1 (0 for the last): Y_b = H_{b+1} + R Y_{b+1}, R = z^(HS_T HS_L); one workgroup
-static __global__ __launch_bounds__(1024) void horner_top_kernel(const uint64_t* __restrict__ block_vals, uint32_t n_blocks, FrArg z_val,
-                                                          uint64_t* __restrict__ carries, uint64_t* __restrict__ v0_out) {
+__device__ __forceinline__ void horner_top_body(const uint64_t* __restrict__ block_vals, uint32_t n_blocks, const Fr& z, uint64_t* __restrict__ carries,
+                                                uint64_t* __restrict__ v0_out) {
     __shared__ Fr a_lds[1024];
     const uint32_t t = threadIdx.x;
-    Fr R = fr_from_arg(z_val);
+    Fr R = z;
     for (int q = 1; q < HS_T * HS_L; q <<= 1) R = R * R;
     const uint32_t per = (n_blocks + 1023) / 1024;
-    const uint32_t lo = t * per, hi = min(lo + per, n_blocks);       // this lane's workgroups [lo, hi)
+    // this lane's workgroups [lo, hi); lo is not clamped: a lane beyond the last workgroup has hi = n_blocks <= lo and both loops
+    // below (`b = hi; b-- > lo`) end before their first step
+    const uint32_t lo = t * per, hi = min(lo + per, n_blocks);
     Fr g = Fr::zero();
     for (uint32_t b = hi; b-- > lo;) g = load_fr(block_vals, b) + R * g;   // value at the base of `lo` for zero carry-in
     Fr rp = Fr::one();                                               // R^per
@@ -371,6 +379,10 @@ static __global__ __launch_bounds__(1024) void horner_top_kernel(const uint64_t*
         y = load_fr(block_vals, b) + R * y;
     }
     if (t == 0 && v0_out) store_fr(v0_out, 0, y);   // V at the base of workgroup 0 = p(z)
+}
+static __global__ __launch_bounds__(1024) void horner_top_kernel(const uint64_t* __restrict__ block_vals, uint32_t n_blocks, FrArg z_val,
+                                                          uint64_t* __restrict__ carries, uint64_t* __restrict__ v0_out) {
+    horner_top_body(block_vals, n_blocks, fr_from_arg(z_val), carries, v0_out);
 }
 // DenseUnivariatePolynomial::degree (dense_univariate.rs:199-207): index of the last non-zero coefficient, 0 if none;
 // *out must be zeroed first

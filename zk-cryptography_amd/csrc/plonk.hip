@@ -20,6 +20,7 @@
 #include "plonk_batch_kernels.hpp"
 #include "plonk_kernels.hpp"
 #include "plonk_scalars.hpp"
+#include "plonk_transcript.hpp"
 #include "plonk_verify_kernels.hpp"
 #include "tunables.hpp"
 
@@ -27,7 +28,10 @@ using namespace zk;
 
 namespace {
 
-using HFr = zkhost::Fr;
+// Host only, each with a stand-alone sanitizer program under tests/cpp: plonk_scalars.hpp (HFr, h_is_zero, h_neg, h_pow, l1_at and the
+// verifier's scalar algebra) and plonk_transcript.hpp (the Merlin transcript, the rounds' schedule PlonkRoundTranscript and the ABI's
+// orders P_*, E_*, C_*).
+using namespace zkplonk;
 using zkhost::fr_add;
 using zkhost::fr_mul;
 using zkhost::fr_sub;
@@ -35,90 +39,6 @@ using zkhost::fr_sub;
 inline HFr h_load(const uint64_t* p) { HFr r; std::memcpy(r.l, p, 32); return r; }
 inline FrArg fa(const HFr& a) { FrArg r; std::memcpy(r.v, a.l, 32); return r; }
 inline bool h_eq(const HFr& a, const HFr& b) { return std::memcmp(a.l, b.l, 32) == 0; }
-using zkplonk::h_is_zero;      // plonk_scalars.hpp: shared with the verifier's scalar algebra
-using zkplonk::h_neg;
-using zkplonk::h_pow;
-using zkplonk::l1_at;
-
-// ---- MerlinTranscript (transcripts/merlin/src/lib.rs:11-49) and PlonkRoundTranscript (plonk/src/protocol/transcript.rs) ----------
-// canonical integer of a Montgomery Fq element in decimal, leading zeros trimmed (ark-ff 0.4.2 Display for Fp: zero prints as "")
-std::string fq_decimal(const uint64_t* mont) {
-    zkhost::Fq a, one = zkhost::fq_zero();
-    std::memcpy(a.l, mont, 48);
-    one.l[0] = 1;
-    zkhost::Fq c = zkhost::fq_mul(a, one);
-    std::string out;
-    for (;;) {
-        bool zero = true;
-        for (int i = 0; i < 6; ++i) zero = zero && c.l[i] == 0;
-        if (zero) break;
-        unsigned __int128 rem = 0;                                 // c /= 10^19
-        const uint64_t base = 10000000000000000000ull;
-        for (int i = 5; i >= 0; --i) {
-            const unsigned __int128 cur = (rem << 64) | c.l[i];
-            c.l[i] = (uint64_t)(cur / base);
-            rem = cur % base;
-        }
-        char buf[24];
-        snprintf(buf, sizeof buf, "%019llu", (unsigned long long)(uint64_t)rem);
-        out.insert(0, buf);
-    }
-    const size_t nz = out.find_first_not_of('0');
-    return nz == std::string::npos ? std::string() : out.substr(nz);
-}
-// ark-ec 0.4.2 Display for an affine point: "(x, y)", the identity "infinity"
-std::string point_string(const uint64_t* xy, bool inf) {
-    if (inf) return "infinity";
-    return "(" + fq_decimal(xy) + ", " + fq_decimal(xy + 6) + ")";
-}
-
-struct Merlin {
-    zkhost::Sha256 hasher;
-    explicit Merlin(const char* label) {                           // :12-21
-        hasher.update((const uint8_t*)"Merlin Transcript", 17);
-        hasher.update((const uint8_t*)label, std::strlen(label));
-    }
-    void append_message(const char* label, const uint8_t* m, size_t len) {   // :23-28 label, len as 8 bytes little-endian, message
-        hasher.update((const uint8_t*)label, std::strlen(label));
-        uint8_t le[8];
-        for (int i = 0; i < 8; ++i) le[i] = (uint8_t)((uint64_t)len >> (8 * i));
-        hasher.update(le, 8);
-        hasher.update(m, len);
-    }
-    void append_scalar(const char* label, const HFr& mont) {       // :30-35 serialize_compressed: 32 bytes little-endian canonical
-        const HFr c = zkhost::fr_from_mont(mont);
-        uint8_t b[32];
-        for (int i = 0; i < 32; ++i) b[i] = (uint8_t)(c.l[i / 8] >> (8 * (i % 8)));
-        append_message(label, b, 32);
-    }
-    void append_point(const char* label, const uint64_t* xy, bool inf) {     // :37-41 the UTF-8 of to_string()
-        const std::string s = point_string(xy, inf);
-        append_message(label, (const uint8_t*)s.data(), s.size());
-    }
-    HFr challenge(const char* label) {                             // :43-49 finalize_reset: the label goes into the EMPTY hasher
-        uint8_t d[32];
-        hasher.finish(d);
-        hasher.reset();
-        hasher.update((const uint8_t*)label, std::strlen(label));
-        uint64_t t[4];
-        for (int i = 0; i < 4; ++i) {
-            uint64_t w = 0;
-            for (int j = 0; j < 8; ++j) w = (w << 8) | d[8 * (3 - i) + j];
-            t[i] = w;
-        }
-        while (zkhost::fr_geq_p(t)) zkhost::fr_sub_p(t);            // from_be_bytes_mod_order
-        HFr c, r2;
-        std::memcpy(c.l, t, 32);
-        std::memcpy(r2.l, zkhost::FR_R2, 32);
-        return fr_mul(c, r2);
-    }
-};
-
-// proof layout of the ABI: points as, bs, cs, accumulator, t_low, t_mid, t_high, w_zeta, w_zeta_omega; evaluations a, b, c, sigma1,
-// sigma2, w_accumulator; challenges beta, gamma, alpha, zeta, nu, mu
-enum { P_AS, P_BS, P_CS, P_ACC, P_TL, P_TM, P_TH, P_WZ, P_WZW, N_POINTS };
-enum { E_A, E_B, E_C, E_S1, E_S2, E_ZW, N_EVALS };
-enum { C_BETA, C_GAMMA, C_ALPHA, C_ZETA, C_NU, C_MU, N_CHALLENGES };
 
 // ---- the key --------------------------------------------------------------------------------------------------------------------
 // Coset evaluations of the eight preprocessed columns, of L_1 and of X: ten vectors of D elements.  They are kept with the key up to
@@ -158,10 +78,72 @@ struct Work {
     uint64_t* pre;                                                          // 10 D when the key holds no cache
     size_t zero_bytes;                                                      // the leading part a proof clears
 };
+// workgroups of a Horner scan over n coefficients; a job's row of workgroup values (and of carries) in the work area
+inline uint32_t horner_blocks(size_t n) { return (uint32_t)((n + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L)); }
+inline size_t horner_row(const zkhip_plonk_key& k) { return (size_t)horner_blocks(k.S) + 1; }
+
+// ---- the round table ------------------------------------------------------------------------------------------------------------
+// What the five rounds commit, transform, evaluate, divide and combine, stated once: zkhip_plonk_prove walks these rows with proof 0's
+// pointers, BatchRun::rounds packs the same rows into its kernels' argument structs.  A row's polynomial is a member of the proof's
+// work area (`own`) or, where `own` is null, coefficient column `key_col` of the key; its length is n + extra.
+struct RoundPoly {
+    uint64_t* Work::*own; int key_col; int extra;
+    bool at_zeta_w;                                            // Horner jobs: the point is w zeta, not zeta
+    uint64_t* Work::*quotient;                                 // divisions: where (p(X) - p(z)) / (X - z) goes
+};
+constexpr RoundPoly own_poly(uint64_t* Work::*m, int extra, bool at_zeta_w = false, uint64_t* Work::*quotient = nullptr) {
+    return {m, -1, extra, at_zeta_w, quotient};
+}
+constexpr RoundPoly key_poly(int col) { return {nullptr, col, 0, false, nullptr}; }
+// the commitments of rounds 1, 2, 3 and 5 (prover.rs:113-123, 167-175, 249-258, 361-376): first point of the proof, count, polynomials
+struct CommitRound { int first, m; RoundPoly p[3]; };
+constexpr CommitRound COMMIT_WIRES = {P_AS, 3, {own_poly(&Work::A, 2), own_poly(&Work::B, 2), own_poly(&Work::C, 2)}};
+constexpr CommitRound COMMIT_ACC = {P_ACC, 1, {own_poly(&Work::Z, 3)}};
+constexpr CommitRound COMMIT_T = {P_TL, 3, {own_poly(&Work::TL, 1), own_poly(&Work::TM, 1), own_poly(&Work::TH, 6)}};
+constexpr CommitRound COMMIT_OPENINGS = {P_WZ, 2, {own_poly(&Work::Q1, 5), own_poly(&Work::Q2, 2)}};
+// round 3: the rows of `ev`, in the order plonk_quotient_kernel reads them
+constexpr RoundPoly COSET_INPUTS[PB_COSET_ROWS] = {own_poly(&Work::A, 2), own_poly(&Work::B, 2), own_poly(&Work::C, 2), own_poly(&Work::Z, 3),
+                                                   own_poly(&Work::PI, 0)};
+// round 4: the six evaluations in the ABI's order E_*, then PI(zeta) for round 5; job j's value is element j of `out`
+constexpr RoundPoly EVAL_JOBS[PB_JOBS] = {own_poly(&Work::A, 2), own_poly(&Work::B, 2), own_poly(&Work::C, 2), key_poly(5), key_poly(6),
+                                          own_poly(&Work::Z, 3, true),       // apply_w_to_polynomial(z)(zeta) = z(w zeta)
+                                          own_poly(&Work::PI, 0)};
+// round 5: W_zeta = (r + nu-combination) / (X - zeta), W_zeta_omega = (z - z(w zeta)) / (X - w zeta)
+constexpr RoundPoly DIVIDE_JOBS[2] = {own_poly(&Work::W, 6, false, &Work::Q1), own_poly(&Work::Z, 3, true, &Work::Q2)};
+// round 5: the vectors of plonk_linearise_kernel's terms, in the order of round5_scalars' weights
+constexpr RoundPoly LIN_TERMS[PLONK_LIN_TERMS] = {key_poly(0), key_poly(1), key_poly(2), key_poly(3), key_poly(4), own_poly(&Work::Z, 3), key_poly(7),
+                                                  own_poly(&Work::TL, 1), own_poly(&Work::TM, 1), own_poly(&Work::TH, 6), own_poly(&Work::A, 2),
+                                                  own_poly(&Work::B, 2), own_poly(&Work::C, 2), key_poly(5), key_poly(6)};
+static_assert(EVAL_JOBS[E_ZW].at_zeta_w && EVAL_JOBS[E_S1].key_col == 5 && EVAL_JOBS[E_S2].key_col == 6, "the evaluations in the ABI's order");
+
+uint64_t* poly_at(const zkhip_plonk_key& k, const Work& w, const RoundPoly& r) { return r.own ? w.*r.own : k.col_coeff(r.key_col); }
+// bit j set: row j is the proof's own polynomial (the batch kernels move it by the proof's offset), not the key's
+template <int N> constexpr uint32_t own_mask(const RoundPoly (&rows)[N]) {
+    uint32_t m = 0;
+    for (int j = 0; j < N; ++j) m |= (rows[j].own != nullptr ? 1u : 0u) << j;
+    return m;
+}
+// commit, coset and division rows are read as w.*row.own: every one of them must be the proof's own
+constexpr bool all_own(const CommitRound& r) {
+    for (int j = 0; j < r.m; ++j) if (r.p[j].own == nullptr) return false;
+    return true;
+}
+static_assert(all_own(COMMIT_WIRES) && all_own(COMMIT_ACC) && all_own(COMMIT_T) && all_own(COMMIT_OPENINGS) &&
+              own_mask(COSET_INPUTS) == (1u << PB_COSET_ROWS) - 1 && DIVIDE_JOBS[0].quotient != nullptr && DIVIDE_JOBS[1].quotient != nullptr,
+              "a commit, a coset input or a division names a member of the work area");
+static_assert(own_mask(EVAL_JOBS) == 0x67u && own_mask(DIVIDE_JOBS) == 3u && own_mask(LIN_TERMS) == ((1u << 5) | (0x3fu << 7)),
+              "sigma_1 and sigma_2 are the key's among the evaluations; z, the parts of t and the wires are the proof's among the terms");
+struct CommitSet { uint64_t* polys[3]; size_t lens[3]; };
+CommitSet commit_set(const Work& w, size_t n, const CommitRound& r) {
+    CommitSet s = {};
+    for (int j = 0; j < r.m; ++j) { s.polys[j] = w.*r.p[j].own; s.lens[j] = n + r.p[j].extra; }
+    return s;
+}
+
 size_t work_layout(const zkhip_plonk_key& k, char* base, bool with_pre, Work* w) {
     size_t off = 0;
     auto take = [&](size_t elems) { uint64_t* p = (uint64_t*)(base + off); off += (elems * 32 + 255) & ~(size_t)255; return p; };
-    const size_t nb = (k.S + GP_ROWS - 1) / GP_ROWS + 1, hb = (k.S + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L) + 1;
+    const size_t nb = (k.S + GP_ROWS - 1) / GP_ROWS + 1, hb = horner_row(k);
     Work t;
     uint64_t** s[] = {&t.A, &t.B, &t.C, &t.Z, &t.PI, &t.TL, &t.TM, &t.TH, &t.W, &t.Q1, &t.Q2, &t.F, &t.ACC};
     for (auto p : s) *p = take(k.S);
@@ -227,13 +209,13 @@ int commit_group(const zkhip_plonk_key& k, const uint64_t* const* polys, const s
 
 // p(z) of n coefficients -> out (device): the scan of zkhip_dense_evaluate
 void eval_at(zkhip_ctx* c, const Work& w, const uint64_t* coeffs, size_t n, const HFr& z, uint64_t* out) {
-    const uint32_t nb = (uint32_t)((n + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L));
+    const uint32_t nb = horner_blocks(n);
     hipLaunchKernelGGL(horner_scan_kernel<false>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), w.hv, nullptr, nullptr, nullptr);
     hipLaunchKernelGGL(horner_top_kernel, dim3(1), dim3(1024), 0, c->stream, w.hv, nb, fa(z), w.hc, out);
 }
 // (p(X) - p(z)) / (X - z): n - 1 quotient coefficients, the scan of zkhip_univariate_kzg_open; the remainder p(z) goes to rem
 void divide_by_linear(zkhip_ctx* c, const Work& w, const uint64_t* coeffs, size_t n, const HFr& z, uint64_t* quotient, uint64_t* rem) {
-    const uint32_t nb = (uint32_t)((n + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L));
+    const uint32_t nb = horner_blocks(n);
     hipLaunchKernelGGL(horner_scan_kernel<false>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), w.hv, nullptr, nullptr, nullptr);
     hipLaunchKernelGGL(horner_top_kernel, dim3(1), dim3(1024), 0, c->stream, w.hv, nb, fa(z), w.hc, (uint64_t*)nullptr);
     hipLaunchKernelGGL(horner_scan_kernel<true>, dim3(nb), dim3(HS_T), 0, c->stream, coeffs, n, fa(z), nullptr, w.hc, quotient, rem);
@@ -275,18 +257,13 @@ void round5_scalars(const zkhip_plonk_key& k, const HFr* ch, const HFr* ev, HFr*
 }
 
 void absorb_challenges_from_proof(const uint64_t* xy, const uint8_t* inf, const uint64_t* evals, HFr* ch) {   // protocol/utils.rs:56-96
-    Merlin t("plonk_protocol");
-    for (int p = P_AS; p <= P_CS; ++p) t.append_point("first_round", xy + 12 * p, inf[p] != 0);
-    ch[C_BETA] = t.challenge("beta");
-    ch[C_GAMMA] = t.challenge("gamma");
-    t.append_point("second_round", xy + 12 * P_ACC, inf[P_ACC] != 0);
-    ch[C_ALPHA] = t.challenge("alpha");
-    for (int p = P_TL; p <= P_TH; ++p) t.append_point("third_round", xy + 12 * p, inf[p] != 0);
-    ch[C_ZETA] = t.challenge("zeta");
-    for (int e = 0; e < N_EVALS; ++e) t.append_scalar("fourth_round", h_load(evals + 4 * e));
-    ch[C_NU] = t.challenge("nu");
-    for (int p = P_WZ; p <= P_WZW; ++p) t.append_point("fifth_round", xy + 12 * p, inf[p] != 0);
-    ch[C_MU] = t.challenge("mu");
+    PlonkRoundTranscript t;
+    t.first_round(xy, inf);
+    t.second_round(xy, inf);
+    t.third_round(xy, inf);
+    t.fourth_round(evals);
+    t.fifth_round(xy, inf);
+    std::memcpy(ch, t.ch, sizeof t.ch);
 }
 
 // ---- host G1 for the verifier's combination ---------------------------------------------------------------------------------------
@@ -417,29 +394,30 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
     uint64_t* xy[N_POINTS]; uint8_t* inf[N_POINTS];
     for (int p = 0; p < N_POINTS; ++p) { xy[p] = h_points_xy + 12 * p; inf[p] = h_points_inf + p; }
     ZK_HIP(c, hipMemsetAsync(w.A, 0, w.zero_bytes, c->stream));
-    Merlin tr("plonk_protocol");
-    HFr ch[N_CHALLENGES];
+    PlonkRoundTranscript tr;
+    const HFr* const ch = tr.ch;
+    auto commit = [&](const CommitRound& r) {
+        const CommitSet cs = commit_set(w, n, r);
+        return commit_group(k, cs.polys, cs.lens, r.m, &xy[r.first], &inf[r.first]);
+    };
 
     // ---- round 1 (prover.rs:98-123): a_s = (r0 X + r1) Z_H + a, likewise b_s, c_s
     {
         const uint64_t* wires[3] = {d_a, d_b, d_c};
-        uint64_t* dst[3] = {w.A, w.B, w.C};
         for (int j = 0; j < 3; ++j) {
-            ZK_TRY(zkhip_domain_transform(c, wires[j], n, dst[j], k.log_n, 1));
+            uint64_t* const dst = w.*COMMIT_WIRES.p[j].own;
+            ZK_TRY(zkhip_domain_transform(c, wires[j], n, dst, k.log_n, 1));
             PlonkBlindArg b = {};
             std::memcpy(b.v, bl[2 * j + 1].l, 32);                 // constant coefficient: rands[1], then rands[0] X
             std::memcpy(b.v + 4, bl[2 * j].l, 32);
-            hipLaunchKernelGGL(plonk_blind_kernel, dim3(1), dim3(64), 0, c->stream, dst[j], n, 2u, b);
+            hipLaunchKernelGGL(plonk_blind_kernel, dim3(1), dim3(64), 0, c->stream, dst, n, 2u, b);
         }
         ZK_TRY(zkhip_domain_transform(c, d_public, n, w.PI, k.log_n, 1));
         ZK_HIP(c, hipGetLastError());
-        const size_t lens[3] = {n + 2, n + 2, n + 2};
-        ZK_TRY(commit_group(k, dst, lens, 3, &xy[P_AS], &inf[P_AS]));
-        for (int p = P_AS; p <= P_CS; ++p) tr.append_point("first_round", xy[p], *inf[p] != 0);
+        ZK_TRY(commit(COMMIT_WIRES));
     }
+    tr.first_round(h_points_xy, h_points_inf);
     // ---- round 2 (:125-175): the accumulator, z = (r0 + r1 X + r2 X^2) Z_H + acc
-    ch[C_BETA] = tr.challenge("beta");
-    ch[C_GAMMA] = tr.challenge("gamma");
     {
         PlonkCols cols;
         for (int j = 0; j < 8; ++j) cols.q[j] = k.col_eval(j);
@@ -460,17 +438,12 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
         for (int j = 0; j < 3; ++j) std::memcpy(b.v + 4 * j, bl[6 + j].l, 32);
         hipLaunchKernelGGL(plonk_blind_kernel, dim3(1), dim3(64), 0, c->stream, w.Z, n, 3u, b);
         ZK_HIP(c, hipGetLastError());
-        const uint64_t* polys[1] = {w.Z};
-        const size_t lens[1] = {n + 3};
-        ZK_TRY(commit_group(k, polys, lens, 1, &xy[P_ACC], &inf[P_ACC]));
-        tr.append_point("second_round", xy[P_ACC], *inf[P_ACC] != 0);
+        ZK_TRY(commit(COMMIT_ACC));
     }
+    tr.second_round(h_points_xy, h_points_inf);
     // ---- round 3 (:177-258): t = numerator / Z_H on the coset, back to coefficients, split and blinded
-    ch[C_ALPHA] = tr.challenge("alpha");
     {
-        const uint64_t* src[5] = {w.A, w.B, w.C, w.Z, w.PI};
-        const size_t lens5[5] = {n + 2, n + 2, n + 2, n + 3, n};
-        for (int j = 0; j < 5; ++j) ZK_TRY(coset_forward(k, src[j], lens5[j], w.ev + 4 * D * j));
+        for (int j = 0; j < PB_COSET_ROWS; ++j) ZK_TRY(coset_forward(k, w.*COSET_INPUTS[j].own, n + COSET_INPUTS[j].extra, w.ev + 4 * D * j));
         if (!k.pre) ZK_TRY(fill_pre(k, w.pre, w.W));
         PlonkQuotArg q = {};
         q.beta = fa(ch[C_BETA]); q.gamma = fa(ch[C_GAMMA]); q.alpha = fa(ch[C_ALPHA]); q.alpha2 = fa(fr_mul(ch[C_ALPHA], ch[C_ALPHA]));
@@ -491,38 +464,30 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
         bool bad = false;
         ZK_TRY(read_flags(c, w, &bad));
         if (bad) return ZKHIP_ERR_ARG;      // Z_H does not divide the numerator: no proof from it
-        const uint64_t* polys[3] = {w.TL, w.TM, w.TH};
-        const size_t lens[3] = {n + 1, n + 1, n + 6};
-        ZK_TRY(commit_group(k, polys, lens, 3, &xy[P_TL], &inf[P_TL]));
-        for (int p = P_TL; p <= P_TH; ++p) tr.append_point("third_round", xy[p], *inf[p] != 0);
+        ZK_TRY(commit(COMMIT_T));
     }
+    tr.third_round(h_points_xy, h_points_inf);
     // ---- round 4 (:260-293): six evaluations (and PI(zeta) for round 5)
-    ch[C_ZETA] = tr.challenge("zeta");
     const HFr zeta = ch[C_ZETA], zeta_w = fr_mul(zeta, k.w_n);
-    HFr ev[7];
+    HFr ev[PB_JOBS];
     {
         ProfScope ps(c, "plonk_evaluate", 32.0 * 7.0 * (double)n);
-        eval_at(c, w, w.A, n + 2, zeta, w.out + 4 * E_A);
-        eval_at(c, w, w.B, n + 2, zeta, w.out + 4 * E_B);
-        eval_at(c, w, w.C, n + 2, zeta, w.out + 4 * E_C);
-        eval_at(c, w, k.col_coeff(5), n, zeta, w.out + 4 * E_S1);
-        eval_at(c, w, k.col_coeff(6), n, zeta, w.out + 4 * E_S2);
-        eval_at(c, w, w.Z, n + 3, zeta_w, w.out + 4 * E_ZW);       // apply_w_to_polynomial(z)(zeta) = z(w zeta)
-        eval_at(c, w, w.PI, n, zeta, w.out + 4 * 6);
+        for (int j = 0; j < PB_JOBS; ++j) {
+            const RoundPoly& e = EVAL_JOBS[j];
+            eval_at(c, w, poly_at(k, w, e), n + e.extra, e.at_zeta_w ? zeta_w : zeta, w.out + 4 * j);
+        }
     }
     ZK_HIP(c, hipGetLastError());
     ZK_HIP(c, hipMemcpyAsync(ev, w.out, sizeof ev, hipMemcpyDeviceToHost, c->stream));
     ZK_HIP(c, hipStreamSynchronize(c->stream));
-    for (int e = 0; e < N_EVALS; ++e) { std::memcpy(h_evals + 4 * e, ev[e].l, 32); tr.append_scalar("fourth_round", ev[e]); }
+    std::memcpy(h_evals, ev, 32 * N_EVALS);
+    tr.fourth_round(h_evals);
     // ---- round 5 (:295-376): W_zeta = (r + nu-combination) / (X - zeta), W_zeta_omega = (z - z(w zeta)) / (X - w zeta)
-    ch[C_NU] = tr.challenge("nu");
     {
         HFr s[PLONK_LIN_TERMS], c0;
         round5_scalars(k, ch, ev, s, &c0);
         PlonkLinArg L = {};
-        const uint64_t* ptr[PLONK_LIN_TERMS] = {k.col_coeff(0), k.col_coeff(1), k.col_coeff(2), k.col_coeff(3), k.col_coeff(4), w.Z, k.col_coeff(7),
-                                                w.TL, w.TM, w.TH, w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6)};
-        for (int j = 0; j < PLONK_LIN_TERMS; ++j) { L.p[j] = ptr[j]; L.s[j] = fa(s[j]); }
+        for (int j = 0; j < PLONK_LIN_TERMS; ++j) { L.p[j] = poly_at(k, w, LIN_TERMS[j]); L.s[j] = fa(s[j]); }
         L.c0 = fa(c0);
         {
             ProfScope ps(c, "plonk_linearise", 32.0 * 16.0 * (double)n);
@@ -530,17 +495,16 @@ extern "C" int zkhip_plonk_prove(zkhip_plonk_key* key, const uint64_t* d_a, cons
         }
         {
             ProfScope ps(c, "plonk_divide", 96.0 * 2.0 * (double)n);
-            divide_by_linear(c, w, w.W, n + 6, zeta, w.Q1, w.out);
-            divide_by_linear(c, w, w.Z, n + 3, zeta_w, w.Q2, w.out + 4);
+            for (int j = 0; j < 2; ++j) {
+                const RoundPoly& d = DIVIDE_JOBS[j];
+                divide_by_linear(c, w, w.*d.own, n + d.extra, d.at_zeta_w ? zeta_w : zeta, w.*d.quotient, w.out + 4 * j);
+            }
         }
         ZK_HIP(c, hipGetLastError());
-        const uint64_t* polys[2] = {w.Q1, w.Q2};
-        const size_t lens[2] = {n + 5, n + 2};
-        ZK_TRY(commit_group(k, polys, lens, 2, &xy[P_WZ], &inf[P_WZ]));
-        for (int p = P_WZ; p <= P_WZW; ++p) tr.append_point("fifth_round", xy[p], *inf[p] != 0);
+        ZK_TRY(commit(COMMIT_OPENINGS));
     }
-    ch[C_MU] = tr.challenge("mu");
-    if (h_challenges) std::memcpy(h_challenges, ch, sizeof ch);
+    tr.fifth_round(h_points_xy, h_points_inf);
+    if (h_challenges) std::memcpy(h_challenges, ch, sizeof tr.ch);
     return ZKHIP_OK;
 }
 
@@ -566,7 +530,7 @@ inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 BatchLayout batch_layout(const zkhip_plonk_key& k, uint32_t chunk) {
     BatchLayout L;
     const size_t base = work_layout(k, nullptr, false, nullptr);
-    L.hb = (k.S + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L) + 1;
+    L.hb = horner_row(k);
     L.o_hv = base;
     L.o_hc = L.o_hv + al256((size_t)PB_JOBS * L.hb * 32);
     L.per = L.o_hc + al256((size_t)PB_JOBS * L.hb * 32);
@@ -599,8 +563,8 @@ void pack_columns(const uint64_t* const* a, const uint64_t* const* b, const uint
 
 // one proof of a chunk on the host: its transcript, challenges, blinding and verdict
 struct BatchProof {
-    Merlin tr{"plonk_protocol"};
-    HFr ch[N_CHALLENGES], ev[PB_JOBS];
+    PlonkRoundTranscript tr;                                   // with the proof's challenges, tr.ch
+    HFr ev[PB_JOBS];
     bool refused = false;
 };
 
@@ -646,7 +610,12 @@ struct BatchRun {
     }
     // One round's commits of the chunk, m polynomials per proof, results at point `first` on; ends in the round's synchronisation.
     // Short path: one launch chain for all of them.  Otherwise commit_group, three in flight, proof after proof.
-    int commit(uint64_t* const* polys, const size_t* lens, uint32_t m, int first) {
+    int commit(const CommitRound& r) {
+        const CommitSet cs = commit_set(w, k.n, r);
+        uint64_t* const* polys = cs.polys;
+        const size_t* lens = cs.lens;
+        const uint32_t m = (uint32_t)r.m;
+        const int first = r.first;
         if (k.srs_table && zk_msm_commit_batch_serves(k.n_points, k.n + 6)) {
             size_t off[3];
             for (uint32_t j = 0; j < m; ++j) off[j] = (size_t)(polys[j] - w.A) / 4;
@@ -666,14 +635,31 @@ struct BatchRun {
         }
         return ZKHIP_OK;
     }
+    // the jobs of one Horner launch chain from rows of the round table; *nb: the workgroups of the longest job
+    template <int N> HornerBatchArg horner_arg(const RoundPoly (&jobs)[N], uint32_t* nb) {
+        static_assert(N <= PB_JOBS, "a launch takes up to PB_JOBS jobs");
+        HornerBatchArg h = {};
+        size_t longest = 0;
+        for (int j = 0; j < N; ++j) {
+            h.coeffs[j] = poly_at(k, w, jobs[j]);
+            h.quotient[j] = jobs[j].quotient ? w.*jobs[j].quotient : nullptr;
+            h.len[j] = (uint32_t)(k.n + jobs[j].extra);
+            h.zslot[j] = jobs[j].at_zeta_w ? PB_ZETA_W : PB_ZETA;
+            longest = std::max<size_t>(longest, h.len[j]);
+        }
+        h.own = own_mask(jobs);
+        h.vstride = (uint32_t)L.hb;
+        *nb = horner_blocks(longest);
+        return h;
+    }
     int rounds(const uint64_t* const* h_cols, bool* pre_ready);
 };
 
 int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
     const size_t n = k.n, D = k.D, ws = L.ws, fs = L.fs;
     const uint64_t* pre = k.pre ? (const uint64_t*)k.pre.get() : (const uint64_t*)(dev + L.o_pre);
-    auto point = [&](uint32_t b, int p) { return xy + 12 * ((size_t)b * N_POINTS + p); };
-    auto is_inf = [&](uint32_t b, int p) { return inf[(size_t)b * N_POINTS + p] != 0; };
+    auto points = [&](uint32_t b) { return xy + 12 * (size_t)N_POINTS * b; };      // proof b's nine points and their flags
+    auto flags = [&](uint32_t b) { return inf + (size_t)N_POINTS * b; };
     ZK_HIP(c, hipMemset2DAsync(w.A, L.per, 0, w.zero_bytes, bc, c->stream));
     // ---- round 1: the columns into the areas, to coefficients, blinded, committed
     std::memcpy(pin + L.p_cols, h_cols, (size_t)bc * 4 * sizeof(uint64_t*));
@@ -692,15 +678,12 @@ int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
         static const uint8_t slots[3][3] = {{1, 0, 0}, {3, 2, 0}, {5, 4, 0}};      // constant coefficient: rands[1], then rands[0] X
         blind(dst, 3, 2, slots);
         ZK_HIP(c, hipGetLastError());
-        const size_t lens[3] = {n + 2, n + 2, n + 2};
         ZK_TRY(copy_flags());
-        ZK_TRY(commit(dst, lens, 3, P_AS));
+        ZK_TRY(commit(COMMIT_WIRES));
     }
     each([&](uint32_t b) {
-        for (int p = P_AS; p <= P_CS; ++p) pr[b].tr.append_point("first_round", point(b, p), is_inf(b, p));
-        pr[b].ch[C_BETA] = pr[b].tr.challenge("beta");
-        pr[b].ch[C_GAMMA] = pr[b].tr.challenge("gamma");
-        slot(b, PB_BETA) = pr[b].ch[C_BETA]; slot(b, PB_GAMMA) = pr[b].ch[C_GAMMA];
+        pr[b].tr.first_round(points(b), flags(b));
+        slot(b, PB_BETA) = pr[b].tr.ch[C_BETA]; slot(b, PB_GAMMA) = pr[b].tr.ch[C_GAMMA];
     });
     // ---- round 2: the accumulator
     ZK_TRY(upload_par());
@@ -724,22 +707,18 @@ int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
         static const uint8_t slots[1][3] = {{6, 7, 8}};
         blind(polys, 1, 3, slots);
         ZK_HIP(c, hipGetLastError());
-        const size_t lens[1] = {n + 3};
-        ZK_TRY(commit(polys, lens, 1, P_ACC));
+        ZK_TRY(commit(COMMIT_ACC));
         read_flags();       // a row breaks the gate identity, a denominator vanishes or the accumulator does not close: that proof is refused
     }
     each([&](uint32_t b) {
-        pr[b].tr.append_point("second_round", point(b, P_ACC), is_inf(b, P_ACC));
-        pr[b].ch[C_ALPHA] = pr[b].tr.challenge("alpha");
-        slot(b, PB_ALPHA) = pr[b].ch[C_ALPHA]; slot(b, PB_ALPHA2) = fr_mul(pr[b].ch[C_ALPHA], pr[b].ch[C_ALPHA]);
+        pr[b].tr.second_round(points(b), flags(b));
+        slot(b, PB_ALPHA) = pr[b].tr.ch[C_ALPHA]; slot(b, PB_ALPHA2) = fr_mul(pr[b].tr.ch[C_ALPHA], pr[b].tr.ch[C_ALPHA]);
     });
     // ---- round 3: the quotient on the coset
     ZK_TRY(upload_par());
     {
         PlonkPadBatchArg pad = {};
-        const uint64_t* src[PB_COSET_ROWS] = {w.A, w.B, w.C, w.Z, w.PI};
-        const size_t lens5[PB_COSET_ROWS] = {n + 2, n + 2, n + 2, n + 3, n};
-        for (int j = 0; j < PB_COSET_ROWS; ++j) { pad.src[j] = src[j]; pad.len[j] = (uint32_t)lens5[j]; }
+        for (int j = 0; j < PB_COSET_ROWS; ++j) { pad.src[j] = w.*COSET_INPUTS[j].own; pad.len[j] = (uint32_t)(n + COSET_INPUTS[j].extra); }
         {
             ProfScope ps(c, "plonk_batch_scale_pad", 32.0 * 5.0 * (double)(D + n) * bc);
             hipLaunchKernelGGL(plonk_batch_scale_pad_kernel, dim3(mle_grid_stream(D), PB_COSET_ROWS, bc), dim3(MLE_BLOCK), 0, c->stream, pad,
@@ -767,28 +746,18 @@ int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
         }
         ZK_HIP(c, hipGetLastError());
         ZK_TRY(copy_flags());
-        uint64_t* polys[3] = {w.TL, w.TM, w.TH};
-        const size_t lens[3] = {n + 1, n + 1, n + 6};
-        ZK_TRY(commit(polys, lens, 3, P_TL));
+        ZK_TRY(commit(COMMIT_T));
         read_flags();       // Z_H does not divide the numerator: no proof from it
     }
     each([&](uint32_t b) {
-        for (int p = P_TL; p <= P_TH; ++p) pr[b].tr.append_point("third_round", point(b, p), is_inf(b, p));
-        pr[b].ch[C_ZETA] = pr[b].tr.challenge("zeta");
-        slot(b, PB_ZETA) = pr[b].ch[C_ZETA]; slot(b, PB_ZETA_W) = fr_mul(pr[b].ch[C_ZETA], k.w_n);
+        pr[b].tr.third_round(points(b), flags(b));
+        slot(b, PB_ZETA) = pr[b].tr.ch[C_ZETA]; slot(b, PB_ZETA_W) = fr_mul(pr[b].tr.ch[C_ZETA], k.w_n);
     });
     // ---- round 4: the six evaluations and PI(zeta), seven jobs per proof in one scan and one top launch
     ZK_TRY(upload_par());
-    const size_t per_block = (size_t)HS_T * HS_L;
     {
-        HornerBatchArg h = {};
-        const uint64_t* poly[PB_JOBS] = {w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6), w.Z, w.PI};       // the order of the evaluations, then PI
-        const size_t len[PB_JOBS] = {n + 2, n + 2, n + 2, n, n, n + 3, n};
-        for (int j = 0; j < PB_JOBS; ++j) { h.coeffs[j] = poly[j]; h.len[j] = (uint32_t)len[j]; h.zslot[j] = PB_ZETA; }
-        h.zslot[E_ZW] = PB_ZETA_W;                             // apply_w_to_polynomial(z)(zeta) = z(w zeta)
-        h.own = 0x67u;                                         // A, B, C, Z, PI are the proof's; sigma_1, sigma_2 the key's
-        h.vstride = (uint32_t)L.hb;
-        const uint32_t nb = (uint32_t)((n + 3 + per_block - 1) / per_block);
+        uint32_t nb;
+        const HornerBatchArg h = horner_arg(EVAL_JOBS, &nb);
         {
             ProfScope ps(c, "plonk_batch_evaluate", 32.0 * 7.0 * (double)n * bc);
             hipLaunchKernelGGL(horner_batch_scan_kernel<false>, dim3(nb, PB_JOBS, bc), dim3(HS_T), 0, c->stream, h, par, hv, (const uint64_t*)nullptr,
@@ -801,30 +770,23 @@ int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
     }
     each([&](uint32_t b) {
         std::memcpy(pr[b].ev, pin + L.p_out + (size_t)b * PB_JOBS * 32, sizeof pr[b].ev);
-        for (int e = 0; e < N_EVALS; ++e) pr[b].tr.append_scalar("fourth_round", pr[b].ev[e]);
-        pr[b].ch[C_NU] = pr[b].tr.challenge("nu");
+        pr[b].tr.fourth_round(pr[b].ev[0].l);
         HFr c0;
-        round5_scalars(k, pr[b].ch, pr[b].ev, &slot(b, PB_LIN), &c0);
+        round5_scalars(k, pr[b].tr.ch, pr[b].ev, &slot(b, PB_LIN), &c0);
         slot(b, PB_C0) = c0;
     });
     // ---- round 5: the linearisation and the two opening quotients
     ZK_TRY(upload_par());
     {
         PlonkLinBatchArg lin = {};
-        const uint64_t* ptr[PLONK_LIN_TERMS] = {k.col_coeff(0), k.col_coeff(1), k.col_coeff(2), k.col_coeff(3), k.col_coeff(4), w.Z, k.col_coeff(7),
-                                                w.TL, w.TM, w.TH, w.A, w.B, w.C, k.col_coeff(5), k.col_coeff(6)};
-        for (int j = 0; j < PLONK_LIN_TERMS; ++j) lin.p[j] = ptr[j];
-        lin.own = (1u << 5) | (0x3fu << 7);                    // z, the three parts of t, the three wires
+        for (int j = 0; j < PLONK_LIN_TERMS; ++j) lin.p[j] = poly_at(k, w, LIN_TERMS[j]);
+        lin.own = own_mask(LIN_TERMS);                         // z, the three parts of t, the three wires
         {
             ProfScope ps(c, "plonk_batch_linearise", 32.0 * 16.0 * (double)n * bc);
             hipLaunchKernelGGL(plonk_batch_linearise_kernel, dim3(mle_grid_stream(n + 6), bc), dim3(MLE_BLOCK), 0, c->stream, lin, n + 6, par, w.W, ws);
         }
-        HornerBatchArg h = {};
-        h.coeffs[0] = w.W; h.len[0] = (uint32_t)(n + 6); h.zslot[0] = PB_ZETA; h.quotient[0] = w.Q1;
-        h.coeffs[1] = w.Z; h.len[1] = (uint32_t)(n + 3); h.zslot[1] = PB_ZETA_W; h.quotient[1] = w.Q2;
-        h.own = 3u;
-        h.vstride = (uint32_t)L.hb;
-        const uint32_t nb = (uint32_t)((n + 6 + per_block - 1) / per_block);
+        uint32_t nb;
+        const HornerBatchArg h = horner_arg(DIVIDE_JOBS, &nb);
         {
             ProfScope ps(c, "plonk_batch_divide", 96.0 * 2.0 * (double)n * bc);
             hipLaunchKernelGGL(horner_batch_scan_kernel<false>, dim3(nb, 2, bc), dim3(HS_T), 0, c->stream, h, par, hv, (const uint64_t*)nullptr, (uint64_t*)nullptr, ws);
@@ -833,13 +795,10 @@ int BatchRun::rounds(const uint64_t* const* h_cols, bool* pre_ready) {
         }
         ZK_HIP(c, hipGetLastError());
         ZK_TRY(copy_flags());
-        uint64_t* polys[2] = {w.Q1, w.Q2};
-        const size_t lens[2] = {n + 5, n + 2};
-        ZK_TRY(commit(polys, lens, 2, P_WZ));
+        ZK_TRY(commit(COMMIT_OPENINGS));
     }
     each([&](uint32_t b) {
-        for (int p = P_WZ; p <= P_WZW; ++p) pr[b].tr.append_point("fifth_round", point(b, p), is_inf(b, p));
-        pr[b].ch[C_MU] = pr[b].tr.challenge("mu");
+        pr[b].tr.fifth_round(points(b), flags(b));
     });
     return ZKHIP_OK;
 }
@@ -904,7 +863,7 @@ extern "C" int zkhip_plonk_prove_batch(zkhip_plonk_key* key, uint32_t batch, con
                 refused[b] = run.pr[b].refused;
                 if (refused[b]) continue;
                 std::memcpy(evals + 4 * (size_t)N_EVALS * b, run.pr[b].ev, 32 * N_EVALS);
-                if (chal) std::memcpy(chal + 4 * (size_t)N_CHALLENGES * b, run.pr[b].ch, 32 * N_CHALLENGES);
+                if (chal) std::memcpy(chal + 4 * (size_t)N_CHALLENGES * b, run.pr[b].tr.ch, 32 * N_CHALLENGES);
             }
         }
         for (uint32_t b = 0; b < bc; ++b) {

@@ -5,8 +5,12 @@
 // the address a buffer has in proof 0's area and the proof index -- the grid's LAST used dimension -- moves it by b * ws.  What differs
 // from proof to proof and is a kernel argument in the single prover -- beta, gamma, alpha, alpha^2, the eleven blinding scalars, zeta,
 // w zeta, the fifteen linearisation weights and c0 -- is a row of PB_SLOTS field elements per proof in device memory (`par`), uploaded
-// once per round; the flags are PLONK_FLAGS ints per proof, `fs` INTS apart.  The bodies are those of the single kernels, written
-// beside them and not shared with them: the single prover's kernels compile to what they did (profiles/plonk_batch/NOTES.md).
+// once per round; the flags are PLONK_FLAGS ints per proof, `fs` INTS apart.
+//
+// No field arithmetic is written here.  Every kernel but the gather is a wrapper: it moves the pointers to its proof's area, reads the
+// proof's scalars from `par` and calls the `.._body` that the single prover's kernel of the same pass calls (plonk_kernels.hpp,
+// mle_kernels.hpp), so a formula exists once.  The bodies index rows by blockIdx.x alone, which is why the proof (and the job, and the
+// coset row) sit on the grid's other dimensions.
 // No workgroup waits on another; a launch's size depends on the proofs of a chunk, the number of launches does not.
 #pragma once
 #include "plonk_kernels.hpp"
@@ -37,10 +41,7 @@ struct PlonkBlindBatchArg { uint64_t* p[3]; uint8_t slot[3][3]; };
 static __global__ __launch_bounds__(64) void plonk_batch_blind_kernel(PlonkBlindBatchArg a, size_t n, uint32_t k, const uint64_t* __restrict__ par, size_t ws) {
     const uint32_t j = threadIdx.x, q = blockIdx.x, b = blockIdx.y;
     if (j >= k) return;
-    uint64_t* __restrict__ p = a.p[q] + 4 * (size_t)b * ws;
-    const Fr bj = pb_par(par, b, PB_BLIND + a.slot[q][j]);
-    store_fr(p, j, load_fr(p, j) - bj);
-    store_fr(p, n + j, bj);
+    plonk_blind_body(a.p[q] + 4 * (size_t)b * ws, n, j, pb_par(par, b, PB_BLIND + a.slot[q][j]));
 }
 
 // ---- grand product: plonk_gp_ratio / _top / _apply with the proof as grid.y ---------------------------------------------------------
@@ -49,126 +50,24 @@ static __global__ __launch_bounds__(GP_T) void plonk_batch_gp_ratio_kernel(const
                                                                          PlonkCols cols, const uint64_t* __restrict__ omega_pow, size_t n,
                                                                          const uint64_t* __restrict__ par, uint64_t* __restrict__ f_out,
                                                                          uint64_t* __restrict__ block_prod, int* __restrict__ flags, size_t ws, size_t fs) {
-    __shared__ Fr pre[GP_T], suf[GP_T];
-    __shared__ Fr inv_total;
     const uint32_t pb = blockIdx.y;
     const size_t shift = 4 * (size_t)pb * ws;
-    wa += shift; wb += shift; wc += shift; pub += shift; f_out += shift; block_prod += shift; flags += (size_t)pb * fs;
-    const Fr beta = pb_par(par, pb, PB_BETA), gamma = pb_par(par, pb, PB_GAMMA);
-    const uint32_t t = threadIdx.x;
-    const size_t base = ((size_t)blockIdx.x * GP_T + t) * GP_E;
-    Fr num[GP_E], den[GP_E];
-#pragma unroll
-    for (int j = 0; j < GP_E; ++j) {
-        const size_t i = base + j;
-        num[j] = Fr::one(); den[j] = Fr::one();
-        if (i >= n) continue;
-        const Fr a = load_fr(wa, i), b = load_fr(wb, i), c = load_fr(wc, i);
-        const Fr gate = a * b * load_fr(cols.q[0], i) + a * load_fr(cols.q[1], i) + b * load_fr(cols.q[2], i) + c * load_fr(cols.q[3], i) +
-                        load_fr(pub, i) + load_fr(cols.q[4], i);
-        if (!gate.is_zero()) flags[PLONK_FLAG_GATE] = 1;
-        const Fr bw = beta * load_fr(omega_pow, i);
-        const Fr ag = a + gamma, bg = b + gamma, cg = c + gamma;
-        num[j] = (ag + bw) * (bg + bw + bw) * (cg + bw + bw + bw);
-        Fr d = (ag + beta * load_fr(cols.q[5], i)) * (bg + beta * load_fr(cols.q[6], i)) * (cg + beta * load_fr(cols.q[7], i));
-        if (d.is_zero()) { flags[PLONK_FLAG_DENOM] = 1; d = Fr::one(); }
-        den[j] = d;
-    }
-    Fr part[GP_E];
-    Fr p = Fr::one();
-#pragma unroll
-    for (int j = 0; j < GP_E; ++j) { part[j] = p; p = p * den[j]; }
-    gp_scan_both(p, pre, suf);
-    if (t == 0) inv_total = fr_inverse(pre[GP_T - 1]);
-    __syncthreads();
-    Fr run = inv_total;
-    if (t > 0) run = run * pre[t - 1];
-    if (t + 1 < (uint32_t)GP_T) run = run * suf[t + 1];
-    Fr f[GP_E];
-#pragma unroll
-    for (int j = GP_E - 1; j >= 0; --j) {
-        f[j] = num[j] * (run * part[j]);
-        run = run * den[j];
-    }
-    Fr q = Fr::one();
-#pragma unroll
-    for (int j = 0; j < GP_E; ++j) {
-        if (base + j < n) store_fr(f_out, base + j, f[j]);
-        q = q * f[j];
-    }
-    __syncthreads();
-    pre[t] = q;
-    __syncthreads();
-    for (uint32_t d = GP_T / 2; d >= 1; d >>= 1) {
-        if (t < d) pre[t] = pre[t] * pre[t + d];
-        __syncthreads();
-    }
-    if (t == 0) store_fr(block_prod, blockIdx.x, pre[0]);
+    plonk_gp_ratio_body(wa + shift, wb + shift, wc + shift, pub + shift, cols, omega_pow, n, pb_par(par, pb, PB_BETA), pb_par(par, pb, PB_GAMMA),
+                        f_out + shift, block_prod + shift, flags + (size_t)pb * fs);
 }
 
 // grid (proofs)
 static __global__ __launch_bounds__(1024) void plonk_batch_gp_top_kernel(const uint64_t* __restrict__ block_prod, uint32_t n_blocks,
                                                                         uint64_t* __restrict__ block_excl, size_t ws) {
-    __shared__ Fr lds[1024];
-    block_prod += 4 * (size_t)blockIdx.x * ws; block_excl += 4 * (size_t)blockIdx.x * ws;
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (n_blocks + 1023) / 1024;
-    const uint32_t lo = min(t * per, n_blocks), hi = min(lo + per, n_blocks);
-    Fr g = Fr::one();
-    for (uint32_t b = lo; b < hi; ++b) g = g * load_fr(block_prod, b);
-    Fr p = g;
-    lds[t] = p;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        Fr v = Fr::one();
-        if (t >= d) v = lds[t - d];
-        __syncthreads();
-        p = p * v;
-        lds[t] = p;
-        __syncthreads();
-    }
-    Fr y = t ? lds[t - 1] : Fr::one();
-    for (uint32_t b = lo; b < hi; ++b) {
-        store_fr(block_excl, b, y);
-        y = y * load_fr(block_prod, b);
-    }
+    const size_t shift = 4 * (size_t)blockIdx.x * ws;
+    plonk_gp_top_body(block_prod + shift, n_blocks, block_excl + shift);
 }
 
 // grid (workgroups of a proof, proofs)
 static __global__ __launch_bounds__(GP_T) void plonk_batch_gp_apply_kernel(const uint64_t* __restrict__ f_in, const uint64_t* __restrict__ block_excl,
                                                                          size_t n, uint64_t* __restrict__ acc, int* __restrict__ flags, size_t ws, size_t fs) {
-    __shared__ Fr pre[GP_T];
     const size_t shift = 4 * (size_t)blockIdx.y * ws;
-    f_in += shift; block_excl += shift; acc += shift; flags += (size_t)blockIdx.y * fs;
-    const uint32_t t = threadIdx.x;
-    const size_t base = ((size_t)blockIdx.x * GP_T + t) * GP_E;
-    Fr f[GP_E];
-    Fr q = Fr::one();
-#pragma unroll
-    for (int j = 0; j < GP_E; ++j) {
-        f[j] = base + j < n ? load_fr(f_in, base + j) : Fr::one();
-        q = q * f[j];
-    }
-    Fr p = q;
-    pre[t] = p;
-    __syncthreads();
-    for (uint32_t d = 1; d < (uint32_t)GP_T; d <<= 1) {
-        Fr v = Fr::one();
-        if (t >= d) v = pre[t - d];
-        __syncthreads();
-        p = p * v;
-        pre[t] = p;
-        __syncthreads();
-    }
-    Fr y = load_fr(block_excl, blockIdx.x);
-    if (t) y = y * pre[t - 1];
-#pragma unroll
-    for (int j = 0; j < GP_E; ++j) {
-        const size_t i = base + j;
-        if (i < n) store_fr(acc, i, y);
-        y = y * f[j];
-        if (i == n - 1 && !(y == Fr::one())) flags[PLONK_FLAG_CLOSE] = 1;
-    }
+    plonk_gp_apply_body(f_in + shift, block_excl + shift, n, acc + shift, flags + (size_t)blockIdx.y * fs);
 }
 
 // ---- quotient -----------------------------------------------------------------------------------------------------------------------
@@ -179,12 +78,7 @@ struct PlonkPadBatchArg { const uint64_t* src[PB_COSET_ROWS]; uint32_t len[PB_CO
 static __global__ __launch_bounds__(MLE_BLOCK) void plonk_batch_scale_pad_kernel(PlonkPadBatchArg a, const uint64_t* __restrict__ mul, size_t D,
                                                                                uint64_t* __restrict__ dst, size_t ws) {
     const uint32_t j = blockIdx.y, b = blockIdx.z;
-    const uint64_t* __restrict__ src = a.src[j] + 4 * (size_t)b * ws;
-    uint64_t* __restrict__ out = dst + 4 * ((size_t)b * ws + (size_t)j * D);
-    const size_t n_src = a.len[j];
-    const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t i = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; i < D; i += stride)
-        store_fr(out, i, i < n_src ? load_fr(src, i) * load_fr(mul, i) : Fr::zero());
+    plonk_scale_pad_body(a.src[j] + 4 * (size_t)b * ws, mul, a.len[j], D, dst + 4 * ((size_t)b * ws + (size_t)j * D));
 }
 
 // plonk_quotient_kernel; the ten coset columns `pre` are the key's, the same for every proof.  grid (x, proofs)
@@ -193,22 +87,9 @@ static __global__ __launch_bounds__(MLE_BLOCK) void plonk_batch_quotient_kernel(
                                                                               PlonkQuotBatchArg k, const uint64_t* __restrict__ par,
                                                                               uint64_t* __restrict__ t_out, size_t ws) {
     const uint32_t pb = blockIdx.y;
-    ev += 4 * (size_t)pb * ws; t_out += 4 * (size_t)pb * ws;
-    const Fr beta = pb_par(par, pb, PB_BETA), gamma = pb_par(par, pb, PB_GAMMA), alpha = pb_par(par, pb, PB_ALPHA), alpha2 = pb_par(par, pb, PB_ALPHA2);
-    const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t j = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; j < D; j += stride) {
-        const Fr a = load_fr(ev, j), b = load_fr(ev + 4 * D, j), c = load_fr(ev + 8 * D, j);
-        const Fr z = load_fr(ev + 12 * D, j), zw = load_fr(ev + 12 * D, (j + k.rot) & (D - 1));
-        Fr gate = a * b * load_fr(pre, j) + a * load_fr(pre + 4 * D, j) + b * load_fr(pre + 8 * D, j) + c * load_fr(pre + 12 * D, j) +
-                  load_fr(ev + 16 * D, j) + load_fr(pre + 16 * D, j);
-        const Fr ag = a + gamma, bg = b + gamma, cg = c + gamma;
-        const Fr bx = beta * load_fr(pre + 36 * D, j);
-        const Fr p1 = (ag + bx) * (bg + bx + bx) * (cg + bx + bx + bx) * z;
-        const Fr p2 = (ag + beta * load_fr(pre + 20 * D, j)) * (bg + beta * load_fr(pre + 24 * D, j)) * (cg + beta * load_fr(pre + 28 * D, j)) * zw;
-        const Fr l = (z - Fr::one()) * load_fr(pre + 32 * D, j);
-        const Fr num = gate + alpha * (p1 - p2) + alpha2 * l;
-        store_fr(t_out, j, num * fr_from_arg(k.zh_inv[j & (k.rot - 1)]));
-    }
+    const size_t shift = 4 * (size_t)pb * ws;
+    plonk_quotient_body(ev + shift, pre, D, pb_par(par, pb, PB_BETA), pb_par(par, pb, PB_GAMMA), pb_par(par, pb, PB_ALPHA), pb_par(par, pb, PB_ALPHA2),
+                        k.zh_inv, k.rot, t_out + shift);
 }
 
 // plonk_split_kernel.  grid (x, proofs)
@@ -218,43 +99,28 @@ static __global__ __launch_bounds__(MLE_BLOCK) void plonk_batch_split_kernel(con
                                                                            size_t ws, size_t fs) {
     const uint32_t pb = blockIdx.y;
     const size_t shift = 4 * (size_t)pb * ws;
-    t += shift; tl += shift; tm += shift; th += shift; flags += (size_t)pb * fs;
-    const Fr b10 = pb_par(par, pb, PB_BLIND + 9), b11 = pb_par(par, pb, PB_BLIND + 10);
-    const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t i = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; i < D; i += stride) {
-        Fr v = load_fr(t, i);
-        if (i >= 3 * n + 6) {
-            if (!v.is_zero()) flags[PLONK_FLAG_QUOTIENT] = 1;
-            continue;
-        }
-        v = v * load_fr(ginv_pow, i);
-        if (i < n) {
-            store_fr(tl, i, v);
-            if (i == 0) { store_fr(tl, n, b10); store_fr(tm, n, b11); }
-        } else if (i < 2 * n) {
-            store_fr(tm, i - n, i == n ? v - b10 : v);
-        } else {
-            store_fr(th, i - 2 * n, i == 2 * n ? v - b11 : v);
-        }
-    }
+    plonk_split_body(t + shift, ginv_pow, n, D, pb_par(par, pb, PB_BLIND + 9), pb_par(par, pb, PB_BLIND + 10), tl + shift, tm + shift, th + shift,
+                     flags + (size_t)pb * fs);
 }
 
 // ---- linearisation ------------------------------------------------------------------------------------------------------------------
 // plonk_linearise_kernel: term q reads p[q], moved by the proof's offset when bit q of `own` is set (the proof's own polynomials; the
 // others are the key's), with the weight par[PB_LIN + q]; c0 = par[PB_C0].  grid (x, proofs)
 struct PlonkLinBatchArg { const uint64_t* p[PLONK_LIN_TERMS]; uint32_t own; };
+struct PlonkLinBatchSrc {
+    const PlonkLinBatchArg& k;
+    const uint64_t* __restrict__ par;
+    uint32_t pb;
+    size_t shift;
+    __device__ __forceinline__ Fr c0() const { return pb_par(par, pb, PB_C0); }
+    __device__ __forceinline__ Fr weight(int q) const { return pb_par(par, pb, PB_LIN + q); }
+    __device__ __forceinline__ const uint64_t* poly(int q) const { return k.p[q] + (((k.own >> q) & 1u) ? shift : 0); }
+};
 static __global__ __launch_bounds__(MLE_BLOCK) void plonk_batch_linearise_kernel(PlonkLinBatchArg k, size_t len, const uint64_t* __restrict__ par,
                                                                                uint64_t* __restrict__ out, size_t ws) {
     const uint32_t pb = blockIdx.y;
     const size_t shift = 4 * (size_t)pb * ws;
-    out += shift;
-    const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t i = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; i < len; i += stride) {
-        Fr acc = i == 0 ? pb_par(par, pb, PB_C0) : Fr::zero();
-#pragma unroll
-        for (int q = 0; q < PLONK_LIN_TERMS; ++q) acc = acc + pb_par(par, pb, PB_LIN + q) * load_fr(k.p[q] + (((k.own >> q) & 1u) ? shift : 0), i);
-        store_fr(out, i, acc);
-    }
+    plonk_linearise_body(PlonkLinBatchSrc{k, par, pb, shift}, len, out + shift);
 }
 
 // ---- Horner: evaluations and divisions by a linear factor --------------------------------------------------------------------------
@@ -274,91 +140,21 @@ struct HornerBatchArg {
 template <bool APPLY>
 static __global__ __launch_bounds__(HS_T) void horner_batch_scan_kernel(HornerBatchArg a, const uint64_t* __restrict__ par, uint64_t* __restrict__ vals,
                                                                       const uint64_t* __restrict__ carries, uint64_t* __restrict__ evals, size_t ws) {
-    __shared__ Fr a_lds[HS_T];
     const uint32_t job = blockIdx.y, pb = blockIdx.z;
     const size_t n = a.len[job];
     if ((size_t)blockIdx.x * HS_T * HS_L >= n) return;                  // the whole workgroup: nobody is left at a barrier
     const size_t shift = 4 * (size_t)pb * ws;
-    const uint64_t* __restrict__ coeffs = a.coeffs[job] + (((a.own >> job) & 1u) ? shift : 0);
-    const size_t v_at = (size_t)pb * ws + (size_t)job * a.vstride + blockIdx.x;
-    const Fr z = pb_par(par, pb, a.zslot[job]);
-    const uint32_t t = threadIdx.x;
-    const size_t s = ((size_t)blockIdx.x * HS_T + t) * HS_L;
-    Fr c[HS_L];
-#pragma unroll
-    for (int j = 0; j < HS_L; ++j) c[j] = (s + j < n) ? load_fr(coeffs, s + j) : Fr::zero();
-    Fr h = c[HS_L - 1];
-#pragma unroll
-    for (int j = HS_L - 2; j >= 0; --j) h = c[j] + z * h;
-    Fr rp = z;
-#pragma unroll
-    for (int q = 1; q < HS_L; q <<= 1) rp = rp * rp;
-    Fr carry_in = Fr::zero();
-    if (APPLY) {
-        carry_in = load_fr(carries, v_at);
-        if (t == HS_T - 1) h = h + rp * carry_in;
-    }
-    a_lds[t] = h;
-    __syncthreads();
-    for (uint32_t d = 1; d < (uint32_t)HS_T; d <<= 1) {
-        Fr v = Fr::zero();
-        const bool has = t + d < (uint32_t)HS_T;
-        if (has) v = a_lds[t + d];
-        __syncthreads();
-        if (has) { h = h + rp * v; a_lds[t] = h; }
-        __syncthreads();
-        rp = rp * rp;
-    }
-    if (!APPLY) {
-        if (t == 0) store_fr(vals, v_at, h);
-        return;
-    }
-    uint64_t* __restrict__ quotient = a.quotient[job] + shift;
-    Fr v = (t == HS_T - 1) ? carry_in : a_lds[t + 1];
-#pragma unroll
-    for (int j = HS_L - 1; j >= 0; --j) {
-        v = c[j] + z * v;
-        const size_t i = s + j;
-        if (i == 0) store_fr(evals, (size_t)pb * ws + job, v);
-        else if (i < n) store_fr(quotient, i - 1, v);
-    }
+    const size_t v_at = 4 * ((size_t)pb * ws + (size_t)job * a.vstride);   // the job's row of workgroup values and of carries
+    horner_scan_body<APPLY>(a.coeffs[job] + (((a.own >> job) & 1u) ? shift : 0), n, pb_par(par, pb, a.zslot[job]), APPLY ? nullptr : vals + v_at,
+                            APPLY ? carries + v_at : nullptr, APPLY ? a.quotient[job] + shift : nullptr, APPLY ? evals + shift + 4 * job : nullptr);
 }
 // grid (jobs, proofs); evals == nullptr: the carries alone
 static __global__ __launch_bounds__(1024) void horner_batch_top_kernel(HornerBatchArg a, const uint64_t* __restrict__ par, const uint64_t* __restrict__ vals,
                                                                      uint64_t* __restrict__ carries, uint64_t* __restrict__ evals, size_t ws) {
-    __shared__ Fr a_lds[1024];
     const uint32_t job = blockIdx.x, pb = blockIdx.y;
     const uint32_t n_blocks = (uint32_t)(((size_t)a.len[job] + (size_t)HS_T * HS_L - 1) / ((size_t)HS_T * HS_L));
-    const size_t v_at = (size_t)pb * ws + (size_t)job * a.vstride;
-    const uint64_t* __restrict__ block_vals = vals + 4 * v_at;
-    uint64_t* __restrict__ out = carries + 4 * v_at;
-    const uint32_t t = threadIdx.x;
-    Fr R = pb_par(par, pb, a.zslot[job]);
-    for (int q = 1; q < HS_T * HS_L; q <<= 1) R = R * R;
-    const uint32_t per = (n_blocks + 1023) / 1024;
-    const uint32_t lo = min(t * per, n_blocks), hi = min(lo + per, n_blocks);
-    Fr g = Fr::zero();
-    for (uint32_t b = hi; b-- > lo;) g = load_fr(block_vals, b) + R * g;
-    Fr rp = Fr::one();
-    for (uint32_t q = 0; q < per; ++q) rp = rp * R;
-    a_lds[t] = g;
-    __syncthreads();
-    Fr h = g;
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        Fr v = Fr::zero();
-        const bool has = t + d < 1024;
-        if (has) v = a_lds[t + d];
-        __syncthreads();
-        if (has) { h = h + rp * v; a_lds[t] = h; }
-        __syncthreads();
-        rp = rp * rp;
-    }
-    Fr y = (t == 1023) ? Fr::zero() : a_lds[t + 1];
-    for (uint32_t b = hi; b-- > lo;) {
-        store_fr(out, b, y);
-        y = load_fr(block_vals, b) + R * y;
-    }
-    if (t == 0 && evals) store_fr(evals, (size_t)pb * ws + job, y);
+    const size_t v_at = 4 * ((size_t)pb * ws + (size_t)job * a.vstride);
+    horner_top_body(vals + v_at, n_blocks, pb_par(par, pb, a.zslot[job]), carries + v_at, evals ? evals + 4 * ((size_t)pb * ws + job) : nullptr);
 }
 
 }  // namespace zk
