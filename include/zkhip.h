@@ -38,8 +38,8 @@
  *     zkhip_circuit_add_mult_mle without gates, which clears its two tables.)
  *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
  *     zkhip_circuit_add_mult_mle, zkhip_gkr_prove, zkhip_gkr_prove_circuit, zkhip_gkr_prove_sharded, zkhip_sumcheck_prove,
- *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_mc_begin,
- *     zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
+ *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_multi_composed_prove_batch,
+ *     zkhip_mc_begin, zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
  *     zkhip_srs_univariate_g1, zkhip_srs_multilinear_g2, zkhip_srs_univariate_g2, zkhip_srs_fold_levels, zkhip_srs_level_tables,
  *     zkhip_kzg_open, zkhip_kzg_open_tables, zkhip_kzg_open_batch, zkhip_univariate_kzg_open, zkhip_g2_prepare, zkhip_kzg_prepare,
  *     zkhip_pairing, zkhip_pairing_prepared, zkhip_kzg_verify_batch, zkhip_univariate_kzg_verify_batch, zkhip_ntt, zkhip_domain_transform,
@@ -408,6 +408,30 @@ int zkhip_multi_composed_sum(zkhip_ctx *ctx, const uint64_t *const *h_table_ptrs
 int zkhip_multi_composed_prove(zkhip_ctx *ctx, const uint64_t *const *h_table_ptrs, const uint32_t *h_term_sizes,
                                uint32_t n_terms, size_t n, const uint64_t *h_sum, int partial,
                                uint32_t *h_round_poly_lens, uint64_t *h_round_polys, uint64_t *h_challenges);
+/* MultiComposedSumcheckProver::prove / ::prove_partial of `batch` claims of one term shape and n entries per table in one call:
+ * h_table_ptrs[batch][T] device pointers (T = sum of h_term_sizes), term after term as zkhip_multi_composed_prove takes them (a
+ * pointer may repeat, across proofs and within one; the tables are only read); h_sums[batch][4] the claimed sums.  Outputs proof
+ * after proof in the layouts of zkhip_multi_composed_prove: h_round_poly_lens[batch][n_vars], h_round_polys[batch][n_vars][7][2][4],
+ * h_challenges[batch][n_vars][4]; proof b is bit for bit what zkhip_multi_composed_prove returns for its tables, its sum and
+ * `partial` (the monomials of a round up to its length; the batch kernel leaves zeros behind them).  Checks and status codes as
+ * zkhip_multi_composed_prove, plus a null among the batch * T pointers (ZKHIP_ERR_ARG), applied once and before anything is launched,
+ * reserved or written; batch == 0 is ZKHIP_OK and touches nothing, and so is n == 1 (no rounds).  T * n <= 2^16 entries run on
+ * the batch kernel from zkhip_multi_composed_batch_min proofs on, one workgroup per proof with its own transcript -- the context's
+ * composed transcript is not written, so a continuation or session before or after does not notice the call --, chunked as
+ * zkhip_sumcheck_prove_batch (resident from the first round up to T * n = 2^12, a slab of T * n / 2 entries per proof above);
+ * everything else runs zkhip_multi_composed_prove per proof.  partial = 0: every proof's transcript first absorbs the bytes of its
+ * own tables; the chunk's tables are converted in one launch and copied out, the host hashes each proof's stream (as the single
+ * prover does) and uploads the states, and the T * n * 32 staging bytes per proof count against the chunk's scratch.  That path is
+ * bounded by the host's SHA-256 rate, not by the kernel.  (A chunk is never fewer than 256 proofs, so at the largest claims the
+ * 256 MiB budget is exceeded: at T * n = 2^16, partial = 0, a chunk of 256 reserves 256 x (1 MiB slab + 2 MiB bytes) = 768 MiB of
+ * the workspace and 512 MiB of pinned memory, as long as the batch has that many proofs; partial = 1 stays within 256 MiB.) */
+int zkhip_multi_composed_prove_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_table_ptrs,
+                                     const uint32_t *h_term_sizes, uint32_t n_terms, size_t n, const uint64_t *h_sums, int partial,
+                                     uint32_t *h_round_poly_lens, uint64_t *h_round_polys, uint64_t *h_challenges);
+/* The fewest proofs from which on zkhip_multi_composed_prove_batch runs a claim shape on the batch kernel (measured: the batch is
+ * faster per proof than a loop of zkhip_multi_composed_prove from there on), or 0 when the kernel never serves the shape (a shape
+ * the prover refuses, n < 2, more than 2^16 entries). */
+int zkhip_multi_composed_batch_min(const uint32_t *h_term_sizes, uint32_t n_terms, size_t n);
 
 /* The same provers over tables SHARDED across `world` ranks (rank g holds entry j*world + g of every table at
  * local index j; the rounds fold the most significant variable, so folds are local).  ComposedSumcheck::prove (multi = 0,

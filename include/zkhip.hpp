@@ -393,6 +393,10 @@ class MultiComposedSumcheckProver {
     }
     static std::pair<MultiComposedSumcheckProof, std::vector<Fr>> prove(const std::vector<ComposedMultilinear>& poly, const Fr& sum) { return run(poly, sum, 0); }          // :47-54
     static std::pair<MultiComposedSumcheckProof, std::vector<Fr>> prove_partial(const std::vector<ComposedMultilinear>& poly, const Fr& sum) { return run(poly, sum, 1); }  // :56-62
+    // the proofs of claims of one term shape and one length in one call (zkhip_multi_composed_prove_batch), each as from prove() / prove_partial()
+    using Proved = std::pair<MultiComposedSumcheckProof, std::vector<Fr>>;
+    static std::vector<Proved> prove_batch(const std::vector<std::vector<ComposedMultilinear>>& polys, const std::vector<Fr>& sums) { return run_batch(polys, sums, 0); }
+    static std::vector<Proved> prove_partial_batch(const std::vector<std::vector<ComposedMultilinear>>& polys, const std::vector<Fr>& sums) { return run_batch(polys, sums, 1); }
     // prove_partial over rank-interleaved shards of every table (sum = the claimed sum of the WHOLE tables); the proof of the whole claim on every rank
     static std::pair<MultiComposedSumcheckProof, std::vector<Fr>> prove_partial_sharded(const std::vector<ComposedMultilinear>& shards, const Fr& sum, const Comm& comm,
                                                                                          int use_stages = -1, uint32_t* exchanges = nullptr) {
@@ -437,6 +441,33 @@ class MultiComposedSumcheckProver {
         check(zkhip_multi_composed_prove(ctx(), ptrs.data(), sizes.data(), (uint32_t)sizes.size(), poly[0].polys[0].len(), sum.l, partial, lens.data(), rp.data(), ch[0].l),
               "multi_composed_prove");
         return unpack(sum, nv, lens, rp, ch);
+    }
+    static std::vector<Proved> run_batch(const std::vector<std::vector<ComposedMultilinear>>& polys, const std::vector<Fr>& sums, int partial) {
+        std::vector<Proved> out;
+        if (polys.empty()) return out;
+        if (sums.size() != polys.size()) throw Panic("one claimed sum per claim");
+        if (polys.size() == 1) { out.push_back(run(polys[0], sums[0], partial)); return out; }
+        std::vector<const uint64_t*> ptrs; std::vector<uint32_t> sizes;
+        flatten(polys[0], ptrs, sizes);
+        const size_t B = polys.size(), nv = polys[0][0].n_vars(), n = polys[0][0].polys[0].len(), m = nv ? nv : 1;
+        for (size_t b = 1; b < B; ++b) {
+            std::vector<uint32_t> sz;
+            flatten(polys[b], ptrs, sz);
+            if (sz != sizes) throw Panic("the claims of a batch share their term sizes");
+        }
+        for (auto& p : polys) for (auto& t : p) for (auto& tab : t.polys) if (tab.len() != n) throw Panic("the tables of a batch share their length");
+        std::vector<uint32_t> lens(m * B);
+        std::vector<uint64_t> rp(7 * 8 * m * B);
+        std::vector<Fr> ch(m * B);
+        check(zkhip_multi_composed_prove_batch(ctx(), (uint32_t)B, ptrs.data(), sizes.data(), (uint32_t)sizes.size(), n, sums[0].l, partial, lens.data(), rp.data(), ch[0].l),
+              "multi_composed_prove_batch");
+        for (size_t b = 0; b < B; ++b) {
+            std::vector<uint32_t> l(lens.begin() + b * nv, lens.begin() + (b + 1) * nv);
+            std::vector<uint64_t> r(rp.begin() + 56 * b * nv, rp.begin() + 56 * (b + 1) * nv);
+            std::vector<Fr> c(ch.begin() + b * nv, ch.begin() + (b + 1) * nv);
+            out.push_back(unpack(sums[b], nv, l, r, c));
+        }
+        return out;
     }
 };
 

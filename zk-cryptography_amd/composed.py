@@ -203,29 +203,69 @@ class MultiComposedSumcheckProver:
         return out
 
     @staticmethod
-    def _prove(poly, sum_, partial):
-        ptrs, sizes = MultiComposedSumcheckProver._flat(poly)
-        nv = poly[0].n_vars()
-        lens = np.zeros(max(nv, 1), dtype=np.uint32)
-        rp = np.zeros((max(nv, 1), MAX_MONO, 2, 4), dtype=np.uint64)
-        ch = np.empty((max(nv, 1), 4), dtype=np.uint64)
-        s = np.ascontiguousarray(sum_, dtype=np.uint64).reshape(4)
-        ctx = N.Context.get(poly[0].polys[0].evaluations.device.index)
-        st = N.lib().zkhip_multi_composed_prove(ctx.handle, _ptr_array(ptrs), (C.c_uint32 * len(sizes))(*sizes),
-                                                C.c_uint32(len(sizes)), C.c_size_t(len(poly[0].polys[0])),
-                                                s.ctypes.data_as(C.c_void_p), C.c_int(1 if partial else 0),
-                                                lens.ctypes.data_as(C.c_void_p), rp.ctypes.data_as(C.c_void_p),
-                                                ch.ctypes.data_as(C.c_void_p))
-        N.check(st, "multi_composed_prove")
-        polys = [SparseUnivariatePolynomial(rp[r, : lens[r], 0].copy(), rp[r, : lens[r], 1].copy()) for r in range(nv)]
-        return MultiComposedSumcheckProof(polys, s.copy()), ch[:nv]
+    def _prove(polys, sums, partial):
+        """The proofs of a list of claims of one term shape, one length and one device -> (lens [B, n_vars], monomials
+        [B, n_vars, MAX_MONO, 2, 4], challenges [B, n_vars, 4], sums [B, 4]).  One claim goes to zkhip_multi_composed_prove, more to
+        zkhip_multi_composed_prove_batch."""
+        flat = [MultiComposedSumcheckProver._flat(p) for p in polys]
+        sizes, first = flat[0][1], polys[0][0].polys[0]
+        nv, n, dev = first.n_vars, len(first), first.evaluations.device
+        for p, (_, sz) in zip(polys, flat):
+            assert sz == sizes, "the claims of a batch share their term sizes"
+            assert all(len(t) == n for term in p for t in term.polys), "the tables of a batch share their length"
+            assert all(t.evaluations.device == dev for term in p for t in term.polys), "the tables of a batch live on one device"
+        B, m = len(polys), max(nv, 1)
+        s = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1, 4)
+        assert len(s) == B, "one claimed sum per claim"
+        lens = np.zeros((B, m), dtype=np.uint32)
+        rp = np.zeros((B, m, MAX_MONO, 2, 4), dtype=np.uint64)
+        ch = np.empty((B, m, 4), dtype=np.uint64)
+        ctx = N.Context.get(dev.index)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        shape = ((C.c_uint32 * len(sizes))(*sizes), C.c_uint32(len(sizes)), C.c_size_t(n))
+        if B == 1:
+            st = N.lib().zkhip_multi_composed_prove(ctx.handle, _ptr_array(flat[0][0]), *shape, vp(s), C.c_int(1 if partial else 0),
+                                                    vp(lens), vp(rp), vp(ch))
+            N.check(st, "multi_composed_prove")
+        else:
+            st = N.lib().zkhip_multi_composed_prove_batch(ctx.handle, C.c_uint32(B), _ptr_array([a for ptrs, _ in flat for a in ptrs]), *shape,
+                                                          vp(s), C.c_int(1 if partial else 0), vp(lens), vp(rp), vp(ch))
+            N.check(st, "multi_composed_prove_batch")
+        return lens[:, :nv], rp[:, :nv], ch[:, :nv], s
+
+    @staticmethod
+    def _prove_one(poly, sum_, partial):
+        lens, rp, ch, s = MultiComposedSumcheckProver._prove([poly], sum_, partial)
+        polys = [SparseUnivariatePolynomial(rp[0, r, : lens[0, r], 0].copy(), rp[0, r, : lens[0, r], 1].copy()) for r in range(lens.shape[1])]
+        return MultiComposedSumcheckProof(polys, s[0].copy()), ch[0]
+
+    @staticmethod
+    def _prove_many(polys, sums, partial):
+        polys = list(polys)
+        if not polys:
+            return []
+        if len(polys) == 1:
+            return [MultiComposedSumcheckProver._prove_one(polys[0], np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1, 4)[0], partial)]
+        lens, rp, ch, s = MultiComposedSumcheckProver._prove(polys, sums, partial)
+        return [(MultiComposedSumcheckProof.from_packed(rp[b], lens[b], s[b].copy()), ch[b]) for b in range(len(polys))]
 
     @staticmethod
     def prove(poly, sum_):
         """multi_composed_sumcheck.rs:47-54 -> Ok((proof, challenges))"""
-        return MultiComposedSumcheckProver._prove(poly, sum_, False)
+        return MultiComposedSumcheckProver._prove_one(poly, sum_, False)
 
     @staticmethod
     def prove_partial(poly, sum_):
         """multi_composed_sumcheck.rs:56-62"""
-        return MultiComposedSumcheckProver._prove(poly, sum_, True)
+        return MultiComposedSumcheckProver._prove_one(poly, sum_, True)
+
+    @staticmethod
+    def prove_batch(polys, sums):
+        """prove() of a list of claims of one term shape and one length in one call (zkhip_multi_composed_prove_batch)
+        -> [(MultiComposedSumcheckProof, challenges)], each as from prove(); sums: one claimed sum per claim, [B, 4]."""
+        return MultiComposedSumcheckProver._prove_many(polys, sums, False)
+
+    @staticmethod
+    def prove_partial_batch(polys, sums):
+        """prove_partial() of a list of claims in one call -> [(MultiComposedSumcheckProof, challenges)]"""
+        return MultiComposedSumcheckProver._prove_many(polys, sums, True)

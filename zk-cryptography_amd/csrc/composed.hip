@@ -16,6 +16,8 @@
 #include "composed_stage.hpp"
 #include "composed_dot.hpp"
 #include "composed_pipe.hpp"
+#include "sumcheck_batch_kernels.hpp"
+#include "multi_composed_batch_kernels.hpp"
 #include "host_fr.hpp"
 #include "tunables.hpp"
 
@@ -107,6 +109,36 @@ extern "C" int zkhip_multi_composed_sum(zkhip_ctx* c, const uint64_t* const* ptr
     return product_sums(c, ptrs, term_sizes, n_terms, n, h_sum);
 }
 
+// a host hasher's state (whole 32-byte items absorbed so far) as the kernels continue it
+static Sha256State device_sha_state(const zkhost::Sha256& sha) {
+    Sha256State hs = {};
+    std::memcpy(hs.h, sha.h, 32);
+    const uint32_t fill = (uint32_t)(sha.len % 64);
+    for (uint32_t i = 0; i < fill / 4; ++i)
+        hs.buf[i] = ((uint32_t)sha.buf[4 * i] << 24) | ((uint32_t)sha.buf[4 * i + 1] << 16) | ((uint32_t)sha.buf[4 * i + 2] << 8) | sha.buf[4 * i + 3];
+    hs.fill = fill;
+    hs.len = sha.len;
+    return hs;
+}
+
+// the context's ComposedDev, made on first use: a zero transcript and the interpolation matrices of every degree
+static int composed_dev_state(zkhip_ctx* c, ComposedDev** st) {
+    if (!c->d_composed) {
+        std::vector<uint64_t> img(sizeof(ComposedDev) / 8, 0);
+        uint64_t* mats = img.data() + offsetof(ComposedDev, interp) / 8;
+        for (int d = 1; d <= CMP_MAX_K; ++d) {
+            std::vector<zkhost::Fr> m = zkhost::interpolation_matrix(d);
+            std::memcpy(&mats[(size_t)d * (CMP_MAX_K + 1) * (CMP_MAX_K + 1) * 4], m.data(), m.size() * 32);
+        }
+        DevMem mem;
+        if (dev_alloc(mem, sizeof(ComposedDev)) != hipSuccess) return ZKHIP_ERR_NOMEM;
+        if (hipMemcpy(mem.get(), img.data(), sizeof(ComposedDev), hipMemcpyHostToDevice) != hipSuccess) return ZKHIP_ERR_HIP;
+        c->d_composed = std::move(mem);
+    }
+    *st = (ComposedDev*)c->d_composed.get();
+    return ZKHIP_OK;
+}
+
 // One composed / multi-composed sumcheck in progress: the state shared by the one-call provers below and by the
 // split-phase session (zkhip_mc_*, tables sharded over several GPUs).  multi = 0: ComposedSumcheck (one term).
 // lin_ptrs (nullable): per term an optional additive table (term = product + table; K <= 2).  cont: continue the
@@ -190,19 +222,7 @@ struct ComposedRun {
         cur_buf = 0;
         // the device-resident state (transcript, interpolation matrices of every degree) belongs to the context: uploaded once,
         // and a continuation (cont) finds the transcript where the previous call's kernels left it -- no copies, no waiting
-        if (!c->d_composed) {
-            std::vector<uint64_t> img(sizeof(ComposedDev) / 8, 0);
-            uint64_t* mats = img.data() + offsetof(ComposedDev, interp) / 8;
-            for (int d = 1; d <= CMP_MAX_K; ++d) {
-                std::vector<zkhost::Fr> m = zkhost::interpolation_matrix(d);
-                std::memcpy(&mats[(size_t)d * (CMP_MAX_K + 1) * (CMP_MAX_K + 1) * 4], m.data(), m.size() * 32);
-            }
-            DevMem mem;
-            if (dev_alloc(mem, sizeof(ComposedDev)) != hipSuccess) return ZKHIP_ERR_NOMEM;
-            if (hipMemcpy(mem.get(), img.data(), sizeof(ComposedDev), hipMemcpyHostToDevice) != hipSuccess) return ZKHIP_ERR_HIP;
-            c->d_composed = std::move(mem);
-        }
-        st = (ComposedDev*)c->d_composed.get();
+        ZK_TRY(composed_dev_state(c, &st));
         d_partials = c->small_u64(ZK_SMALL_PARTIALS);
         d_rp = c->small_u64(ZK_SMALL_ROUNDPOLYS);
         d_ch = c->small_u64(ZK_SMALL_CHALLENGES);
@@ -237,13 +257,7 @@ struct ComposedRun {
                 ZK_HIP(c, hipEventSynchronize(c->msm_ev[k & 1].get()));
                 sha.update((const uint8_t*)c->msm_pin[k & 1].ptr, 32 * chunk_len(k));
             }
-            Sha256State hs = {};
-            std::memcpy(hs.h, sha.h, 32);
-            const uint32_t fill = (uint32_t)(sha.len % 64);
-            for (uint32_t i = 0; i < fill / 4; ++i)
-                hs.buf[i] = ((uint32_t)sha.buf[4 * i] << 24) | ((uint32_t)sha.buf[4 * i + 1] << 16) | ((uint32_t)sha.buf[4 * i + 2] << 8) | sha.buf[4 * i + 3];
-            hs.fill = fill;
-            hs.len = sha.len;
+            const Sha256State hs = device_sha_state(sha);
             ZK_HIP(c, hipMemcpyAsync(&st->transcript, &hs, sizeof(hs), hipMemcpyHostToDevice, c->stream));
             ZK_HIP(c, hipStreamSynchronize(c->stream));   // hs is a stack temporary
             first = 2;
@@ -731,6 +745,152 @@ extern "C" int zkhip_multi_composed_prove(zkhip_ctx* c, const uint64_t* const* p
                                           uint32_t n_terms, size_t n, const uint64_t* h_sum, int partial,
                                           uint32_t* h_lens, uint64_t* h_round_polys, uint64_t* h_challenges) {
     return composed_prove_impl(c, ptrs, term_sizes, n_terms, n, 1, h_sum, partial, h_lens, h_round_polys, h_challenges);
+}
+
+// ---------------------------------------------------------------------------------------
+// a batch of multi-composed proofs in one launch (multi_composed_batch_kernels.hpp)
+// ---------------------------------------------------------------------------------------
+// record length and table count of a term shape, or false where zkhip_multi_composed_prove refuses it
+static bool mcb_shape(const uint32_t* sizes, uint32_t n_terms, uint32_t* rec, uint32_t* total) {
+    if (!sizes || n_terms == 0 || n_terms > CMP_MAX_TERMS) return false;
+    *rec = *total = 0;
+    for (uint32_t p = 0; p < n_terms; ++p) {
+        if (sizes[p] < 1 || sizes[p] > CMP_MAX_K) return false;
+        *rec += sizes[p] + 1;
+        *total += sizes[p];
+    }
+    return *rec <= CMP_MAX_REC;
+}
+// Fewest proofs from which on the batch kernel measured faster per proof than a loop of zkhip_multi_composed_prove
+// (profiles/multi_composed_batch/NOTES.md, "Where the kernel starts to pay"); 0: the kernel never serves the shape.
+// Two proofs pay at every measured shape up to [2, 3] x 2^12 = 20480 entries (1.3 - 2.0 x the loop); at [2, 2] x 2^14 = 2^16 entries
+// two proofs take 1.3 x the loop's time and four 0.66 x.  Nothing between was measured: above 20480 entries the larger bound.
+extern "C" int zkhip_multi_composed_batch_min(const uint32_t* term_sizes, uint32_t n_terms, size_t n) {
+    uint32_t rec, total;
+    if (!mcb_shape(term_sizes, n_terms, &rec, &total) || !is_pow2(n) || n < 2 || (size_t)total * n > MCB_MAX_ENTRIES) return 0;
+    return (size_t)total * n > 20480 ? 4 : 2;
+}
+// Chunk after chunk as zk_sumcheck_batch_run: one upload of the chunk's table pointers and claimed sums, one launch of one workgroup
+// per proof, one copy of all results, one synchronisation.  prove (partial = 0) puts the table bytes' hash in front: one conversion
+// launch over the chunk's tables, one copy, the host hashes proof after proof, one upload of the states.  The caller has checked
+// the arguments.
+static int multi_composed_batch_run(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_ptrs, const uint32_t* sizes, uint32_t n_terms,
+                                    size_t n, const uint64_t* h_sums, int partial, uint32_t* h_lens, uint64_t* h_round_polys,
+                                    uint64_t* h_challenges) {
+    MultiComposedBatchArgs a = {};
+    ComposedMeta& meta = a.ca.meta;
+    meta.n_terms = n_terms;
+    meta.multi = 1;
+    uint32_t total = 0;
+    for (uint32_t p = 0; p < n_terms; ++p) {
+        meta.k[p] = sizes[p];
+        meta.rec_off[p] = meta.rec;
+        meta.lin_tab[p] = ~0u;
+        meta.rec += sizes[p] + 1;
+        total += sizes[p];
+    }
+    const uint32_t n_vars = log2_exact(n);
+    const uint32_t m = (uint32_t)std::min<size_t>(n, composed_tail_len(total));
+    const size_t slab_per = m < n ? (size_t)total * (n / 2) * 32 : 0;
+    const size_t bytes_per = partial ? 0 : (size_t)total * n * 32;
+    const uint32_t bc_max = std::min(batch, scb_chunk(slab_per + bytes_per));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // workspace: [table pointers | claimed sums | states] (uploaded) [challenges | rounds] (read back) [slabs] [table bytes]
+    // pinned 0: [challenges | rounds] [table pointers | claimed sums | states];  pinned 1: [table bytes]
+    const size_t o_sums = al((size_t)bc_max * total * 8), o_init = o_sums + al((size_t)bc_max * 32);
+    const size_t stage_bytes = o_init + (partial ? 0 : al((size_t)bc_max * sizeof(Sha256State)));
+    const size_t ch_bytes = al((size_t)bc_max * n_vars * 32), out_bytes = ch_bytes + al((size_t)bc_max * n_vars * MCB_ROUND_WORDS * 8);
+    const size_t o_slab = stage_bytes + out_bytes, o_bytes = al(o_slab + (size_t)bc_max * slab_per);
+    ZK_TRY(c->reserve_ws(o_bytes + (size_t)bc_max * bytes_per));
+    ZK_TRY(c->reserve_msm_pin(0, out_bytes + stage_bytes));
+    if (!partial) ZK_TRY(c->reserve_msm_pin(1, (size_t)bc_max * bytes_per));
+    ZK_TRY(composed_dev_state(c, &a.ca.st));
+    char* ws = (char*)c->ws.ptr;
+    char* pin = (char*)c->msm_pin[0].ptr;
+    const size_t lds = (size_t)total * m * 32;
+    ZK_TRY(c->allow_big_lds((const void*)multi_composed_batch_kernel, (size_t)CMP_TAIL_ENTRIES * 32));
+    a.ca.first = partial ? 1u : 2u;
+    a.ca.sum_dev = (const uint64_t*)(ws + o_sums);
+    a.ca.challenges = (uint64_t*)(ws + stage_bytes);
+    a.tables = (const uint64_t* const*)ws;
+    a.init = partial ? nullptr : (const Sha256State*)(ws + o_init);
+    a.slab = (uint64_t*)(ws + o_slab);
+    a.total = total; a.n = (uint32_t)n; a.n_vars = n_vars; a.m = m;
+    for (uint32_t b0 = 0; b0 < batch; b0 += bc_max) {
+        const uint32_t bc = std::min(bc_max, batch - b0);
+        const size_t ch_now = al((size_t)bc * n_vars * 32);      // the rounds right behind THIS chunk's challenges: one copy of no more than it wrote
+        a.ca.round_out = (uint64_t*)(ws + stage_bytes + ch_now);
+        // (the previous chunk's upload has ended: every chunk ends in a synchronisation)
+        std::memcpy(pin + out_bytes, h_ptrs + (size_t)b0 * total, (size_t)bc * total * 8);
+        std::memcpy(pin + out_bytes + o_sums, h_sums + 4 * (size_t)b0, (size_t)bc * 32);
+        ZK_HIP(c, hipMemcpyAsync(ws, pin + out_bytes, o_sums + (size_t)bc * 32, hipMemcpyHostToDevice, c->stream));
+        if (!partial) {
+            // transcript.commit(&composed_poly_to_bytes(&poly)) first (multi_composed_sumcheck.rs:51-53), per proof
+            uint8_t* d_bytes = (uint8_t*)(ws + o_bytes);
+            const uint8_t* h_bytes = (const uint8_t*)c->msm_pin[1].ptr;
+            const unsigned gx = (unsigned)std::min<size_t>(64, (n + MLE_BLOCK - 1) / MLE_BLOCK);
+            hipLaunchKernelGGL(to_bytes_tables_kernel, dim3(gx, bc * total), dim3(MLE_BLOCK), 0, c->stream, a.tables, (uint32_t)n, (uint32_t*)d_bytes);
+            ZK_HIP(c, hipGetLastError());
+            ZK_HIP(c, hipMemcpyAsync(c->msm_pin[1].ptr, d_bytes, (size_t)bc * bytes_per, hipMemcpyDeviceToHost, c->stream));
+            ZK_HIP(c, hipStreamSynchronize(c->stream));
+            Sha256State* states = (Sha256State*)(pin + out_bytes + o_init);
+            for (uint32_t p = 0; p < bc; ++p) {
+                zkhost::Sha256 sha;
+                sha.update(h_bytes + (size_t)p * bytes_per, bytes_per);
+                states[p] = device_sha_state(sha);
+            }
+            ZK_HIP(c, hipMemcpyAsync(ws + o_init, states, (size_t)bc * sizeof(Sha256State), hipMemcpyHostToDevice, c->stream));
+        }
+        {
+            ProfScope ps(c, "multi_composed_batch", 32.0 * (double)total * (double)n * bc);
+            hipLaunchKernelGGL(multi_composed_batch_kernel, dim3(bc), dim3(MCB_BLOCK), lds, c->stream, a);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(pin, a.ca.challenges, ch_now + (size_t)bc * n_vars * MCB_ROUND_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        std::memcpy(h_challenges + 4 * (size_t)b0 * n_vars, pin, (size_t)bc * n_vars * 32);
+        const uint64_t* h_rp = (const uint64_t*)(pin + ch_now);
+        for (size_t r = 0; r < (size_t)bc * n_vars; ++r) {       // a round's record -> its length and its monomials; none behind the last
+            const uint64_t* rec = h_rp + MCB_ROUND_WORDS * r;
+            const uint32_t len = (uint32_t)std::min<uint64_t>(rec[0], CMP_MAX_MONO);
+            uint64_t* dst = h_round_polys + ((size_t)b0 * n_vars + r) * CMP_MAX_MONO * 8;
+            h_lens[(size_t)b0 * n_vars + r] = len;
+            std::memcpy(dst, rec + 8, (size_t)len * 64);
+            std::memset(dst + 8 * (size_t)len, 0, (size_t)(CMP_MAX_MONO - len) * 64);
+        }
+    }
+    return ZKHIP_OK;
+}
+
+// MultiComposedSumcheckProver::prove / prove_partial of `batch` claims of one term shape and one length (include/zkhip.h).  What the
+// batch kernel does not serve (fewer proofs than zkhip_multi_composed_batch_min, claims above MCB_MAX_ENTRIES entries) goes through
+// zkhip_multi_composed_prove proof after proof.
+extern "C" int zkhip_multi_composed_prove_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* ptrs, const uint32_t* term_sizes,
+                                                uint32_t n_terms, size_t n, const uint64_t* h_sums, int partial, uint32_t* h_lens,
+                                                uint64_t* h_round_polys, uint64_t* h_challenges) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!ptrs || !term_sizes) return ZKHIP_ERR_ARG;
+    if (n_terms == 0 || n_terms > CMP_MAX_TERMS) return ZKHIP_ERR_ARG;
+    if (!is_pow2(n)) return ZKHIP_ERR_SHAPE;
+    const uint32_t n_vars = log2_exact(n);
+    if (n_vars > ZK_MAX_ROUNDS) return ZKHIP_ERR_SHAPE;
+    if (n_vars == 0) return ZKHIP_OK;   // `for _ in 0..n_vars` never runs
+    if (!h_round_polys || !h_challenges || !h_sums || !h_lens) return ZKHIP_ERR_ARG;
+    uint32_t rec, total;
+    if (!mcb_shape(term_sizes, n_terms, &rec, &total)) return ZKHIP_ERR_ARG;
+    for (size_t q = 0; q < (size_t)batch * total; ++q) if (!ptrs[q]) return ZKHIP_ERR_ARG;
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;      // a commit in flight or a split-phase session holds the workspace
+    ZK_TRY(c->activate());
+    const uint32_t min_batch = (uint32_t)zkhip_multi_composed_batch_min(term_sizes, n_terms, n);
+    if (min_batch == 0 || batch < min_batch) {
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_multi_composed_prove(c, ptrs + (size_t)b * total, term_sizes, n_terms, n, h_sums + 4 * (size_t)b, partial,
+                                              h_lens + (size_t)b * n_vars, h_round_polys + (size_t)b * n_vars * CMP_MAX_MONO * 8,
+                                              h_challenges + 4 * (size_t)b * n_vars));
+        return ZKHIP_OK;
+    }
+    return multi_composed_batch_run(c, batch, ptrs, term_sizes, n_terms, n, h_sums, partial, h_lens, h_round_polys, h_challenges);
 }
 
 

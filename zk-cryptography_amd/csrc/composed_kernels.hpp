@@ -13,6 +13,8 @@
 // first folds the tables at the previous challenge and writes them back (fused, like the basic prover).
 // Algorithmic traffic per round and table: read 32 n + write 16 n bytes (n = entries before the fold).
 #pragma once
+#include <type_traits>
+
 #include "mle_kernels.hpp"
 #include "stamps.hpp"
 #include "wide_acc.hpp"
@@ -214,7 +216,8 @@ struct CloseArgs {
     uint64_t* challenges;
     OuterPub outer;
 };
-__device__ __forceinline__ Fr close_claimed_sum(const CloseArgs& ca) { return ca.sum_dev ? load_fr(ca.sum_dev, 0) : fr_from_arg(ca.sum); }
+// claim: which of the sums at sum_dev (the batch kernel keeps one per proof there, multi_composed_batch_kernels.hpp)
+__device__ __forceinline__ Fr close_claimed_sum(const CloseArgs& ca, uint32_t claim = 0) { return ca.sum_dev ? load_fr(ca.sum_dev, claim) : fr_from_arg(ca.sum); }
 // one whole wave, after the round's items are in sh (canon, pow_of, n_items) and a barrier has made them visible to it.
 // One row = 64 words = one agent-scope store per lane, then the flag behind a release fence at agent scope (the reader may run on
 // another XCD, behind another L2).
@@ -344,10 +347,12 @@ __device__ __forceinline__ void close_preload(CloseShared& sh, const ComposedMet
 // compute the message schedules run it once they are done, i.e. beside the hash (lane < n_lanes = blockDim.x - 64).
 // On return sh.challenge_canon holds the challenge as a CANONICAL integer (what the hash yields) for every thread; its Montgomery
 // form goes to challenges[round] without anyone waiting for the conversion.
+// CTX_STATE = false: the caller's transcript is its own, no pipelined round follows and no outer transcript is fed, so the context's
+// ComposedDev is only read (the batch kernel: a proof per workgroup, `round` counted over the whole batch, `claim` = the proof).
 struct NoShadow { __device__ __forceinline__ void operator()(uint32_t, uint32_t) const {} };
-template <class Shadow = NoShadow>
+template <class Shadow = NoShadow, bool CTX_STATE = true>
 __device__ __forceinline__ void close_round(CloseShared& sh, const CloseArgs& ca, Sha256State* tr_state,
-                                            uint32_t round, uint32_t first, const Shadow& shadow = Shadow()) {
+                                            uint32_t round, uint32_t first, const Shadow& shadow = Shadow(), uint32_t claim = 0) {
     const ComposedMeta& meta = ca.meta;
     ComposedDev* st = ca.st;
     uint64_t* __restrict__ challenges = ca.challenges;
@@ -430,7 +435,7 @@ __device__ __forceinline__ void close_round(CloseShared& sh, const CloseArgs& ca
             if (tid == 0) { sh.n_items = (uint32_t)__popcll(mask); out[0] = (uint64_t)__popcll(mask); }
         }
     }
-    if (meta.multi && first && tid == 64) sh.sum_canon = fr_from_mont_outlined(close_claimed_sum(ca));   // multi_composed_sumcheck.rs:70
+    if (meta.multi && first && tid == 64) sh.sum_canon = fr_from_mont_outlined(close_claimed_sum(ca, claim));   // multi_composed_sumcheck.rs:70
     __syncthreads();
     ZK_STAMP_AT(0, round, 1);
     // ---- the round's message, padded (FiatShamirTranscript: commit ... then challenge = finalize, fiat_shamir.rs:17-25):
@@ -473,7 +478,9 @@ __device__ __forceinline__ void close_round(CloseShared& sh, const CloseArgs& ca
             const uint32_t bb = active ? b : b0;
             sha256_schedule_rows_to_lds(sh.msg[16 * bb + (tid & 15)], sh.kw + 64 * bb, &sh.kw_ready[bb], 0u, bb == 0 ? 1u : 0u, active);
         }
-        if (wave == n_sched - 1) outer_publish(ca.outer, sh, round);      // the last wave: the one with the fewest schedules
+        if constexpr (CTX_STATE) {
+            if (wave == n_sched - 1) outer_publish(ca.outer, sh, round);  // the last wave: the one with the fewest schedules
+        }
         shadow(tid - 64, blockDim.x - 64);
     } else {
         uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
@@ -497,8 +504,10 @@ __device__ __forceinline__ void close_round(CloseShared& sh, const CloseArgs& ca
             tr.commit_words8(h);
             tr.store(tr_state);
             sh.challenge_canon = c;
+            if constexpr (CTX_STATE) {
 #pragma unroll
-            for (int i = 0; i < Fr::N; ++i) reinterpret_cast<uint32_t*>(st->last_canon[round & 1])[i] = c.l[i];
+                for (int i = 0; i < Fr::N; ++i) reinterpret_cast<uint32_t*>(st->last_canon[round & 1])[i] = c.l[i];
+            }
         }
     }
     __syncthreads();
@@ -975,19 +984,35 @@ inline uint32_t composed_tail_len(uint32_t total_tables) {   // entries per tabl
     while (2 * m * total_tables <= CMP_TAIL_ENTRIES) m *= 2;
     return m;
 }
-// one term: per-wave sums of the K+1 evaluations over the pairs (j, j + cn/2) of its K tables (table k at tab + k * m)
-template <int K>
-__device__ __forceinline__ void tail_term_sums(const uint32_t* tab, const uint32_t* lin /* the term's additive table or nullptr */,
-                                               uint32_t m, uint32_t cn, Fr* wave_part /* [rec] of this wave */, uint32_t rec_off) {
+// Where a term's tables lie: in LDS (table k at tab + k * m) or, in the first rounds of a proof of the batch kernel, behind pointers.
+struct LdsTables {
+    const uint32_t* tab;
+    uint32_t m;
+    __device__ __forceinline__ LdsTables term(uint32_t q0) const { return LdsTables{tab + 8 * (size_t)q0 * m, m}; }   // from table q0 on
+    __device__ __forceinline__ Fr at(uint32_t k, uint32_t j) const { return lds_load_fr(tab, k * m + j); }
+};
+struct PointedTables {
+    const uint64_t* const* ptr;          // (in LDS: k is a compile-time index, the term's first table is not)
+    __device__ __forceinline__ PointedTables term(uint32_t q0) const { return PointedTables{ptr + q0}; }
+    __device__ __forceinline__ Fr at(uint32_t k, uint32_t j) const {      // the pointer is the same in every lane: kept in scalar registers
+        const uint64_t p = (uint64_t)ptr[k];
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+        return load_fr(reinterpret_cast<const uint64_t*>(((uint64_t)hi << 32) | lo), j);
+    }
+};
+// one term: per-wave sums of the K+1 evaluations over the pairs (j, j + cn/2) of its K tables, by a workgroup of BLOCK lanes
+template <int K, int BLOCK, class Tables>
+__device__ __forceinline__ void tail_term_sums_of(const Tables& tabs, const uint32_t* lin /* the term's additive table or nullptr */,
+                                                  uint32_t cn, Fr* wave_part /* [rec] of this wave */, uint32_t rec_off) {
     Fr sums[K + 1];
 #pragma unroll
     for (int t = 0; t <= K; ++t) sums[t] = Fr::zero();
     const uint32_t half = cn >> 1;
     if ((threadIdx.x & ~63u) < half) {   // waves without a pair keep their zeros
-        for (uint32_t j = threadIdx.x; j < half; j += CMP_TAIL_BLOCK) {
+        for (uint32_t j = threadIdx.x; j < half; j += BLOCK) {
             Fr lo[K], hi[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) { lo[k] = lds_load_fr(tab, k * m + j); hi[k] = lds_load_fr(tab, k * m + j + half); }
+            for (int k = 0; k < K; ++k) { lo[k] = tabs.at(k, j); hi[k] = tabs.at(k, j + half); }
             accumulate_round_evals<K>(lo, hi, sums);
             if (lin) accumulate_linear_evals<K>(lds_load_fr(lin, j), lds_load_fr(lin, j + half), sums);
         }
@@ -998,6 +1023,10 @@ __device__ __forceinline__ void tail_term_sums(const uint32_t* tab, const uint32
 #pragma unroll
         for (int t = 0; t <= K; ++t) wave_part[rec_off + t] = sums[t];
     }
+}
+template <int K>
+__device__ __forceinline__ void tail_term_sums(const uint32_t* tab, const uint32_t* lin, uint32_t m, uint32_t cn, Fr* wave_part, uint32_t rec_off) {
+    tail_term_sums_of<K, CMP_TAIL_BLOCK>(LdsTables{tab, m}, lin, cn, wave_part, rec_off);
 }
 
 // The tail's work beside the hash: the upper half of every table becomes d^ = to_mont(hi - lo), so that the fold behind the
@@ -1015,13 +1044,93 @@ struct TailShadow {
     }
 };
 // the fold itself, by the waves that do not convert the challenge (1..): tables of `half` entries afterwards
+template <int BLOCK = CMP_TAIL_BLOCK>
 __device__ __forceinline__ void tail_fold(uint32_t* tab, uint32_t total, uint32_t m, uint32_t half, const Fr& c_canon) {
     if (threadIdx.x < 64) return;
-    for (uint32_t idx = threadIdx.x - 64; idx < total * half; idx += CMP_TAIL_BLOCK - 64) {
+    for (uint32_t idx = threadIdx.x - 64; idx < total * half; idx += BLOCK - 64) {
         const uint32_t q = idx / half, j = idx % half;
         const Fr lo = lds_load_fr(tab, q * m + j), dhat = lds_load_fr(tab, q * m + j + half);
         lds_store_fr(tab, q * m + j, lo + fr_mul_outlined(c_canon, dhat));
     }
+}
+// A round's sums into sh.evals, for a workgroup of BLOCK lanes (every thread calls; ends behind a barrier).  Two forms.
+// tail_late_round / tail_late_evals -- late rounds (all pairs fit one wave): wave w computes evaluation w of the record -- one point t
+// of one term -- for every pair and reduces it, so the critical path is K - 1 products and ONE wave reduction instead of all (K + 1)
+// points of all terms one after another on the same lanes.  Field arithmetic is exact: same sums.
+// Terms of three and more tables take this form from 256 pairs on (a few pairs per lane: K - 1 products each, against
+// (K + 1)(K - 1) per pair with one lane per pair: 24 at K = 5, ~16 us of a round).
+template <int BLOCK>
+__device__ __forceinline__ bool tail_late_round(const ComposedMeta& meta, uint32_t cn) {
+    const bool wide_terms = meta.k[0] >= 3 || (meta.n_terms > 1 && meta.k[1] >= 3);
+    return (cn >> 1) <= (wide_terms ? 256u : 64u) && meta.rec <= BLOCK / 64;
+}
+__device__ __forceinline__ void tail_late_evals(const uint32_t* tab, const ComposedMeta& meta, uint32_t m, uint32_t cn, CloseShared& sh) {
+    const uint32_t half = cn >> 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < meta.rec) {
+        uint32_t p = 0, q0w = 0;
+        while (p + 1 < meta.n_terms && wave >= meta.rec_off[p + 1]) { q0w += meta.k[p]; ++p; }
+        const uint32_t t = wave - meta.rec_off[p], K = meta.k[p];
+        Fr s = Fr::zero();
+        for (uint32_t j = lane; j < half; j += 64) {
+            Fr pr = Fr::zero();
+            for (uint32_t k = 0; k < K; ++k) {
+                const Fr lo = lds_load_fr(tab, (q0w + k) * m + j), hi = lds_load_fr(tab, (q0w + k) * m + j + half);
+                Fr v = t == 0 ? lo : hi;
+                if (t >= 2) {
+                    const Fr d = hi - lo;
+                    for (uint32_t i = 1; i < t; ++i) v = v + d;
+                }
+                pr = k == 0 ? v : fr_mul_outlined(pr, v);
+            }
+            if (meta.lin_tab[p] != ~0u) {
+                const uint32_t lq = meta.lin_tab[p];
+                const Fr lo = lds_load_fr(tab, lq * m + j), hi = lds_load_fr(tab, lq * m + j + half);
+                Fr v = t == 0 ? lo : hi;
+                if (t >= 2) {
+                    const Fr d = hi - lo;
+                    for (uint32_t i = 1; i < t; ++i) v = v + d;
+                }
+                pr = pr + v;
+            }
+            s = s + pr;
+        }
+        if (half >= 64) {
+            s = wave_reduce_fr(s);
+        } else {
+            // lanes >= half hold zero: log2(half) shuffle steps instead of six
+            for (uint32_t dd = half > 1 ? (1u << (31 - __builtin_clz(half - 1))) : 0; dd >= 1; dd >>= 1) s = s + shfl_down_fr(s, (int)dd);
+        }
+        if (lane == 0) sh.evals[wave] = s;
+    }
+    __syncthreads();
+}
+// tail_round_evals -- every other round: term after term, a lane per pair, all K + 1 points of the term (tail_term_sums_of).
+// lds: where the additive tables lie (meta.lin_tab; only read when a term has one, and then the product tables are there too).
+template <int BLOCK, class Tables>
+__device__ __forceinline__ void tail_round_evals(const Tables& tabs, const uint32_t* lds, const ComposedMeta& meta, uint32_t cn, CloseShared& sh,
+                                                 Fr (*wave_part)[CMP_MAX_REC]) {
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t q0 = 0;
+    for (uint32_t p = 0; p < meta.n_terms; ++p) {
+        const Tables base = tabs.term(q0);
+        const uint32_t* lin = nullptr;
+        if constexpr (std::is_same<Tables, LdsTables>::value) lin = meta.lin_tab[p] != ~0u ? lds + 8 * (size_t)meta.lin_tab[p] * tabs.m : nullptr;
+        switch (meta.k[p]) {
+            case 1: tail_term_sums_of<1, BLOCK>(base, lin, cn, wave_part[wave], meta.rec_off[p]); break;
+            case 2: tail_term_sums_of<2, BLOCK>(base, lin, cn, wave_part[wave], meta.rec_off[p]); break;
+            case 3: tail_term_sums_of<3, BLOCK>(base, lin, cn, wave_part[wave], meta.rec_off[p]); break;
+            case 4: tail_term_sums_of<4, BLOCK>(base, lin, cn, wave_part[wave], meta.rec_off[p]); break;
+            default: tail_term_sums_of<5, BLOCK>(base, lin, cn, wave_part[wave], meta.rec_off[p]); break;
+        }
+        q0 += meta.k[p];
+    }
+    __syncthreads();
+    if (threadIdx.x < meta.rec) {
+        Fr s = wave_part[0][threadIdx.x];
+        for (uint32_t w = 1; w < BLOCK / 64; ++w) s = s + wave_part[w][threadIdx.x];
+        sh.evals[threadIdx.x] = s;
+    }
+    __syncthreads();
 }
 static __global__ __launch_bounds__(CMP_TAIL_BLOCK) void composed_tail_kernel(TailTables tt, uint32_t total, uint32_t m, uint32_t load_fold,
                                                                        const uint64_t* __restrict__ r_ptr, CloseArgs ca,
@@ -1047,83 +1156,10 @@ static __global__ __launch_bounds__(CMP_TAIL_BLOCK) void composed_tail_kernel(Ta
     }
     __syncthreads();
     uint32_t cn = m, first = ca.first;
-    const uint32_t wave = threadIdx.x >> 6;
     for (uint32_t round = ca.round; round < ca.round + n_rounds; ++round) {
         ZK_STAMP_AT(0, round, 6);
-        // Late rounds (all pairs fit one wave): wave w computes evaluation w of the record -- one point t of one term -- for
-        // every pair and reduces it, so the critical path is K - 1 products and ONE wave reduction instead of all (K + 1) points
-        // of all terms one after another on the same lanes.  Field arithmetic is exact: same sums.
-        // Terms of three and more tables take this form from 256 pairs on (a few pairs per lane: K - 1 products each, against
-        // (K + 1)(K - 1) per pair with one lane per pair: 24 at K = 5, ~16 us of a round).
-        const bool wide_terms = ca.meta.k[0] >= 3 || (ca.meta.n_terms > 1 && ca.meta.k[1] >= 3);
-        if ((cn >> 1) <= (wide_terms ? 256u : 64u) && ca.meta.rec <= CMP_TAIL_BLOCK / 64) {
-            const uint32_t half = cn >> 1, lane = threadIdx.x & 63;
-            if (wave < ca.meta.rec) {
-                uint32_t p = 0, q0w = 0;
-                while (p + 1 < ca.meta.n_terms && wave >= ca.meta.rec_off[p + 1]) { q0w += ca.meta.k[p]; ++p; }
-                const uint32_t t = wave - ca.meta.rec_off[p], K = ca.meta.k[p];
-                Fr s = Fr::zero();
-                for (uint32_t j = lane; j < half; j += 64) {
-                    Fr pr = Fr::zero();
-                    for (uint32_t k = 0; k < K; ++k) {
-                        const Fr lo = lds_load_fr(tab, (q0w + k) * m + j), hi = lds_load_fr(tab, (q0w + k) * m + j + half);
-                        Fr v = t == 0 ? lo : hi;
-                        if (t >= 2) {
-                            const Fr d = hi - lo;
-                            for (uint32_t i = 1; i < t; ++i) v = v + d;
-                        }
-                        pr = k == 0 ? v : fr_mul_outlined(pr, v);
-                    }
-                    if (ca.meta.lin_tab[p] != ~0u) {
-                        const uint32_t lq = ca.meta.lin_tab[p];
-                        const Fr lo = lds_load_fr(tab, lq * m + j), hi = lds_load_fr(tab, lq * m + j + half);
-                        Fr v = t == 0 ? lo : hi;
-                        if (t >= 2) {
-                            const Fr d = hi - lo;
-                            for (uint32_t i = 1; i < t; ++i) v = v + d;
-                        }
-                        pr = pr + v;
-                    }
-                    s = s + pr;
-                }
-                if (half >= 64) {
-                    s = wave_reduce_fr(s);
-                } else {
-                    // lanes >= half hold zero: log2(half) shuffle steps instead of six
-                    for (uint32_t dd = half > 1 ? (1u << (31 - __builtin_clz(half - 1))) : 0; dd >= 1; dd >>= 1) s = s + shfl_down_fr(s, (int)dd);
-                }
-                if (lane == 0) sh.evals[wave] = s;
-            }
-            __syncthreads();
-            close_round(sh, ca, &trs, round, first, TailShadow{tab, total, m, cn == 2 ? 0u : half});
-            first = 0;
-            if (cn == 2) break;
-            tail_fold(tab, total, m, half, sh.challenge_canon);
-            __syncthreads();
-            ZK_STAMP_AT(0, round, 7);
-            cn = half;
-            continue;
-        }
-        uint32_t q0 = 0;
-        for (uint32_t p = 0; p < ca.meta.n_terms; ++p) {
-            const uint32_t* base = tab + 8 * (size_t)q0 * m;
-            const uint32_t* lin = ca.meta.lin_tab[p] != ~0u ? tab + 8 * (size_t)ca.meta.lin_tab[p] * m : nullptr;
-            switch (ca.meta.k[p]) {
-                case 1: tail_term_sums<1>(base, lin, m, cn, wave_part[wave], ca.meta.rec_off[p]); break;
-                case 2: tail_term_sums<2>(base, lin, m, cn, wave_part[wave], ca.meta.rec_off[p]); break;
-                case 3: tail_term_sums<3>(base, lin, m, cn, wave_part[wave], ca.meta.rec_off[p]); break;
-                case 4: tail_term_sums<4>(base, lin, m, cn, wave_part[wave], ca.meta.rec_off[p]); break;
-                default: tail_term_sums<5>(base, lin, m, cn, wave_part[wave], ca.meta.rec_off[p]); break;
-            }
-            q0 += ca.meta.k[p];
-        }
-        __syncthreads();
-        if (threadIdx.x < ca.meta.rec) {
-            Fr s = wave_part[0][threadIdx.x];
-            for (uint32_t w = 1; w < CMP_TAIL_BLOCK / 64; ++w) s = s + wave_part[w][threadIdx.x];
-            sh.evals[threadIdx.x] = s;
-        }
-        __syncthreads();
+        if (tail_late_round<CMP_TAIL_BLOCK>(ca.meta, cn)) tail_late_evals(tab, ca.meta, m, cn, sh);
+        else tail_round_evals<CMP_TAIL_BLOCK>(LdsTables{tab, m}, tab, ca.meta, cn, sh, wave_part);
         const uint32_t half = cn >> 1;
         close_round(sh, ca, &trs, round, first, TailShadow{tab, total, m, cn == 2 ? 0u : half});
         first = 0;

@@ -199,17 +199,18 @@ static __global__ __launch_bounds__(MLE_BLOCK) void elementwise_kernel(const uin
 }
 
 // Canonical big-endian bytes of every element (Multilinear::to_bytes, evaluation_form.rs:54-62)
+__device__ __forceinline__ void store_be_bytes(uint32_t* __restrict__ out_words, size_t q, Fr stored) {
+    const Fr c = stored.from_mont();
+    uint4* p = reinterpret_cast<uint4*>(out_words + 8 * q);
+    p[0] = make_uint4(__builtin_bswap32(c.l[7]), __builtin_bswap32(c.l[6]), __builtin_bswap32(c.l[5]),
+                      __builtin_bswap32(c.l[4]));
+    p[1] = make_uint4(__builtin_bswap32(c.l[3]), __builtin_bswap32(c.l[2]), __builtin_bswap32(c.l[1]),
+                      __builtin_bswap32(c.l[0]));
+}
 static __global__ __launch_bounds__(MLE_BLOCK) void to_bytes_kernel(const uint64_t* __restrict__ in, size_t n,
                                                              uint32_t* __restrict__ out_words) {
     const size_t stride = (size_t)gridDim.x * MLE_BLOCK;
-    for (size_t q = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; q < n; q += stride) {
-        Fr c = load_fr(in, q).from_mont();
-        uint4* p = reinterpret_cast<uint4*>(out_words + 8 * q);
-        p[0] = make_uint4(__builtin_bswap32(c.l[7]), __builtin_bswap32(c.l[6]), __builtin_bswap32(c.l[5]),
-                          __builtin_bswap32(c.l[4]));
-        p[1] = make_uint4(__builtin_bswap32(c.l[3]), __builtin_bswap32(c.l[2]), __builtin_bswap32(c.l[1]),
-                          __builtin_bswap32(c.l[0]));
-    }
+    for (size_t q = (size_t)blockIdx.x * MLE_BLOCK + threadIdx.x; q < n; q += stride) store_be_bytes(out_words, q, load_fr(in, q));
 }
 
 // One round of MultilinearKZG::open on an n-entry table: quotient[j] = in[j + n/2] - in[j]  (get_poly_quotient,

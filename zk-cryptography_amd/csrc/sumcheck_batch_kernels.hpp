@@ -22,6 +22,12 @@ constexpr uint32_t SCB_MAX_ENTRIES = 1u << 16;        // K * n above this: the e
 constexpr uint32_t SCB_CHUNK = 1024;                  // proofs per launch
 constexpr uint32_t SCB_MIN_CHUNK = 256;               // ... never fewer (one workgroup per CU), whatever the slabs take
 constexpr size_t SCB_SLAB_BYTES = (size_t)256 << 20;  // most global scratch a chunk asks of the workspace (256 proofs of 2^16 entries)
+// proofs per launch of every batched sumcheck prover, from the global scratch one proof needs (slab, staging; 0: resident)
+inline uint32_t scb_chunk(size_t scratch_per_proof) {
+    if (!scratch_per_proof) return SCB_CHUNK;
+    const size_t fit = SCB_SLAB_BYTES / scratch_per_proof;
+    return (uint32_t)(fit < SCB_MIN_CHUNK ? SCB_MIN_CHUNK : fit > SCB_CHUNK ? SCB_CHUNK : fit);
+}
 
 // Fewest proofs from which on the batch kernel measured faster per proof than the better thing a caller could do without it
 // (profiles/sumcheck_batch/NOTES.md, "Where the kernel starts to pay"): for the basic prover eight proofs in flight through

@@ -1091,9 +1091,7 @@ int zk_sumcheck_batch_run(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h
     const uint32_t n_vars = log2_exact(n);
     const uint32_t resident_len = scb_resident_len(k, n);
     const size_t slab_per = resident_len < n ? (size_t)k * (n / 2) * 32 : 0;
-    uint32_t chunk = SCB_CHUNK;
-    if (slab_per) chunk = (uint32_t)std::max<size_t>(SCB_MIN_CHUNK, std::min<size_t>(SCB_CHUNK, SCB_SLAB_BYTES / slab_per));
-    const uint32_t bc_max = std::min(batch, chunk);
+    const uint32_t bc_max = std::min(batch, scb_chunk(slab_per));
     const uint32_t out_words = scb_out_words(k, n_vars, absorb_sum);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // workspace: [table pointers | claimed sums] (uploaded) [results] [slabs]; pinned: [results] [table pointers | claimed sums]
