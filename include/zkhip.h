@@ -50,10 +50,11 @@
  *     NO WORKSPACE: zkhip_ctx_synchronize, zkhip_mle_partial_evaluation, zkhip_mle_half_sums, zkhip_mle_add_distinct,
  *     zkhip_mle_mul_distinct, zkhip_mle_elementwise, zkhip_mle_add_to_front, zkhip_mle_add_to_back, zkhip_mle_to_bytes,
  *     zkhip_mle_block_sums, zkhip_mle_block_sums_deferred, zkhip_mle_block_sums_total, zkhip_composed_sum, zkhip_multi_composed_sum,
- *     zkhip_composed_element_wise, zkhip_circuit_create, zkhip_gkr_prove_batch, zkhip_gkr_layer_tables, zkhip_srs_fingerprint,
+ *     zkhip_composed_element_wise, zkhip_circuit_create, zkhip_circuit_evaluate_batch, zkhip_gkr_prove_batch, zkhip_gkr_layer_tables, zkhip_srs_fingerprint,
  *     zkhip_table_release, zkhip_dense_evaluate, zkhip_dense_degree, zkhip_sc_begin, zkhip_plonk_vkey_create,
  *     zkhip_plonk_key_destroy.
- *     (zkhip_gkr_prove_batch proves on lanes with a workspace each.  zkhip_sc_begin takes an allocation of its own while the workspace
+ *     (zkhip_gkr_prove_batch proves on lanes with a workspace each.  zkhip_circuit_evaluate_batch keeps its pointer table in a buffer of the
+ *     circuit's own.  zkhip_sc_begin takes an allocation of its own while the workspace
  *     is lent.  zkhip_mle_block_sums* need none at the granularity zkhip_sumcheck_plan_log_blocks asks for; with more than 2^15 chunks of
  *     4096 entries, or fine blocks of more than 256 entries, they take a buffer from it and are then refused like the users above.)
  */
@@ -228,6 +229,29 @@ int zkhip_gkr_prove_circuit(zkhip_circuit *circuit, const uint64_t *const *h_lay
 int zkhip_gkr_prove_batch(zkhip_circuit *circuit, uint32_t n_proofs, uint32_t max_lanes, const uint64_t *const *h_layer_ptrs,
                           const size_t *h_layer_len, uint64_t *h_sums, uint32_t *h_n_rounds, uint32_t *h_round_poly_lens,
                           uint64_t *h_round_polys, uint64_t *h_wb, uint64_t *h_wc, uint64_t *h_w0, uint64_t *h_challenges, int *h_status);
+/* Circuit::evaluation (circuit/src/circuit.rs:31-57) of n_inputs inputs on the resident circuit in ONE call: what a loop of
+ * zkhip_circuit_layer_eval over the layers and the inputs leaves, bit for bit, without that loop's gate upload and two synchronisations
+ * per layer and input (gkr/benches/gkr_benchmark.rs:19-26 evaluates, then proves, input after input).
+ *   h_layer_ptrs : the pointer array zkhip_gkr_prove_batch takes, and may be handed to it unchanged afterwards: entry
+ *                  b * (n_layers + 1) + k is the DEVICE table of layer k of input b.  Entry k = n_layers is the input: it is read and holds
+ *                  input_len entries.  Entries k < n_layers are WRITTEN: layer k's h_n_gates[k] values, in tables the caller allocated.
+ *                  The tables one call writes must not overlap each other or an input; several b may share one input table.  The
+ *                  table of a layer without gates has no entries, and its pointer may be NULL.
+ *   h_layer_len  : nullable; [n_layers + 1] receives the lengths in that order (h_n_gates[0 .. n_layers), then input_len).
+ * Every circuit zkhip_circuit_create accepts is evaluated, also one with a layer the PROVER reports (more than 2^l gates in layer l, a
+ * label beyond 2^(l+1)): evaluation needs a layer's gates and the length of the table below it, nothing else.  The reference's index
+ * panic -- a label >= the length of the table below: h_n_gates[k + 1], or input_len under the last layer -- is ZKHIP_ERR_INDEX, found
+ * from the largest label of every layer (kept since zkhip_circuit_create) before anything is enqueued: no table is written.
+ * n_inputs = 0: ZKHIP_OK, nothing is done.  A NULL circuit or pointer array, or a NULL table that would be read or written:
+ * ZKHIP_ERR_ARG.  Per call the host copies the pointer table to the device (one upload, into a buffer the circuit owns: nothing of the
+ * context's workspace is taken, so the call is served beside every holder), enqueues a handful of launches and waits once; the outputs
+ * are complete when it returns.  Layers of more than 2^10 gates take one launch each for all inputs (gate tiles x inputs); from the
+ * first layer of at most 2^10 gates up to the output ONE launch walks the rest, a workgroup per input with a workgroup barrier
+ * between layers (depth 8: the whole circuit).  More than 4096 inputs run as chunks of 4096 inside the call.
+ * Circuit::random(8): 26.6 us for one input, 1.0 us per input at 32; depth 20: 90.9 us, 20.4 us per input at 24
+ * (profiles/circuit_eval_batch/NOTES.md). */
+int zkhip_circuit_evaluate_batch(zkhip_circuit *circuit, uint32_t n_inputs, size_t input_len,
+                                 const uint64_t *const *h_layer_ptrs, size_t *h_layer_len);
 /* The tables of one layer's sumcheck in the linear-time form, for a caller that runs the sumcheck itself --
  * the sharded prover shards these tables over the ranks (zkhip_mc_begin_ex) instead of calling zkhip_gkr_prove_circuit.
  * Layer `layer` (0 = output layer) of a device-resident circuit, d_w = the layer's input values (w_len = 2^(layer+1)).

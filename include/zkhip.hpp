@@ -712,10 +712,9 @@ struct GKRProof {                                                               
 class DeviceCircuit {
   public:
     explicit DeviceCircuit(const Circuit& circuit) : n_layers_((uint32_t)circuit.layers.size()) {
-        std::vector<size_t> n_gates;
         std::vector<uint8_t> gt; std::vector<uint32_t> i0, i1;
-        for (auto& l : circuit.layers) { n_gates.push_back(l.layer.size()); Circuit::arrays(l, gt, i0, i1); }
-        check(zkhip_circuit_create(ctx(), n_layers_, n_gates.data(), gt.data(), i0.data(), i1.data(), &handle_), "circuit_create");
+        for (auto& l : circuit.layers) { n_gates_.push_back(l.layer.size()); Circuit::arrays(l, gt, i0, i1); }
+        check(zkhip_circuit_create(ctx(), n_layers_, n_gates_.data(), gt.data(), i0.data(), i1.data(), &handle_), "circuit_create");
     }
     ~DeviceCircuit() { zkhip_circuit_destroy(handle_); }
     DeviceCircuit(const DeviceCircuit&) = delete;
@@ -790,8 +789,33 @@ class DeviceCircuit {
                                  &wb[(size_t)b * nl], &wc[(size_t)b * nl], &w0[(size_t)b * 2]));
         return out;
     }
+    // Circuit::evaluation of every input (one length) in ONE call (zkhip_circuit_evaluate_batch): no gate list is packed or uploaded per
+    // layer and input, one wait.  Every Evaluation equals Circuit::evaluation's and goes into prove_batch as it is; the same
+    // std::out_of_range where evaluation throws it (no table is written then).
+    std::vector<Circuit::Evaluation> evaluation_batch(const std::vector<std::vector<Fr>>& inputs) const {
+        const uint32_t nl = n_layers_, B = (uint32_t)inputs.size();
+        if (!B) return {};
+        const size_t n_in = inputs[0].size();
+        std::vector<Circuit::Evaluation> evs(B);
+        std::vector<const uint64_t*> ptrs;
+        for (uint32_t b = 0; b < B; ++b) {
+            if (inputs[b].size() != n_in) throw Panic("evaluation_batch: the inputs of a batch share their length");
+            for (uint32_t k = 0; k <= nl; ++k) {
+                const size_t len = k < nl ? n_gates_[k] : n_in;
+                evs[b].tables.push_back(std::make_shared<DeviceBuffer>(32 * len));
+                evs[b].lens.push_back(len);
+                ptrs.push_back(evs[b].tables.back()->u64());
+            }
+            evs[b].tables.back()->upload(inputs[b].data(), 32 * n_in);
+        }
+        const int st = zkhip_circuit_evaluate_batch(handle_, B, n_in, ptrs.data(), nullptr);
+        if (st == ZKHIP_ERR_INDEX) throw std::out_of_range("index out of bounds: gate input");
+        check(st, "circuit_evaluate_batch");
+        return evs;
+    }
   private:
     uint32_t n_layers_;
+    std::vector<size_t> n_gates_;
     zkhip_circuit* handle_ = nullptr;
 };
 struct GKRProtocol {

@@ -15,6 +15,7 @@
 #include <new>
 #include <vector>
 
+#include "circuit_eval_batch_kernels.hpp"
 #include "ctx.hpp"
 #include "host_util.hpp"
 #include "host_fr.hpp"
@@ -596,6 +597,13 @@ struct zkhip_circuit {
     uint32_t n_layers = 0;
     std::vector<LayerDev> layers;
     zk::DevMem d_mem;
+    // zkhip_circuit_evaluate_batch: the layers as its kernels read them (in d_mem), what its host checks need (every layer's gate count
+    // and largest label), and the call's pointer table -- device copy and pinned staging, the circuit's own, so that the call takes
+    // nothing of the context's workspace
+    const zk::CebLayer* d_eval_layers = nullptr;
+    std::vector<size_t> n_gates;
+    std::vector<uint32_t> max_label;
+    zk::GrowBuf eval_ptrs, eval_ptrs_pin;
 };
 
 extern "C" void zkhip_circuit_destroy(zkhip_circuit* cir) {
@@ -610,7 +618,10 @@ extern "C" void zkhip_circuit_destroy(zkhip_circuit* cir) {
         }
     }
     // the device arrays go with the circuit on its context's device; if that cannot be made current they are left to the runtime
-    if (cir->d_mem && !(cir->c && cir->c->activate() == ZKHIP_OK)) (void)cir->d_mem.release();
+    if (!(cir->c && cir->c->activate() == ZKHIP_OK)) {
+        (void)cir->d_mem.release();
+        cir->eval_ptrs.ptr = cir->eval_ptrs_pin.ptr = nullptr;
+    }
     delete cir;
 }
 
@@ -631,6 +642,8 @@ extern "C" int zkhip_circuit_create(zkhip_ctx* c, uint32_t n_layers, const size_
         total += 2 * al(4 * (w_len + 1 + ng)) + 2 * al(4 * ng) + al(ng);
         g_off += ng;
     }
+    const size_t o_eval_layers = total;
+    total += al(sizeof(zk::CebLayer) * n_layers);
     struct Destroy { void operator()(zkhip_circuit* p) const { zkhip_circuit_destroy(p); } };
     std::unique_ptr<zkhip_circuit, Destroy> cir(new (std::nothrow) zkhip_circuit());
     if (!cir) return ZKHIP_ERR_NOMEM;
@@ -666,12 +679,73 @@ extern "C" int zkhip_circuit_create(zkhip_ctx* c, uint32_t n_layers, const size_
         if (ng) std::memcpy(host.data() + off, h_gate_type + g_off, ng);
         ld.type = (uint8_t*)(base + off); off += al(ng);
         cir->layers.push_back(ld);
+        uint32_t top = 0;
+        for (size_t g = 0; g < ng; ++g) top = std::max(top, std::max(h_in0[g_off + g], h_in1[g_off + g]));
+        cir->n_gates.push_back(ng);
+        cir->max_label.push_back(top);
+        zk::CebLayer el = {ld.in0, ld.in1, ld.type, (uint32_t)ng, 0u};
+        std::memcpy(host.data() + o_eval_layers + sizeof(el) * l, &el, sizeof(el));
         g_off += ng;
     }
+    cir->d_eval_layers = (const zk::CebLayer*)((char*)cir->d_mem.get() + o_eval_layers);
     if (total && (hipMemcpyAsync(cir->d_mem.get(), host.data(), total, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                   hipStreamSynchronize(c->stream) != hipSuccess))
         return ZKHIP_ERR_HIP;
     *out = cir.release();
+    return ZKHIP_OK;
+}
+
+// Circuit::evaluation of n_inputs inputs on the resident circuit (include/zkhip.h; kernels and what they share: circuit_eval_batch_kernels.hpp,
+// the launch plan and the label bounds: circuit_eval_plan.hpp).  The host checks, copies the pointer table up once, enqueues
+// ceb_launches() kernels per chunk of CEB_CHUNK inputs and waits once.
+extern "C" int zkhip_circuit_evaluate_batch(zkhip_circuit* cir, uint32_t n_inputs, size_t input_len, const uint64_t* const* h_layer_ptrs,
+                                            size_t* h_layer_len) {
+    if (!cir) return ZKHIP_ERR_ARG;
+    if (n_inputs == 0) return ZKHIP_OK;
+    if (!h_layer_ptrs) return ZKHIP_ERR_ARG;
+    zkhip_ctx* c = cir->c;
+    const uint32_t nl = cir->n_layers, stride = nl + 1;
+    const size_t* ng = cir->n_gates.data();
+    for (uint32_t k = 0; k < nl; ++k)
+        if (ng[k] > 0xffffffffu) return ZKHIP_ERR_SHAPE;                  // the kernels count a layer's gates in 32 bits, like its labels
+    // current_input[e.inputs[k]] panics (circuit.rs:41-50): before anything is enqueued, so that no table is written
+    if (zk::ceb_first_bad_layer(ng, cir->max_label.data(), nl, input_len) != nl) return ZKHIP_ERR_INDEX;
+    const size_t entries = (size_t)n_inputs * stride;
+    for (size_t b = 0; b < n_inputs; ++b)                                  // a table the kernels would touch must be there
+        for (uint32_t k = 0; k <= nl; ++k)
+            if (!h_layer_ptrs[b * stride + k] && (k < nl ? ng[k] != 0 : ng[nl - 1] != 0)) return ZKHIP_ERR_ARG;
+    ZK_TRY(c->activate());
+    {
+        int hip = 0;
+        int rc = cir->eval_ptrs.reserve(8 * entries, {c->stream}, &hip);
+        if (rc == ZKHIP_OK) rc = cir->eval_ptrs_pin.reserve_pinned(8 * entries);
+        if (rc == ZKHIP_ERR_HIP) c->last_hip = hip;
+        ZK_TRY(rc);
+    }
+    std::memcpy(cir->eval_ptrs_pin.ptr, h_layer_ptrs, 8 * entries);
+    const uint64_t* const* d_ptrs = (const uint64_t* const*)cir->eval_ptrs.ptr;
+    ZK_HIP(c, hipMemcpyAsync(cir->eval_ptrs.ptr, cir->eval_ptrs_pin.ptr, 8 * entries, hipMemcpyHostToDevice, c->stream));
+    const uint32_t wide = zk::ceb_wide_layers(ng, nl);
+    for (uint32_t b0 = 0; b0 < n_inputs; b0 += zk::CEB_CHUNK) {
+        const uint32_t bc = std::min(zk::CEB_CHUNK, n_inputs - b0);
+        const uint64_t* const* rows = d_ptrs + (size_t)b0 * stride;
+        for (uint32_t k = nl; k-- > nl - wide;) {
+            ProfScope ps(c, "circuit_eval_wide", 0.0);
+            const zk::CebLayer L = {cir->layers[k].in0, cir->layers[k].in1, cir->layers[k].type, (uint32_t)ng[k], 0u};
+            hipLaunchKernelGGL(zk::circuit_eval_wide_kernel, dim3((unsigned)((ng[k] + zk::CEB_TILE - 1) / zk::CEB_TILE), bc), dim3(zk::CEB_TILE), 0, c->stream,
+                               L, rows, stride, k);
+        }
+        if (wide < nl) {
+            ProfScope ps(c, "circuit_eval_tail", 0.0);
+            hipLaunchKernelGGL(zk::circuit_eval_tail_kernel, dim3(bc), dim3(zk::CEB_TAIL_BLOCK), 0, c->stream, cir->d_eval_layers, rows, stride, nl - wide - 1);
+        }
+        ZK_HIP(c, hipGetLastError());
+    }
+    ZK_TRY(c->wait_stream());            // the outputs are complete, and the pinned table is free for the next call
+    if (h_layer_len) {
+        for (uint32_t k = 0; k < nl; ++k) h_layer_len[k] = ng[k];
+        h_layer_len[nl] = input_len;
+    }
     return ZKHIP_OK;
 }
 

@@ -136,6 +136,38 @@ class Circuit:
         layers.reverse()
         return layers
 
+    def evaluation_batch(self, inputs):
+        """evaluation() of every input of `inputs` (one length) on the circuit resident in HBM, in ONE C-ABI call
+        (zkhip_circuit_evaluate_batch): no gate list is walked, packed or uploaded per layer and input, and the host waits once.
+        -> a list of evaluations, each as evaluation() returns it (n_layers + 1 device tables, output layer first, input last, the same
+        limbs).  The tables are views of ONE arena allocation per call (input b's tables side by side, its input -- a copy -- last), and
+        the list goes into GKRProtocol.prove_batch as it is.  IndexError where evaluation() raises it; nothing is written then."""
+        import torch
+        from zk_cryptography_amd.polynomial import _to_device
+        inputs = list(inputs)
+        if not inputs:
+            return []
+        if all(not isinstance(x, torch.Tensor) for x in inputs):
+            host = np.stack([np.ascontiguousarray(x, dtype=np.uint64) for x in inputs])     # one upload for the whole batch
+            if host.ndim != 3 or host.shape[2] != 4:
+                raise AssertionError("inputs must be uint64 [n, 4] Montgomery limbs, one length")
+            stacked = torch.from_numpy(host.view(np.int64)).cuda()
+        else:
+            stacked = torch.stack([_to_device(x, None) for x in inputs])
+        B, n_in = stacked.shape[0], stacked.shape[1]
+        ctx = N.Context.get(stacked.device.index)
+        dev = GKRProtocol._device_circuit(self, ctx)
+        lens = list(dev.shape) + [n_in]
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        per = int(offs[-1])
+        arena = torch.empty((B, per, 4), dtype=torch.int64, device=stacked.device)
+        arena[:, per - n_in:, :].copy_(stacked)
+        ptrs = np.uint64(arena.data_ptr()) + np.uint64(32) * (np.arange(B, dtype=np.uint64)[:, None] * np.uint64(per) + offs[None, :-1])
+        ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        N.check(N.lib().zkhip_circuit_evaluate_batch(dev.handle.value, B, n_in, ptrs.ctypes.data, None), "circuit_evaluate_batch")
+        cuts = [int(o) for o in offs]
+        return [[arena[b, cuts[k]:cuts[k + 1]] for k in range(len(lens))] for b in range(B)]
+
     def add_mult_mle(self, layer_index):
         """Circuit::add_mult_mle (circuit.rs:59-97) -> (add_mle, mul_mle) as device Multilinears"""
         import torch
@@ -243,6 +275,8 @@ class _DeviceCircuit:
                                           C.byref(self.handle))
         N.check(st, "circuit_create")
         ctx._circuits.append(self)
+        # the handle's hot call takes plain integers for its pointers (as the prover's hot calls do, _native.lib)
+        N.lib().zkhip_circuit_evaluate_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
 
     @property
     def ctx(self):
@@ -361,6 +395,12 @@ class GKRProtocol:
             proof._challenges = [chal[b, k, : n_rounds[b, k]] for k in range(nl)]
             out.append(proof)
         return out
+
+    @staticmethod
+    def prove_inputs(circuit, inputs, max_lanes=0):
+        """The iteration of gkr/benches/gkr_benchmark.rs:19-26 -- circuit.evaluation(&input), then GKRProtocol::prove -- for every input
+        in two C-ABI calls: Circuit.evaluation_batch, whose tables go into prove_batch as they are."""
+        return GKRProtocol.prove_batch(circuit, circuit.evaluation_batch(inputs), max_lanes)
 
     @staticmethod
     def _device_circuit(circuit, ctx):
@@ -486,6 +526,14 @@ class SuccintGKRProtocol:
         from zk_cryptography_amd.kzg import MultilinearKZG
         assert len(circuit_evaluation) >= 3, "the commitment is made inside `for layer_index in 2..len` (:82-152)"
         base = GKRProtocol.prove(circuit, circuit_evaluation)
+        poly, b_clone, c_clone = SuccintGKRProtocol._input_opening(circuit_evaluation, base, tau)
+        commitment = MultilinearKZG.commitment(poly, tau)
+        open_b, open_c = MultilinearKZG.open_batch([poly, poly], [b_clone, c_clone], tau)      # one polynomial at two points: one batch
+        return commitment, SuccintGKRProof(base, open_b, open_c)
+
+    @staticmethod
+    def _input_opening(circuit_evaluation, base, tau):
+        """the input layer blown up to the SRS size (succint_protocol.rs:134-137) and the two points it is opened at (:139-151)"""
         w_i_mle = Multilinear(circuit_evaluation[-1])
         srs_vars = (len(tau)).bit_length() - 1
         assert 1 << srs_vars == len(tau), "Value is not a power of 2"        # gkr/src/utils.rs:100-111 exponent()
@@ -497,6 +545,22 @@ class SuccintGKRProtocol:
         zeros = np.zeros((poly.n_vars - half, 4), dtype=np.uint64)
         b_clone = np.concatenate([ch[:half], zeros])
         c_clone = np.concatenate([ch[half:], np.zeros((poly.n_vars - (len(ch) - half), 4), dtype=np.uint64)])
-        commitment = MultilinearKZG.commitment(poly, tau)
-        open_b, open_c = MultilinearKZG.open_batch([poly, poly], [b_clone, c_clone], tau)      # one polynomial at two points: one batch
-        return commitment, SuccintGKRProof(base, open_b, open_c)
+        return poly, b_clone, c_clone
+
+    @staticmethod
+    def prove_batch(circuit, circuit_evaluations, tau):
+        """prove() of every evaluation of one circuit -> [(commitment, proof)], each what prove() returns: the sumcheck parts from ONE
+        GKRProtocol.prove_batch, the blown-up input layers committed three commits in flight at a time (commitment_begin; a commit
+        in flight holds the context's workspace, so each group is collected before the openings), and all 2 B openings from ONE
+        MultilinearKZG.open_batch."""
+        from zk_cryptography_amd.kzg import MultilinearKZG
+        circuit_evaluations = list(circuit_evaluations)
+        assert all(len(ev) >= 3 for ev in circuit_evaluations), "the commitment is made inside `for layer_index in 2..len` (:82-152)"
+        bases = GKRProtocol.prove_batch(circuit, circuit_evaluations)
+        opened = [SuccintGKRProtocol._input_opening(ev, base, tau) for ev, base in zip(circuit_evaluations, bases)]
+        commitments = []
+        for at in range(0, len(opened), 3):
+            pending = [MultilinearKZG.commitment_begin(poly, tau) for poly, _, _ in opened[at:at + 3]]
+            commitments += [p.wait() for p in pending]
+        opens = MultilinearKZG.open_batch([poly for poly, _, _ in opened for _ in range(2)], [pt for _, b, c in opened for pt in (b, c)], tau)
+        return [(commitments[i], SuccintGKRProof(bases[i], opens[2 * i], opens[2 * i + 1])) for i in range(len(opened))]
