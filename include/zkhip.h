@@ -36,7 +36,7 @@
  *     also where a small input would not have needed scratch -- and the others serve.  (Two inputs leave a user nothing to do that
  *     needs the workspace, and are served: zkhip_univariate_kzg_open of at most one coefficient, whose quotient is empty, and
  *     zkhip_circuit_add_mult_mle without gates, which clears its two tables.)
- *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
+ *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_mle_evaluation_batch, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
  *     zkhip_circuit_add_mult_mle, zkhip_gkr_prove, zkhip_gkr_prove_circuit, zkhip_gkr_prove_sharded, zkhip_sumcheck_prove,
  *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_multi_composed_prove_batch,
  *     zkhip_mc_begin, zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
@@ -136,6 +136,26 @@ int zkhip_mle_partial_evaluations(zkhip_ctx *ctx, const uint64_t *d_evals, size_
 /* MultilinearTrait::evaluation (evaluation_form.rs:162-175): h_out[4]. n_pts must equal log2(n). */
 int zkhip_mle_evaluation(zkhip_ctx *ctx, const uint64_t *d_evals, size_t n, const uint64_t *h_pts, size_t n_pts,
                          uint64_t *h_out);
+/* MultilinearTrait::evaluation of `batch` tables of n entries each, every one at a point of its own, in one call: h_table_ptrs is a
+ * HOST array of `batch` DEVICE pointers (a pointer may repeat -- one table at several points; the tables are only read),
+ * h_points[batch][n_pts][4] the points job after job, h_out[batch][4] the values: h_out[b] is limb for limb what zkhip_mle_evaluation
+ * returns for table b and point b (field arithmetic is exact and values are kept reduced, so the other association of the sum below
+ * changes no limb).  Checks and status codes as zkhip_mle_evaluation, with a NULL table pointer among the batch's ZKHIP_ERR_ARG, applied
+ * once and before anything is launched, reserved or written (ZKHIP_ERR_BUSY while a commit in flight or a split-phase session holds
+ * the workspace); a refused call leaves h_out untouched; batch == 0 is ZKHIP_OK and touches nothing.
+ * Tables up to 2^12 entries: chunks of up to 1024 jobs, each ONE launch of one workgroup per job, which stages the table in LDS (32 n
+ * bytes requested, so that small tables share a compute unit) and folds it to its value (csrc/mle_batch_kernels.hpp).  Tables of 2^13 ..
+ * 2^16 entries, h = log2(n) - 12: workgroup (q, b) of a grid (2^h, jobs) folds entries [q 2^12, (q + 1) 2^12) of table b with points
+ * h .. n_pts - 1 and weights the value with eq_q(points 0 .. h - 1) -- point 0 is the most significant index bit --, and a second,
+ * small launch sums each job's 2^h records.  Per chunk: one upload of the table pointers and points, the launch or launches, one
+ * copy of the results and one synchronisation on the context's stream; pointers, points, records and results live in the context's
+ * workspace.  Tables of 2^17 entries and more, one job, and fewer jobs than zkhip_mle_evaluation_batch_min(n) run zkhip_mle_evaluation,
+ * job after job.
+ * zkhip_mle_evaluation_batch_min (host only, no handle): the fewest jobs the kernels take at this size -- 2 at every size up to 2^16
+ * (measured against the loop of single calls, profiles/mle_batch/NOTES.md); 0 where no batch is taken (n >= 2^17, n no power of two). */
+int zkhip_mle_evaluation_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_table_ptrs, size_t n,
+                               const uint64_t *h_points, size_t n_pts, uint64_t *h_out);
+uint32_t zkhip_mle_evaluation_batch_min(size_t n);
 /* split_poly_into_two_and_sum_each_part (:68-74) and sum_over_the_boolean_hypercube (:80-84) /
  * Sumcheck::poly_sum (sumcheck.rs:25-27): h_out[12] = (lower-half sum, upper-half sum, total). */
 int zkhip_mle_half_sums(zkhip_ctx *ctx, const uint64_t *d_evals, size_t n, uint64_t *h_out);

@@ -131,6 +131,25 @@ class Multilinear {
               "evaluation");
         return r;
     }
+    // the evaluations of tables of one length in one call (zkhip_mle_evaluation_batch), value b as from tables[b].evaluation(points[b]);
+    // a table may stand in the list several times
+    static std::vector<Fr> evaluation_batch(const std::vector<Multilinear>& tables, const std::vector<std::vector<Fr>>& points) {
+        const size_t B = tables.size();
+        if (points.size() != B) throw Panic("evaluation_batch: one point per table");
+        std::vector<Fr> out(B);
+        if (B == 0) return out;
+        const size_t n = tables[0].len(), nv = tables[0].n_vars;
+        std::vector<const uint64_t*> ptrs(B);
+        std::vector<Fr> flat;
+        for (size_t b = 0; b < B; ++b) {
+            if (tables[b].len() != n) throw Panic("evaluation_batch: the tables of a batch share their length");
+            if (points[b].size() != nv) throw Panic("Number of evaluation points must match the number of variables");
+            ptrs[b] = tables[b].device();
+            flat.insert(flat.end(), points[b].begin(), points[b].end());
+        }
+        check(zkhip_mle_evaluation_batch(ctx(), (uint32_t)B, ptrs.data(), n, flat.empty() ? nullptr : flat[0].l, nv, out[0].l), "evaluation_batch");
+        return out;
+    }
     Multilinear split_poly_into_two_and_sum_each_part() const {   // :68-74
         uint64_t h[12];
         check(zkhip_mle_half_sums(ctx(), device(), n_, h), "half_sums");

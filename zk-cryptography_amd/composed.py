@@ -36,8 +36,8 @@ class ComposedMultilinear:
     def evaluation(self, points):
         """composed_multilinear.rs:51-61: product of the tables' evaluations -> python int (canonical)"""
         acc = 1
-        for p in self.polys:
-            acc = acc * Fr.to_ints(p.evaluation(points))[0] % Fr.MODULUS
+        for v in Fr.to_ints(Multilinear.evaluation_batch(self.polys, points)):     # the K factors in one call
+            acc = acc * v % Fr.MODULUS
         return acc
 
     def to_bytes(self):

@@ -150,6 +150,26 @@ static __global__ __launch_bounds__(MLE_BLOCK) void finish_sums_kernel(const uin
     }
 }
 
+// The folds of one workgroup on a table in LDS: stages in[0..n) in tab, folds variable 0 with point_at(0), point_at(1), ..,
+// point_at(n_pts - 1) and returns the entries left in tab[0..) (n >> n_pts), a barrier behind the last fold; LANES = the
+// workgroup's size.  Shared by
+// fold_tail_kernel (points by value) and the batched evaluation (mle_batch_kernels.hpp: a job's points from device memory).
+template <int LANES, class PointAt>
+__device__ __forceinline__ uint32_t fold_tail_body(Fr* tab, const uint64_t* __restrict__ in, uint32_t n, uint32_t n_pts, PointAt point_at) {
+    for (uint32_t j = threadIdx.x; j < n; j += LANES) tab[j] = load_fr(in, j);
+    __syncthreads();
+    uint32_t cur = n;
+    for (uint32_t p = 0; p < n_pts; ++p) {
+        const Fr r = point_at(p);
+        const uint32_t half = cur >> 1;
+        // in place: lane j reads (j, j+half) and writes j; no other lane touches index j this round
+        for (uint32_t j = threadIdx.x; j < half; j += LANES) tab[j] = fold_pair(tab[j], tab[j + half], r);
+        __syncthreads();
+        cur = half;
+    }
+    return cur;
+}
+
 // Finish an evaluation inside one workgroup: folds variable 0 repeatedly with points pts[0..n_pts) until the
 // table (n <= TAIL_N entries, staged in LDS) has n >> n_pts entries left; writes them to out.
 static __global__ __launch_bounds__(MLE_BLOCK) void fold_tail_kernel(const uint64_t* __restrict__ in, uint32_t n,
@@ -157,17 +177,7 @@ static __global__ __launch_bounds__(MLE_BLOCK) void fold_tail_kernel(const uint6
                                                               uint64_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char zk_dyn_lds[];
     Fr* tab = reinterpret_cast<Fr*>(zk_dyn_lds);   // TAIL_N entries
-    for (uint32_t j = threadIdx.x; j < n; j += MLE_BLOCK) tab[j] = load_fr(in, j);
-    __syncthreads();
-    uint32_t cur = n;
-    for (uint32_t p = 0; p < n_pts; ++p) {
-        const Fr r = fr_from_pts(pts, first_pt + p);
-        const uint32_t half = cur >> 1;
-        // in place: lane j reads (j, j+half) and writes j; no other lane touches index j this round
-        for (uint32_t j = threadIdx.x; j < half; j += MLE_BLOCK) tab[j] = fold_pair(tab[j], tab[j + half], r);
-        __syncthreads();
-        cur = half;
-    }
+    const uint32_t cur = fold_tail_body<MLE_BLOCK>(tab, in, n, n_pts, [&](uint32_t p) { return fr_from_pts(pts, first_pt + p); });
     for (uint32_t j = threadIdx.x; j < cur; j += MLE_BLOCK) store_fr(out, j, tab[j]);
 }
 

@@ -15,6 +15,7 @@
 #include "ctx.hpp"
 #include "host_util.hpp"
 #include "mle_kernels.hpp"
+#include "mle_batch_kernels.hpp"
 #include "sumcheck_kernels.hpp"
 #include "sumcheck_batch_kernels.hpp"
 #include "multifold_kernels.hpp"
@@ -363,6 +364,68 @@ extern "C" int zkhip_mle_evaluation(zkhip_ctx* c, const uint64_t* d_evals, size_
     ZK_HIP(c, hipMemcpyAsync(c->pinned_u64(ZK_PIN_RES), d_res, 32, hipMemcpyDeviceToHost, c->stream));
     ZK_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(h_out, c->pinned_u64(ZK_PIN_RES), 32);
+    return ZKHIP_OK;
+}
+
+// MultilinearTrait::evaluation of `batch` tables of one length, each at its own point (include/zkhip.h; the kernels:
+// mle_batch_kernels.hpp, what is decided here before anything is enqueued: mle_batch_plan.hpp).  A chunk is one upload of its table
+// pointers and points, one launch (two above 2^12 entries), one copy of the results and one synchronisation.
+extern "C" uint32_t zkhip_mle_evaluation_batch_min(size_t n) { return is_pow2(n) ? meb_min_batch(log2_exact(n)) : 0u; }
+
+extern "C" int zkhip_mle_evaluation_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_table_ptrs, size_t n, const uint64_t* h_points,
+                                          size_t n_pts, uint64_t* h_out) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!h_table_ptrs || !h_out || (n_pts && !h_points)) return ZKHIP_ERR_ARG;
+    for (uint32_t b = 0; b < batch; ++b)
+        if (!h_table_ptrs[b]) return ZKHIP_ERR_ARG;
+    if (!is_pow2(n)) return ZKHIP_ERR_SHAPE;
+    if (n_pts != log2_exact(n)) return ZKHIP_ERR_SHAPE;                // assert_eq! evaluation_form.rs:163-167
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;                     // a commit in flight or a split-phase session holds the workspace
+    const uint32_t log_n = (uint32_t)n_pts;
+    const MebPlan plan = meb_plan(log_n, batch);
+    if (plan.regime == MEB_SINGLE) {                                   // the single call's own path, job after job (it activates the device itself)
+        for (uint32_t b = 0; b < batch; ++b)
+            ZK_TRY(zkhip_mle_evaluation(c, h_table_ptrs[b], n, h_points ? h_points + 4 * (size_t)b * n_pts : nullptr, n_pts, h_out + 4 * (size_t)b));
+        return ZKHIP_OK;
+    }
+    ZK_TRY(c->activate());
+    ZK_TRY(c->reserve_ws(plan.ws_bytes));
+    ZK_TRY(c->reserve_msm_pin(0, plan.pin_bytes));
+    char* ws = (char*)c->ws.ptr;
+    char* pin = (char*)c->msm_pin[0].ptr;
+    char* pin_up = pin + meb_align((size_t)plan.chunk * 32);
+    const uint64_t* const* d_tables = (const uint64_t* const*)ws;
+    const uint64_t* d_pts = (const uint64_t*)(ws + plan.o_points);
+    uint64_t* d_res = (uint64_t*)(ws + plan.o_results);
+    uint64_t* d_rec = (uint64_t*)(ws + plan.o_records);
+    void (*resident)(const uint64_t* const*, uint32_t, const uint64_t*, uint32_t, uint64_t*) =
+        plan.lanes == MEB_WIDE_BLOCK ? mle_eval_batch_resident_kernel<(int)MEB_WIDE_BLOCK> : mle_eval_batch_resident_kernel<(int)MEB_BLOCK>;
+    ZK_TRY(c->allow_big_lds(plan.regime == MEB_RESIDENT ? (const void*)resident : (const void*)mle_eval_batch_blocks_kernel, plan.lds_bytes));
+    for (uint32_t i = 0; i < plan.n_chunks; ++i) {
+        const MebChunk ch = meb_chunk(plan, batch, i);
+        // (the previous chunk's upload has ended: every chunk ends in a synchronisation)
+        std::memcpy(pin_up, h_table_ptrs + ch.first, (size_t)ch.count * 8);
+        if (n_pts) std::memcpy(pin_up + plan.o_points, h_points + 4 * (size_t)ch.first * n_pts, (size_t)ch.count * n_pts * 32);
+        ZK_HIP(c, hipMemcpyAsync(ws, pin_up, n_pts ? plan.o_points + (size_t)ch.count * n_pts * 32 : (size_t)ch.count * 8, hipMemcpyHostToDevice, c->stream));
+        if (plan.regime == MEB_RESIDENT) {
+            ProfScope ps(c, "mle_eval_batch", 32.0 * (double)n * ch.count);
+            hipLaunchKernelGGL(resident, dim3(ch.count), dim3(plan.lanes), plan.lds_bytes, c->stream, d_tables, (uint32_t)n, d_pts,
+                               (uint32_t)n_pts, d_res);
+        } else {
+            {
+                ProfScope ps(c, "mle_eval_batch", 32.0 * (double)n * ch.count);
+                hipLaunchKernelGGL(mle_eval_batch_blocks_kernel, dim3(plan.wgs_per_job, ch.count), dim3(plan.lanes), plan.lds_bytes, c->stream, d_tables, plan.h,
+                                   d_pts, (uint32_t)n_pts, d_rec);
+            }
+            hipLaunchKernelGGL(mle_eval_batch_sum_kernel, dim3((ch.count + MLE_BLOCK - 1) / MLE_BLOCK), dim3(MLE_BLOCK), 0, c->stream, (const uint64_t*)d_rec,
+                               plan.records_per_job, ch.count, d_res);
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(pin, d_res, (size_t)ch.count * 32, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        std::memcpy(h_out + 4 * (size_t)ch.first, pin, (size_t)ch.count * 32);
+    }
     return ZKHIP_OK;
 }
 

@@ -96,8 +96,44 @@ class Multilinear:
         N.check(st, "partial_evaluations")
         return Multilinear._wrap(out)
 
+    BATCH_CHUNK = 1024          # csrc/mle_batch_plan.hpp MEB_CHUNK: jobs per launch of the batched evaluation
+
+    @staticmethod
+    def _evaluation_batch(ctx, ptrs, n, pts, call):
+        """`call` (zkhip_mle_evaluation_batch) on len(ptrs) device tables of n entries at pts uint64 [B, n_vars, 4] -> uint64 [B, 4]"""
+        B = len(ptrs)
+        out = np.empty((B, 4), dtype=np.uint64)
+        if pts.shape != (B, n.bit_length() - 1, 4):
+            raise AssertionError("Number of evaluation points must match the number of variables")
+        st = call(ctx.handle, C.c_uint32(B), (C.c_void_p * B)(*ptrs), C.c_size_t(n), pts.ctypes.data_as(C.c_void_p) if pts.size else None,
+                  C.c_size_t(pts.shape[1]), out.ctypes.data_as(C.c_void_p))
+        N.check(st, "Number of evaluation points must match the number of variables")
+        return out
+
+    @staticmethod
+    def evaluation_batch(polys, points):
+        """The evaluations of a list of tables of one length in one call (zkhip_mle_evaluation_batch) -> uint64 [B, 4], row b as from
+        polys[b].evaluation(points[b]).  points: uint64 [B, n_vars, 4], or [n_vars, 4] -- the same point for every table."""
+        polys = [p if isinstance(p, Multilinear) else Multilinear(p) for p in polys]
+        if not polys:
+            return np.empty((0, 4), dtype=np.uint64)
+        evs = [p.evaluations for p in polys]
+        n, nv, dev = evs[0].shape[0], polys[0].n_vars, evs[0].device
+        assert all(e.shape[0] == n for e in evs), "the tables of a batch share their length"
+        assert all(e.device == dev for e in evs), "the tables of a batch live on one device"
+        pts = np.asarray(points, dtype=np.uint64)
+        if pts.ndim < 3:
+            pts = np.broadcast_to(pts.reshape(-1, 4), (len(polys),) + pts.reshape(-1, 4).shape)
+        pts = np.ascontiguousarray(pts)
+        return Multilinear._evaluation_batch(polys[0]._ctx, [e.data_ptr() for e in evs], n, pts, N.lib().zkhip_mle_evaluation_batch)
+
     def evaluation(self, evaluation_points):
-        """evaluation_form.rs:162-175 -> uint64[4] (Montgomery)"""
+        """evaluation_form.rs:162-175 -> uint64[4] (Montgomery); a 3-D uint64 [P, n_vars, 4] argument evaluates this table at P points
+        in one call (zkhip_mle_evaluation_batch, the table's pointer P times) -> uint64 [P, 4]"""
+        if np.ndim(evaluation_points) == 3:
+            pts = np.ascontiguousarray(evaluation_points, dtype=np.uint64)
+            return Multilinear._evaluation_batch(self._ctx, [self.evaluations.data_ptr()] * pts.shape[0], len(self), pts,
+                                                 N.lib().zkhip_mle_evaluation_batch)
         pts = _fr_host(evaluation_points)
         out = np.empty(4, dtype=np.uint64)
         st = N.lib().zkhip_mle_evaluation(self._ctx.handle, N.ptr(self.evaluations), C.c_size_t(len(self)),
