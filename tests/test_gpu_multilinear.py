@@ -221,3 +221,201 @@ def test_add_to_back_front_match_oracle_random(zk, ora):
     import numpy as np
     assert np.array_equal(zk.Multilinear(v).add_to_back(3).to_numpy(), ora.mle_add_to_back(v, 3))
     assert np.array_equal(zk.Multilinear(v).add_to_front(2).to_numpy(), ora.mle_add_to_front(v, 2))
+
+
+# ---- operators, repeats and bytes at size, against the integer model (tests/mle_model.py) -------------------------
+import ctypes as C   # noqa: E402
+import os            # noqa: E402
+import sys           # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mle_model as M   # noqa: E402
+import tables as T      # noqa: E402
+
+
+def same(got, want_ints):
+    """the limbs are the canonical ones of the model's integers"""
+    got = np.asarray(got, dtype=np.uint64).reshape(-1, 4)
+    return bool(T.below_r(got).all()) and np.array_equal(got, M.pack(want_ints))
+
+
+@pytest.mark.parametrize("kind", T.FILLS_ARITH)
+def test_operators_at_2_13_match_the_model(zk, kind):
+    """2^13 entries are 32 workgroups; full-range stored values (tests/tables.py), python integers as the reference"""
+    n = 1 << 13
+    a, b = T.fill(kind, n, 4100), T.fill(T.rotation(T.FILLS_ARITH, kind, 2)[1], n, 4101)
+    ta, tb = T.canonical(a), T.canonical(b)
+    pa, pb = zk.Multilinear(a), zk.Multilinear(b)
+    assert same((pa + pb).to_numpy(), M.elementwise(0, ta, tb))
+    assert same((pa - pb).to_numpy(), M.elementwise(1, ta, tb))
+    assert same((pb - pa).to_numpy(), M.elementwise(1, tb, ta))
+    for s in (tb[5], 0, 1, R - 1):
+        assert same((pa * M.pack([s])[0]).to_numpy(), M.elementwise(2, ta, scalar=s))
+    x, y = zk.Multilinear(a[:64]), zk.Multilinear(b[:128])
+    assert same(x.add_distinct(y).to_numpy(), M.distinct(ta[:64], tb[:128], False))
+    assert same(x.mul_distinct(y).to_numpy(), M.distinct(ta[:64], tb[:128], True))
+    assert same(y.mul_distinct(x).to_numpy(), M.distinct(tb[:128], ta[:64], True))
+    half = zk.Multilinear(a[:n // 4])
+    assert np.array_equal(half.add_to_front(1).to_numpy(), a[np.array(M.repeat(list(range(n // 4)), 0, n))])
+    assert np.array_equal(half.add_to_back(2).to_numpy(), a[np.array(M.repeat(list(range(n // 4)), 2, n))])
+    assert pa.to_bytes() == M.to_bytes(ta)
+
+
+STREAM_STRIDE = 16384 * 256    # mle_grid_stream's cap times MLE_BLOCK: above 2^22 items the library's own grid takes a second step
+
+
+def sampled_rows(n, count=4096):
+    """the first and last row of each stride step of the capped grid, their neighbours, and scattered rows"""
+    import torch
+    edges = {0, 1, n - 2, n - 1}
+    for s in range(STREAM_STRIDE, n, STREAM_STRIDE):
+        edges |= {s - 2, s - 1, s, s + 1}
+    rnd = torch.randint(0, n, (count - len(edges),), generator=torch.Generator().manual_seed(n % 1000003))
+    return torch.cat([torch.tensor(sorted(edges)), rnd])
+
+
+def random_device_table(n, seed):
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.randint(0, 2 ** 62, (n, 4), dtype=torch.int64, device="cuda", generator=g)   # limbs < 2^62: valid residues
+
+
+def rows(t, idx):
+    return t[idx.cuda()].cpu().numpy().view(np.uint64)
+
+
+def test_add_beyond_the_capped_grid(zk):
+    """2^22 + 2^21 entries through the raw ABI (any n): lanes of the second stride step write half of a stride only"""
+    import torch
+    from zk_cryptography_amd import _native as N
+    n = (1 << 22) + (1 << 21)
+    a, b = random_device_table(n, 4201), random_device_table(n, 4202)
+    out = torch.empty_like(a)
+    ctx = N.Context.get(a.device.index)
+    N.check(N.lib().zkhip_mle_elementwise(ctx.handle, C.c_int(0), N.ptr(a), N.ptr(b), None, C.c_size_t(n), C.c_size_t(n), N.ptr(out)), "elementwise")
+    idx = sampled_rows(n)
+    assert same(rows(out, idx), M.elementwise(0, T.canonical(rows(a, idx)), T.canonical(rows(b, idx))))
+
+
+def test_add_distinct_beyond_the_capped_grid(zk):
+    na, nb = 1 << 11, 1 << 12
+    a, b = random_device_table(na, 4203), random_device_table(nb, 4204)
+    out = zk.Multilinear(a).add_distinct(zk.Multilinear(b)).evaluations
+    assert out.shape[0] == na * nb
+    ta, tb = T.canonical(a.cpu().numpy().view(np.uint64)), T.canonical(b.cpu().numpy().view(np.uint64))
+    idx = sampled_rows(na * nb)
+    assert same(rows(out, idx), [(ta[q // nb] + tb[q % nb]) % R for q in idx.tolist()])   # out[i * nb + j] = a[i] + b[j]
+
+
+def test_add_to_back_beyond_the_capped_grid(zk):
+    n_in, v = 1 << 13, 10
+    a = random_device_table(n_in, 4205)
+    out = zk.Multilinear(a).add_to_back(v).evaluations
+    assert out.shape[0] == n_in << v
+    idx = sampled_rows(n_in << v)
+    assert np.array_equal(rows(out, idx), rows(a, idx >> v))
+
+
+def test_to_bytes_beyond_the_capped_grid(zk):
+    import torch
+    from zk_cryptography_amd import _native as N
+    n = (1 << 22) + (1 << 21)
+    a = random_device_table(n, 4206)
+    out = torch.empty(32 * n, dtype=torch.uint8, device="cuda")
+    ctx = N.Context.get(a.device.index)
+    N.check(N.lib().zkhip_mle_to_bytes(ctx.handle, N.ptr(a), C.c_size_t(n), N.ptr(out)), "to_bytes")
+    idx = sampled_rows(n)
+    got = out.view(n, 32)[idx.cuda()].cpu().numpy().tobytes()
+    assert got == M.to_bytes(T.canonical(rows(a, idx)))
+
+
+# ---- DenseUnivariatePolynomial.degree / evaluate where their grids take a second step ---------------------------
+def test_degree_above_the_capped_grid(zk):
+    """2^19 + 257 coefficients: mle_grid's 2048 workgroups stride 2^19, so 257 lanes take a second step"""
+    import torch
+    n, stride = (1 << 19) + 257, 1 << 19
+    one = torch.from_numpy(T.fill("top", 1, 4300).view(np.int64)).cuda()[0]
+    for positions, want in (([], 0), ([0], 0), ([777], 777), ([5, stride - 1], stride - 1), ([stride - 1, stride], stride),
+                            ([3, stride + 5], stride + 5), ([stride + 255, n - 1], n - 1), ([n - 1], n - 1), ([stride + 256, 12], stride + 256)):
+        c = torch.zeros((n, 4), dtype=torch.int64, device="cuda")
+        for at in positions:
+            c[at] = one
+        assert zk.DenseUnivariatePolynomial(c).degree() == want, positions
+
+
+def test_evaluate_2_21_plus_1_sparse(zk):
+    """1025 workgroups of the Horner scan: the top kernel's lanes hold two of them each, the last one"""
+    import torch
+    n = (1 << 21) + 1
+    marks = [0, 7, 8, 2047, 2048, 2 * 2048 - 1, 2 * 2048, 1024 * 2048, n - 1]
+    pos = sorted({m + d for m in marks for d in (-1, 0, 1) if 0 <= m + d < n})
+    vals = T.fill("uniform_r", len(pos), 4400)
+    c = torch.zeros((n, 4), dtype=torch.int64, device="cuda")
+    c[torch.tensor(pos, device="cuda")] = torch.from_numpy(vals.view(np.int64)).cuda()
+    poly = zk.DenseUnivariatePolynomial(c)
+    nonzero = dict(zip(pos, T.canonical(vals)))
+    for z in (0x1234567890ABCDEF1234567890ABCDEF % R, 0, 1, R - 1):
+        assert same(poly.evaluate(M.pack([z])[0]), M.horner_suffix_sparse(nonzero, z, [0])), z
+    assert poly.degree() == n - 1
+
+
+# ---- which kernels fold_chain (csrc/zkhip.hip) launches for which call --------------------------------------------
+FOLD_RECORDS = ("multifold", "multifold_valu", "multifold_small", "fold_tail", "fold")
+EVAL = "evaluation"
+# (log n, number of points, variable_indices or EVAL) -> the records in launch order.  A run of leading zeros is folded k variables at a
+# time while more than 2^12 entries and at least 3 points are left, k = min(log2(entries) - 12, 8, points left), never below 3; the
+# k-variable fold is the matrix-core one ("multifold") for k >= 4 and >= 2^13 outputs, the streaming VALU one (both records) for k = 3
+# there, "multifold_small" below 2^13 outputs.  The rest is one "fold" per point until the indices left are all zero and at most 2^12
+# entries remain: those finish in one "fold_tail".
+DISPATCH = [
+    (16, 3, [0, 0, 0], ["multifold", "multifold_valu"]),                 # k = 3, 2^13 outputs: the VALU streaming shape
+    (17, 4, [0] * 4, ["multifold"]),                                     # k = 4, 2^13 outputs: the matrix cores
+    (20, 5, [0] * 5, ["multifold"]),                                     # k = 8 clipped to the 5 points left
+    (17, 5, [0] * 5, ["multifold_small"]),                               # 2^12 outputs
+    (15, 4, [0] * 4, ["multifold_small", "fold_tail"]),                  # k = 3 of the 4 points, the last in the tail
+    (16, 5, [0] * 5, ["multifold_small", "fold_tail"]),
+    (16, 16, EVAL, ["multifold_small", "fold_tail"]),
+    (21, 11, [0] * 11, ["multifold", "fold", "fold_tail"]),              # k = 8, then 2^13 entries: k = 1 < 3 breaks off
+    (14, 14, EVAL, ["fold", "fold", "fold_tail"]),                       # k = 2 < 3
+    (13, 13, EVAL, ["fold", "fold_tail"]),
+    (12, 12, EVAL, ["fold_tail"]),
+    (10, 2, [0, 0], ["fold_tail"]),
+    (16, 2, [0, 0], ["fold", "fold"]),                                   # fewer than 3 points
+    (13, 4, [0, 0, 0, 1], ["fold"] * 4),                                 # a non-zero index after the zeros: no k-variable fold, no tail
+    (13, 4, [1, 0, 0, 0], ["fold", "fold_tail"]),                        # zeros after it: the tail once 2^12 entries are left
+    (16, 5, [2, 0, 0, 0, 0], ["fold"] * 4 + ["fold_tail"]),              # ... but no k-variable fold, although 2^15 entries remain
+    (12, 3, [11, 5, 0], ["fold"] * 2 + ["fold_tail"]),
+    (14, 0, [], []),                                                     # no point: a copy
+]
+
+
+def fold_records(work):
+    """work() with the library's profile on -> (its result, the names among FOLD_RECORDS in launch order)"""
+    from zk_cryptography_amd import _native as N
+    ctx = N.Context.get()
+    N.check(N.lib().zkhip_profile_enable(ctx.handle, 1), "profile_enable")
+    try:
+        result = work()
+        mx = 64
+        names = C.create_string_buffer(32 * mx)
+        st, sp, cnt = (C.c_double * mx)(), (C.c_double * mx)(), C.c_uint32(0)
+        N.check(N.lib().zkhip_profile_timeline(ctx.handle, C.c_uint32(mx), names, st, sp, C.byref(cnt)), "profile_timeline")
+    finally:
+        N.check(N.lib().zkhip_profile_enable(ctx.handle, 0), "profile_enable")
+    got = [names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode() for i in range(cnt.value)]
+    return result, [g for g in got if g in FOLD_RECORDS]
+
+
+@pytest.mark.parametrize("log_n,n_pts,indices,records", DISPATCH)
+def test_fold_chain_dispatch(zk, ora, log_n, n_pts, indices, records):
+    a = T.fill("uniform_r" if log_n % 2 else "top", 1 << log_n, 4500 + log_n)
+    pts = T.fill("uniform_r", max(n_pts, 1), 4600 + n_pts)[:n_pts]
+    poly = zk.Multilinear(a)
+    if indices == EVAL:
+        got, names = fold_records(lambda: poly.evaluation(pts))
+        want = ora.mle_evaluation(a, pts)
+    else:
+        got, names = fold_records(lambda: poly.partial_evaluations(pts, indices).to_numpy())
+        want = ora.mle_partial_evaluations(a, pts, indices)
+    assert names == records
+    assert np.array_equal(got, want)
