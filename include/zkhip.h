@@ -39,7 +39,7 @@
  *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_mle_evaluation_batch, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
  *     zkhip_circuit_add_mult_mle, zkhip_gkr_prove, zkhip_gkr_prove_circuit, zkhip_gkr_prove_sharded, zkhip_sumcheck_prove,
  *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_multi_composed_prove_batch,
- *     zkhip_mc_begin, zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
+ *     zkhip_mc_begin, zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_kzg_commit_polys, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
  *     zkhip_srs_univariate_g1, zkhip_srs_multilinear_g2, zkhip_srs_univariate_g2, zkhip_srs_fold_levels, zkhip_srs_level_tables,
  *     zkhip_kzg_open, zkhip_kzg_open_tables, zkhip_kzg_open_batch, zkhip_univariate_kzg_open, zkhip_g2_prepare, zkhip_kzg_prepare,
  *     zkhip_pairing, zkhip_pairing_prepared, zkhip_kzg_verify_batch, zkhip_univariate_kzg_verify_batch, zkhip_ntt, zkhip_domain_transform,
@@ -683,6 +683,37 @@ int zkhip_kzg_commit_batch(zkhip_ctx *ctx, const uint64_t *d_points_xy, const ui
  * Returns ZKHIP_ERR_SHAPE when no window widths fit the sort's partitions (more than 64 problems' worth). */
 int zkhip_msm_geometry_info(const size_t *h_offsets, uint32_t n_problems, uint16_t *h_win_first, uint8_t *h_win_bits,
                             uint32_t *h_totals);
+/* `batch` polynomials against ONE SRS in one call (no reference counterpart: the reference commits one polynomial at a time; PLONK's
+ * selector, permutation and wire polynomials and the inputs of a GKR batch are committed this way).  Polynomial b is the device buffer
+ * h_scalar_ptrs[b] (a HOST array of `batch` device pointers; a pointer may repeat) of h_n_scalars[b] scalars, committed against the
+ * first h_n_scalars[b] points of the SRS.  Exactly one of d_points_xy (the plain SRS) and d_table (its shifted-SRS table with header,
+ * zkhip_srs_precompute) is given; d_points_inf as in zkhip_kzg_commit (the flags belong to the POINTS: flag i masks scalar i of every
+ * polynomial).  The scalars are read in place, through a table of the pointers on the device: nothing is copied into a staging area.
+ *   Result: h_out_xy[b][12], h_out_inf[b] are limb for limb what zkhip_kzg_commit -- with d_table: zkhip_kzg_commit_table -- returns
+ *   for (h_scalar_ptrs[b], h_n_scalars[b]): the same group element, so the same affine point.  A polynomial of length 0 is the
+ *   identity (flag 1, coordinates zero; no launch when all are empty); batch == 0 returns ZKHIP_OK and touches nothing; batch == 1 is
+ *   the single call's path.
+ *   Checks run once, before anything is launched or any output is written, with the single call's status codes: require_equal_len and
+ *   some h_n_scalars[b] != n_points -> ZKHIP_ERR_SHAPE; some h_n_scalars[b] > n_points -> ZKHIP_ERR_INDEX; a NULL context, array or
+ *   output, a NULL pointer for a non-empty polynomial, both or neither of d_points_xy / d_table -> ZKHIP_ERR_ARG; a table whose header
+ *   does not match n_points -> ZKHIP_ERR_ARG; the workspace lent (a commit in flight, a split-phase session) -> ZKHIP_ERR_BUSY.  A
+ *   refused call leaves both outputs untouched.
+ *   Routes (csrc/commit_polys_plan.hpp, with the measurements behind them): with a table, no polynomial above 2^12 scalars and at most
+ *   2^13 scalars in the batch, the plane sums of the short commits with the polynomial as a grid dimension -- per chunk of 64 polynomials
+ *   one launch pair per distinct length, one copy, one synchronisation; otherwise chunks of consecutive polynomials as ONE pass of the
+ *   bucket pipeline each (<= 64 problems; every problem its own digit windows and bucket sets, all of them the one set of points; a
+ *   chunk's workspace is at most 512 MiB whatever `batch` is), two chunks in flight: 5-9 x the single commits at 2^12 .. 2^14 scalars
+ *   and B = 64, 1.8 x at 2^16.  Where a shared pass was measured to gain nothing -- a polynomial above 2^16 scalars (2^14 with a
+ *   table), two polynomials against a table -- the call runs the single commits itself, three in flight. */
+int zkhip_kzg_commit_polys(zkhip_ctx *ctx, const uint64_t *d_points_xy, const void *d_table, const uint8_t *d_points_inf,
+                           size_t n_points, uint32_t batch, const uint64_t *const *h_scalar_ptrs, const size_t *h_n_scalars,
+                           int require_equal_len, uint64_t *h_out_xy, uint8_t *h_out_inf);
+/* Diagnostics (host only, no GPU): how zkhip_kzg_commit_polys would serve these lengths (with_table != 0: against a table).
+ *   *h_route: 0 single commits, 1 short route, 2 bucket route;  *h_n_chunks: chunks of the NON-EMPTY polynomials, in order;
+ *   h_chunk_counts[<= batch] (nullable): polynomials per chunk;  h_chunk_ws[<= batch] (nullable): workspace bytes per bucket chunk.
+ * Status codes as the call's checks on the lengths give them (ZKHIP_ERR_INDEX, ZKHIP_ERR_SHAPE). */
+int zkhip_commit_polys_plan_info(size_t n_points, const size_t *h_n_scalars, uint32_t batch, int with_table, uint32_t *h_route,
+                                 uint32_t *h_n_chunks, uint32_t *h_chunk_counts, size_t *h_chunk_ws);
 /* SRS generation on the device, G1 side (the G2 side: zkhip_srs_multilinear_g2 / zkhip_srs_univariate_g2 below).
  *   multilinear: TrustedSetup::generate_powers_of_tau_in_g1 (kzg/src/trusted_setup.rs:25-35):
  *                point i = G * prod_j (bit_j(i) ? tau_j : 1 - tau_j), hypercube bits MSB first; 2^n_vars points.

@@ -598,6 +598,21 @@ inline G1Affine commit_impl(const TrustedSetup& srs, const uint64_t* d_scalars, 
     g.infinity = inf != 0;
     return g;
 }
+// a batch of polynomials against the one SRS in one call (zkhip_kzg_commit_polys): each result what commit_impl returns for that polynomial
+inline std::vector<G1Affine> commit_batch_impl(const TrustedSetup& srs, const std::vector<const uint64_t*>& d_scalars, const std::vector<size_t>& lens, int require_equal) {
+    const size_t b = d_scalars.size();
+    std::vector<G1Affine> out(b);
+    if (b == 0) return out;
+    std::vector<uint64_t> xy(12 * b);
+    std::vector<uint8_t> inf(b);
+    int st = zkhip_kzg_commit_polys(ctx(), srs.table() ? nullptr : srs.points(), srs.table(), srs.inf(), srs.len(), (uint32_t)b, d_scalars.data(), lens.data(),
+                                    require_equal, xy.data(), inf.data());
+    if (st == ZKHIP_ERR_SHAPE) throw Panic("The length of powers_of_tau_in_g1 and the length of the evaluations of the polynomial should tally!");
+    if (st == ZKHIP_ERR_INDEX) throw std::out_of_range("index out of bounds: the len of powers_of_tau_in_g1 is smaller than the polynomial");
+    check(st, "kzg_commit_polys");
+    for (size_t i = 0; i < b; ++i) { std::memcpy(out[i].xy, &xy[12 * i], 96); out[i].infinity = inf[i] != 0; }
+    return out;
+}
 // MultilinearKZG::commitment over (scalars, SRS) sharded by low index bits: this rank's shards in, the whole commitment out on every rank
 inline G1Affine commit_sharded(const TrustedSetup& srs_shard, const uint64_t* d_scalars, size_t n, int require_equal, const Comm& comm) {
     G1Affine g; uint8_t inf = 0;
@@ -615,6 +630,13 @@ struct MultilinearKZGProof {                                                    
 };
 struct MultilinearKZG {
     static G1Affine commitment(const Multilinear& poly, const TrustedSetup& srs) { return commit_impl(srs, poly.device(), poly.len(), 1); }   // multilinear_kzg.rs:33-48
+    // `commitment` of every polynomial against the one SRS in one call; a polynomial of another length than the SRS is `commitment`'s panic, before anything is committed
+    static std::vector<G1Affine> commitment_batch(const std::vector<Multilinear>& polys, const TrustedSetup& srs) {
+        std::vector<const uint64_t*> ptrs;
+        std::vector<size_t> lens;
+        for (const Multilinear& p : polys) { ptrs.push_back(p.device()); lens.push_back(p.len()); }
+        return commit_batch_impl(srs, ptrs, lens, 1);
+    }
     static G1Affine commitment_sharded(const Multilinear& poly_shard, const TrustedSetup& srs_shard, const Comm& comm) { return commit_sharded(srs_shard, poly_shard.device(), poly_shard.len(), 1, comm); }
     static MultilinearKZGProof open(const Multilinear& poly, const std::vector<Fr>& evaluation_points, const TrustedSetup& srs) {             // :50-88
         MultilinearKZGProof pr;
@@ -683,6 +705,13 @@ struct UnivariateKZG {
         return ok != 0;
     }
     static G1Affine commitment(const DenseUnivariatePolynomial& poly, const TrustedSetup& srs) { return commit_impl(srs, poly.dev->u64(), poly.n, 0); }   // :37-58
+    // `commitment` of every polynomial (of any lengths) against the one SRS in one call; the zero polynomial commits to the identity
+    static std::vector<G1Affine> commitment_batch(const std::vector<DenseUnivariatePolynomial>& polys, const TrustedSetup& srs) {
+        std::vector<const uint64_t*> ptrs;
+        std::vector<size_t> lens;
+        for (const DenseUnivariatePolynomial& p : polys) { ptrs.push_back(p.n ? p.dev->u64() : nullptr); lens.push_back(p.n); }
+        return commit_batch_impl(srs, ptrs, lens, 0);
+    }
 };
 
 // ---- circuit::{Gate, CircuitLayer, Circuit}, gkr::GKRProtocol::prove -----------------------------------------------------

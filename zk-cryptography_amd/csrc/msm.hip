@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "commit_polys_plan.hpp"
 #include "ctx.hpp"
 #include "host_util.hpp"
 #include "host_g1.hpp"
@@ -38,20 +39,20 @@ using namespace zk;
 //                  sparse (a 3-bit top window put an eighth of all points into each of 4 buckets: the heavy-bucket passes, 0.6 ms) and
 //                  all problems share ONE pass of every kernel (MultilinearKZG::open at 2^20: twenty problems, ~0.45 M buckets).
 // the geometries of the last few shapes (an opening builds its twenty-problem geometry twice per call otherwise: ~0.1 ms of host time each)
-static int msm_geometry(const MsmProblems& pr, bool shared, size_t table_stride, std::shared_ptr<const MsmGeometry>* out) {
-    struct Entry { MsmProblems pr; bool shared; size_t stride; std::shared_ptr<const MsmGeometry> geo; };
+static int msm_geometry(const MsmProblems& pr, bool shared, size_t table_stride, std::shared_ptr<const MsmGeometry>* out, bool one_points = false) {
+    struct Entry { MsmProblems pr; bool shared; size_t stride; std::shared_ptr<const MsmGeometry> geo; bool one_points; };
     static std::mutex mu;
     static std::vector<Entry> cache;
     std::lock_guard<std::mutex> lk(mu);
     for (const Entry& e : cache)
-        if (e.shared == shared && e.stride == table_stride && e.pr.n == pr.n && std::memcmp(e.pr.off, pr.off, sizeof(uint32_t) * (pr.n + 1)) == 0) {
+        if (e.shared == shared && e.one_points == one_points && e.stride == table_stride && e.pr.n == pr.n && std::memcmp(e.pr.off, pr.off, sizeof(uint32_t) * (pr.n + 1)) == 0) {
             *out = e.geo;
             return ZKHIP_OK;
         }
     auto g = std::make_shared<MsmGeometry>();
-    ZK_TRY(msm_build_geometry(pr, shared, table_stride, *g));
+    ZK_TRY(msm_build_geometry(pr, shared, table_stride, *g, one_points));
     if (cache.size() >= 8) cache.erase(cache.begin());
-    cache.push_back({pr, shared, table_stride, g});
+    cache.push_back({pr, shared, table_stride, g, one_points});
     *out = g;
     return ZKHIP_OK;
 }
@@ -69,11 +70,19 @@ struct MsmPending {
     ZkLoan ws_loan;     // a commit in flight (zkhip_kzg_commit_begin) holds the workspace until it has ended
 };
 void MsmPendingDelete::operator()(MsmPending* p) const { delete p; }
+// ONE SET OF POINTS (zkhip_kzg_commit_polys): the problems of the pass are polynomials of their own -- device buffers read in place
+// through `ptrs`, d_scalars is not read -- against the first points of ONE SRS (d_points_xy / d_table, d_points_inf: the points' flags);
+// n_conv: the points the pass converts (the longest problem; the workspace holds n_conv x 128 bytes of them, not one copy per problem);
+// geo: the geometry the planner built for the chunk (mode "one set of points"), or null to build it here
+struct MsmPolys { MsmPtrTable ptrs; size_t n_conv; std::shared_ptr<const MsmGeometry> geo; };
+static_assert(CPP_SORT_TILE == (size_t)SORT_TILE && CPP_COUNT_BINS == (size_t)MSM_COUNT_BINS && CPP_HEAVY_REC == (size_t)MSM_HEAVY_REC &&
+              CPP_HEAVY_LEVELS == (size_t)MSM_HEAVY_LEVELS && CPP_HEAVY_REC_BYTES == sizeof(MsmHeavyRec) && CPP_OVERFLOW_BYTES == sizeof(MsmOverflow),
+              "commit_polys_plan.hpp sizes a chunk's workspace with the kernels' constants");
 static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t* d_points_inf, const uint64_t* d_scalars, size_t n,
                        const MsmProblems& pr_in, const uint32_t* d_table, size_t table_stride, size_t ws_off, int slot, MsmPending* pend,
-                       size_t* ws_used) {
-    std::shared_ptr<const MsmGeometry> geo_p;
-    ZK_TRY(msm_geometry(pr_in, d_table != nullptr, table_stride, &geo_p));
+                       size_t* ws_used, const MsmPolys* polys = nullptr) {
+    std::shared_ptr<const MsmGeometry> geo_p = polys ? polys->geo : nullptr;
+    if (!geo_p) ZK_TRY(msm_geometry(pr_in, d_table != nullptr, table_stride, &geo_p, polys != nullptr));
     const MsmGeometry& geo = *geo_p;
     MsmProblems pr = pr_in;
     std::memcpy(pr.win_first, geo.win_first, sizeof(pr.win_first));
@@ -95,7 +104,8 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
     const size_t o_pcnt = o_wgc + al(n_wgs * pl.n_parts * 4);
     const size_t o_poff = o_pcnt + al((pl.n_parts + 1) * 4);
     const size_t o_points = o_poff + al((pl.n_parts + 1) * 4);          // SRS in the internal 28-bit-limb layout
-    const size_t o_buckets = o_points + al(d_table ? 0 : n * 128);
+    const size_t n_conv = polys ? polys->n_conv : n;                    // one set of points: the longest problem's worth, once
+    const size_t o_buckets = o_points + al(d_table ? 0 : n_conv * 128);
     const size_t o_segs = o_buckets + al(n_buckets * 256);
     const size_t o_sega = o_segs + al(n_segments * 256);
     const size_t o_terms = o_sega + al(n_segments * 256);
@@ -158,19 +168,22 @@ static int msm_enqueue(zkhip_ctx* c, const uint64_t* d_points_xy, const uint8_t*
         pl.rcwg_set = (const uint16_t*)(dev + b_wins + b_sets + b_part);
         pl.termwg_set = (const uint16_t*)(dev + b_wins + b_sets + b_part + b_rcwg);
     }
-    const int grid_n = (int)std::min<size_t>((n + MSM_BLOCK - 1) / MSM_BLOCK, 256 * 8);
+    const int grid_n = (int)std::min<size_t>((n_conv + MSM_BLOCK - 1) / MSM_BLOCK, 256 * 8);
     if (!d_table) {
-        ProfScope ps(c, "msm_convert_points", 224.0 * (double)n);
-        hipLaunchKernelGGL(msm_convert_points_kernel, dim3(grid_n), dim3(MSM_BLOCK), 0, c->stream, d_points_xy, n, (uint32_t*)(ws + o_points));
+        ProfScope ps(c, "msm_convert_points", 224.0 * (double)n_conv);
+        hipLaunchKernelGGL(msm_convert_points_kernel, dim3(grid_n), dim3(MSM_BLOCK), 0, c->stream, d_points_xy, n_conv, (uint32_t*)(ws + o_points));
     }
     {   // two-level counting sort of the (point, window) pairs by bucket; also yields counts[] and offsets[]
         ProfScope ps(c, "msm_sort", 32.0 * (double)n);
-        hipLaunchKernelGGL(msm_sort_count_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, d_scalars, d_points_inf, n, pl, pr, wg_counts);
+        if (polys) hipLaunchKernelGGL(msm_sort_count_ptrs_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, polys->ptrs, d_points_inf, n, pl, pr, wg_counts);
+        else hipLaunchKernelGGL(msm_sort_count_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, d_scalars, d_points_inf, n, pl, pr, wg_counts);
         hipLaunchKernelGGL(msm_sort_bases_kernel, dim3((pl.n_parts + MSM_BLOCK / 64 - 1) / (MSM_BLOCK / 64)), dim3(MSM_BLOCK), 0, c->stream, wg_counts,
                            (uint32_t)n_wgs, pl.n_parts, part_count);
         hipLaunchKernelGGL(msm_sort_part_scan_kernel, dim3(1), dim3(1024), 0, c->stream, part_count, pl.n_parts, part_off);
-        hipLaunchKernelGGL(msm_sort_scatter_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, d_scalars, d_points_inf, n, pl, pr,
-                           wg_counts, part_off, items);
+        if (polys) hipLaunchKernelGGL(msm_sort_scatter_ptrs_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, polys->ptrs, d_points_inf, n, pl, pr,
+                                      wg_counts, part_off, items);
+        else hipLaunchKernelGGL(msm_sort_scatter_kernel, dim3((unsigned)n_wgs), dim3(MSM_BLOCK), 0, c->stream, d_scalars, d_points_inf, n, pl, pr,
+                                wg_counts, part_off, items);
         // level 2 also takes the histogram of the bucket counts (the order pass) and files the heavy buckets: both cleared here
         ZK_HIP(c, hipMemsetAsync(bins, 0, (size_t)(o_sorted - o_bins), c->stream));      // bins + MsmOverflow
         hipLaunchKernelGGL(msm_sort_local_kernel, dim3(pl.n_parts), dim3(SORT_LOCAL_BLOCK), 0, c->stream, items, part_off, pl, sorted, counts, offsets,
@@ -1151,6 +1164,268 @@ int zk_msm_commit_batch(zkhip_ctx* c, const void* d_table_with_header, const uin
     return ZKHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// zkhip_kzg_commit_polys: a BATCH of polynomials against one SRS
+// ---------------------------------------------------------------------------------------
+// A lone commit of 2^13 .. 2^16 scalars is ~1 ms of latency on a mostly idle chip -- seventeen launches, reduction passes that are chains
+// of point additions, a host epilogue --, whatever the chip could do beside.  B polynomials against ONE SRS share all of it: their
+// (point, window) pairs fill ONE pass of every kernel of the bucket pipeline (the geometry mode "one set of points": every problem its
+// own windows and bucket sets, the point base in the windows' entry_off, the scalars read in place through a pointer table), and their
+// host epilogues run side by side on the context's pool.  What serves a batch, and how it is cut into chunks, is decided by
+// commit_polys_plan.hpp; the routes are below.  Every route delivers the group elements of the single commits, so their affine points.
+static_assert(CPP_SMALL_MAX == MSM_SMALL_MAX, "commit_polys_plan.hpp routes by the short path's limit");
+static int commit_polys_plan(size_t n_points, const size_t* len, uint32_t batch, bool table, std::shared_ptr<const CppPlan>* out) {
+    // the plans of the last few shapes (a plan builds its chunks' geometries: ~0.1 ms of host time per distinct chunk shape)
+    struct Entry { size_t n_points; bool table; std::vector<size_t> len; std::shared_ptr<const CppPlan> plan; };
+    static std::mutex mu;
+    static std::vector<Entry> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    for (const Entry& e : cache)
+        if (e.n_points == n_points && e.table == table && e.len.size() == batch && std::equal(e.len.begin(), e.len.end(), len)) {
+            *out = e.plan;
+            return e.plan->status;
+        }
+    auto p = std::make_shared<CppPlan>(cpp_plan(n_points, len, batch, table, msm_small_on()));
+    if (cache.size() >= 4) cache.erase(cache.begin());
+    cache.push_back({n_points, table, std::vector<size_t>(len, len + batch), p});
+    *out = p;
+    return p->status;
+}
+// one polynomial on the single call's path, behind its checks (d_table: behind the checked header)
+static int commit_polys_one(zkhip_ctx* c, const uint64_t* d_points_xy, const uint32_t* d_table, const uint8_t* d_points_inf, size_t n_points,
+                            const uint64_t* d_scalars, size_t n, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    if (!d_table) return msm_commit(c, d_points_xy, d_points_inf, d_scalars, n, h_out_xy, h_out_inf);
+    if (msm_small_on() && n <= MSM_SMALL_MAX) return msm_commit_small(c, d_table, n_points, d_points_inf, d_scalars, n, h_out_xy, h_out_inf);
+    MsmProblems one = {};
+    one.n = 1;
+    one.off[1] = (uint32_t)n;
+    return msm_commit_multi(c, nullptr, d_points_inf, d_scalars, n, one, h_out_xy, h_out_inf, d_table, n_points);
+}
+// SHORT route: a chunk's polynomials in the order of their lengths; every run of one length (a CLASS) is one launch of the plane sums
+// with the polynomial as grid.z and one of the reduce, all classes of the chunk in front of ONE copy and ONE synchronisation; then the
+// weighted sums on the pool (zk_msm_commit_batch does the same for PLONK's fixed-stride layout).  A class's slots: kzg_open_small_batch's
+// rule -- ~2 waves per SIMD over the whole chunk, and no lane walks more than OPEN_BATCH_LANE_PAIRS pairs.
+// ptrs / len / where: the non-empty polynomials, their lengths and their places in the outputs.
+static int commit_polys_short(zkhip_ctx* c, const uint32_t* d_table, const uint8_t* d_points_inf, size_t n_points, const CppPlan& plan,
+                              const uint64_t* const* ptrs, const size_t* len, const uint32_t* where, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    const MsmLevelWidths lw = msm_table_widths(n_points);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    for (const CppChunk& ch : plan.chunks) {
+        static_assert(CPP_SMALL_CHUNK <= (uint32_t)MSM_MAX_PROBLEMS, "a chunk's pointers are one MsmPtrTable");
+        uint32_t order[CPP_SMALL_CHUNK];
+        for (uint32_t k = 0; k < ch.count; ++k) order[k] = ch.first + k;
+        std::stable_sort(order, order + ch.count, [&](uint32_t x, uint32_t y) { return len[x] < len[y]; });
+        MsmPtrTable pt = {};
+        for (uint32_t k = 0; k < ch.count; ++k) pt.p[k] = ptrs[order[k]];
+        struct Class { uint32_t first, count, slots; size_t part_off; };
+        std::vector<Class> classes;
+        const size_t budget = std::max<size_t>(1, 2048 / lw.hi / ch.count);
+        size_t part_bytes = 0;
+        for (uint32_t k = 0; k < ch.count;) {
+            uint32_t e = k + 1;
+            while (e < ch.count && len[order[e]] == len[order[k]]) ++e;
+            const size_t pairs = len[order[k]] * lw.W, chunks = (pairs + 63) / 64, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
+            const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(budget, capped)));
+            classes.push_back({k, e - k, slots, part_bytes});
+            part_bytes += al((size_t)(e - k) * lw.hi * slots * 256);
+            k = e;
+        }
+        const size_t terms_bytes = (size_t)ch.count * lw.hi * 192;
+        ZK_TRY(c->reserve_ws(part_bytes + al(terms_bytes)));
+        ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
+        uint64_t* d_terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
+        for (const Class& cl : classes) {
+            MsmSmallArgs a = {};
+            a.table = d_table; a.inf = d_points_inf; a.nprob = 1; a.planes = lw.hi; a.total_slots = cl.slots;
+            a.partials = (uint32_t*)((char*)c->ws.ptr + cl.part_off);
+            a.terms = d_terms + 24 * (size_t)cl.first * lw.hi;
+            a.n[0] = (uint32_t)len[order[cl.first]]; a.stride[0] = (uint32_t)n_points; a.W[0] = lw.W; a.hi[0] = lw.hi; a.n_hi[0] = lw.n_hi;
+            a.slot_first[1] = cl.slots;
+            {
+                ProfScope ps(c, "commit_polys_planes", 128.0 * (double)a.n[0] * cl.count);
+                hipLaunchKernelGGL(msm_small_commit_polys_planes_kernel, dim3(cl.slots, lw.hi, cl.count), dim3(64), 0, c->stream, a, pt, cl.first);
+            }
+            {
+                ProfScope ps(c, "commit_polys_reduce", 0.0);
+                hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(lw.hi, 1, cl.count), dim3(64), 0, c->stream, a);
+            }
+        }
+        ZK_HIP(c, hipGetLastError());
+        ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, d_terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        const char* pin = (const char*)c->msm_pin[0].ptr;
+        auto finish = [&](uint32_t k) {                                  // the weighted sum of polynomial order[k]'s plane sums: <= 20 doublings
+            std::vector<zkhost::Xyzz> pts(lw.hi);
+            std::vector<uint32_t> exps(lw.hi);
+            for (uint32_t t = 0; t < lw.hi; ++t) {
+                std::memcpy(&pts[t], pin + 192 * ((size_t)k * lw.hi + t), 192);
+                exps[t] = t;
+            }
+            const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
+            const size_t o = where[order[k]];
+            h_out_inf[o] = zkhost::xyzz_to_affine(res, h_out_xy + 12 * o) ? 0 : 1;
+        };
+        ZkHostPool* pool = ch.count > 1 ? c->pool() : nullptr;
+        if (!pool) {
+            for (uint32_t k = 0; k < ch.count; ++k) finish(k);
+        } else {
+            pool->run(ch.count, [&](unsigned k) { finish(k); });
+        }
+    }
+    return ZKHIP_OK;
+}
+// BUCKET route: chunk after chunk as one pass of the bucket pipeline each, all on the caller's stream, TWO in flight -- a region of the
+// workspace, a result slot and a device copy of the geometry tables each -- so that the host epilogues of a chunk (one weighted sum per
+// problem, on the pool) run beside the passes of the next.
+static int commit_polys_bucket(zkhip_ctx* c, const uint64_t* d_points_xy, const uint32_t* d_table, const uint8_t* d_points_inf, size_t n_points,
+                               const CppPlan& plan, const uint64_t* const* ptrs, const uint32_t* where, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    size_t region = 0;
+    for (const CppChunk& ch : plan.chunks) region = std::max(region, (ch.ws_bytes + 4095) & ~(size_t)4095);
+    const size_t n_chunks = plan.chunks.size();
+    ZK_TRY(c->reserve_ws(region * std::min<size_t>(2, n_chunks)));      // once, up front: growing it later would move it under the chunk in flight
+    MsmPending pend[2];
+    int pend_chunk[2] = {-1, -1};
+    uint64_t xy[12 * MSM_MAX_PROBLEMS];
+    uint8_t inf[MSM_MAX_PROBLEMS];
+    auto finish_slot = [&](int sl) -> int {
+        if (pend_chunk[sl] < 0) return ZKHIP_OK;
+        const CppChunk& ch = plan.chunks[pend_chunk[sl]];
+        pend_chunk[sl] = -1;
+        ZK_TRY(msm_finish(c, pend[sl], xy, inf));
+        for (uint32_t j = 0; j < ch.count; ++j) {                        // (empty polynomials may lie between a chunk's: the outputs are not one run)
+            const size_t o = where[ch.first + j];
+            std::memcpy(h_out_xy + 12 * o, xy + 12 * j, 96);
+            h_out_inf[o] = inf[j];
+        }
+        return ZKHIP_OK;
+    };
+    int rc = ZKHIP_OK;
+    for (size_t k = 0; k < n_chunks && rc == ZKHIP_OK; ++k) {
+        const CppChunk& ch = plan.chunks[k];
+        const int sl = (int)(k & 1);
+        if ((rc = finish_slot(sl)) != ZKHIP_OK) break;                   // chunk k - 2 used this region, result slot and table copy
+        MsmPolys polys = {};
+        for (uint32_t j = 0; j < ch.count; ++j) polys.ptrs.p[j] = ptrs[ch.first + j];
+        polys.n_conv = ch.n_conv;
+        polys.geo = ch.geo;
+        size_t used = 0;
+        rc = msm_enqueue(c, nullptr, nullptr, nullptr, ch.n_total, ch.pr, d_table, n_points, 0, 0, nullptr, &used, &polys);
+        if (rc == ZKHIP_OK && used > region) rc = ZKHIP_ERR_SHAPE;       // (the planner's carve-up is msm_enqueue's: never)
+        if (rc == ZKHIP_OK)
+            rc = msm_enqueue(c, d_points_xy, d_points_inf, nullptr, ch.n_total, ch.pr, d_table, n_points, (size_t)sl * region, sl, &pend[sl], nullptr, &polys);
+        if (rc == ZKHIP_OK) pend_chunk[sl] = (int)k;
+    }
+    // the chunks still in flight, the older first; both are drained even after an error
+    for (int q = 0; q < 2; ++q) {
+        const int sl = (int)((n_chunks + q) & 1);
+        const int r2 = finish_slot(sl);
+        if (rc == ZKHIP_OK) rc = r2;
+    }
+    if (rc != ZKHIP_OK) hipStreamSynchronize(c->stream);
+    return rc;
+}
+// SINGLE route: the shapes a batched route does not serve faster (commit_polys_plan.hpp) run as the single commits a caller could issue
+// himself, the way that serves him best -- the short commits against a table one after another (zkhip_kzg_commit_table's short path:
+// a commit in flight always takes the bucket pipeline), everything else three in flight (zkhip_kzg_commit_begin / _end), which takes
+// and returns the workspace loan inside the call.  One polynomial is the single call's path.
+static int commit_polys_single(zkhip_ctx* c, const uint64_t* d_points_xy, const void* d_table_with_header, const uint32_t* d_table,
+                               const uint8_t* d_points_inf, size_t n_points, uint32_t m, const uint64_t* const* ptrs, const size_t* len,
+                               const uint32_t* where, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    std::vector<uint32_t> rest;
+    for (uint32_t k = 0; k < m; ++k) {
+        if (m > 1 && !(d_table && msm_small_on() && len[k] <= MSM_SMALL_MAX)) { rest.push_back(k); continue; }
+        ZK_TRY(commit_polys_one(c, d_points_xy, d_table, d_points_inf, n_points, ptrs[k], len[k], h_out_xy + 12 * (size_t)where[k], h_out_inf + where[k]));
+    }
+    if (rest.size() == 1) {
+        const uint32_t k = rest[0];
+        return commit_polys_one(c, d_points_xy, d_table, d_points_inf, n_points, ptrs[k], len[k], h_out_xy + 12 * (size_t)where[k], h_out_inf + where[k]);
+    }
+    struct InFlight { uint32_t k, ticket; };
+    InFlight pend[zkhip_ctx::ASYNC_SLOTS];
+    int n_pend = 0, rc = ZKHIP_OK;
+    auto end_oldest = [&](bool deliver) -> int {
+        const InFlight f = pend[0];
+        for (int q = 1; q < n_pend; ++q) pend[q - 1] = pend[q];
+        --n_pend;
+        return zkhip_kzg_commit_end(c, f.ticket, deliver ? h_out_xy + 12 * (size_t)where[f.k] : nullptr, deliver ? h_out_inf + where[f.k] : nullptr);
+    };
+    for (size_t q = 0; q < rest.size() && rc == ZKHIP_OK; ++q) {
+        const uint32_t k = rest[q];
+        uint32_t ticket = 0;
+        for (;;) {
+            if (n_pend == zkhip_ctx::ASYNC_SLOTS && (rc = end_oldest(true)) != ZKHIP_OK) break;
+            rc = zkhip_kzg_commit_begin(c, d_points_xy, d_table_with_header, d_points_inf, n_points, ptrs[k], len[k], 0, &ticket);
+            if (rc != ZKHIP_ERR_BUSY || n_pend == 0) break;
+            if ((rc = end_oldest(true)) != ZKHIP_OK) break;              // a larger commit than the ones in flight: those end first
+        }
+        if (rc == ZKHIP_OK) pend[n_pend++] = InFlight{k, ticket};
+    }
+    while (n_pend) {                                                     // the rest; after an error they are drained, not delivered
+        const int r2 = end_oldest(rc == ZKHIP_OK);
+        if (rc == ZKHIP_OK) rc = r2;
+    }
+    return rc;
+}
+// the checks on the lengths, shared by the call and its diagnostic
+static int commit_polys_check_lengths(size_t n_points, const size_t* h_n_scalars, uint32_t batch, int require_equal_len) {
+    if (require_equal_len) {
+        for (uint32_t b = 0; b < batch; ++b) if (h_n_scalars[b] != n_points) return ZKHIP_ERR_SHAPE;     // multilinear_kzg.rs:36-41
+    }
+    for (uint32_t b = 0; b < batch; ++b) if (h_n_scalars[b] > n_points) return ZKHIP_ERR_INDEX;         // univariate_kzg.rs:53
+    return ZKHIP_OK;
+}
+extern "C" int zkhip_kzg_commit_polys(zkhip_ctx* c, const uint64_t* d_points_xy, const void* d_table_with_header, const uint8_t* d_points_inf,
+                                      size_t n_points, uint32_t batch, const uint64_t* const* h_scalar_ptrs, const size_t* h_n_scalars,
+                                      int require_equal_len, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!h_scalar_ptrs || !h_n_scalars || !h_out_xy || !h_out_inf || (!d_points_xy == !d_table_with_header)) return ZKHIP_ERR_ARG;
+    ZK_TRY(commit_polys_check_lengths(n_points, h_n_scalars, batch, require_equal_len));
+    // the non-empty polynomials and their places in the outputs
+    std::vector<const uint64_t*> ptrs;
+    std::vector<size_t> len;
+    std::vector<uint32_t> where;
+    for (uint32_t b = 0; b < batch; ++b) {
+        if (h_n_scalars[b] == 0) continue;
+        if (!h_scalar_ptrs[b]) return ZKHIP_ERR_ARG;
+        ptrs.push_back(h_scalar_ptrs[b]); len.push_back(h_n_scalars[b]); where.push_back(b);
+    }
+    const uint32_t m = (uint32_t)ptrs.size();
+    const uint32_t* d_table = nullptr;
+    std::shared_ptr<const CppPlan> plan;
+    if (m) {
+        ZK_TRY(commit_polys_plan(n_points, len.data(), m, d_table_with_header != nullptr, &plan));
+        if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
+        ZK_TRY(c->activate());
+        if (d_table_with_header) {
+            int trc = ZKHIP_OK;
+            d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);       // built for THESE n_points, with the widths used below?
+            if (!d_table) return trc;
+        }
+    }
+    for (uint32_t b = 0; b < batch; ++b)
+        if (h_n_scalars[b] == 0) { std::memset(h_out_xy + 12 * (size_t)b, 0, 96); h_out_inf[b] = 1; }       // P::G1::default()
+    if (!m) return ZKHIP_OK;
+    if (plan->route == CPP_SHORT) return commit_polys_short(c, d_table, d_points_inf, n_points, *plan, ptrs.data(), len.data(), where.data(), h_out_xy, h_out_inf);
+    if (plan->route == CPP_BUCKET) return commit_polys_bucket(c, d_points_xy, d_table, d_points_inf, n_points, *plan, ptrs.data(), where.data(), h_out_xy, h_out_inf);
+    return commit_polys_single(c, d_points_xy, d_table_with_header, d_table, d_points_inf, n_points, m, ptrs.data(), len.data(), where.data(), h_out_xy, h_out_inf);
+}
+extern "C" int zkhip_commit_polys_plan_info(size_t n_points, const size_t* h_n_scalars, uint32_t batch, int with_table, uint32_t* h_route,
+                                            uint32_t* h_n_chunks, uint32_t* h_chunk_counts, size_t* h_chunk_ws) {
+    if (!h_n_scalars || !h_route || !h_n_chunks) return ZKHIP_ERR_ARG;
+    ZK_TRY(commit_polys_check_lengths(n_points, h_n_scalars, batch, 0));
+    std::vector<size_t> len;
+    for (uint32_t b = 0; b < batch; ++b) if (h_n_scalars[b]) len.push_back(h_n_scalars[b]);
+    const CppPlan plan = cpp_plan(n_points, len.data(), (uint32_t)len.size(), with_table != 0, msm_small_on());
+    ZK_TRY(plan.status);
+    *h_route = (uint32_t)plan.route;
+    *h_n_chunks = (uint32_t)plan.chunks.size();
+    for (size_t k = 0; k < plan.chunks.size(); ++k) {
+        if (h_chunk_counts) h_chunk_counts[k] = plan.chunks[k].count;
+        if (h_chunk_ws) h_chunk_ws[k] = plan.chunks[k].ws_bytes;
+    }
+    return ZKHIP_OK;
+}
 
 static int kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, const uint64_t* h_points, size_t n_eval_points,
                           const uint64_t* d_points_xy, const uint8_t* d_points_inf, size_t n_points, const uint64_t* d_folded_xy,
@@ -1167,7 +1442,7 @@ static int kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h
         return kzg_open_small_batch(c, batch, h_eval_ptrs, n, n_vars, h_points, d_folded_inf, (const uint32_t*)d_level_tables, h_evaluations,
                                     h_proofs_xy, h_proofs_inf, chunk_max);
     // every other size and configuration: one after another through the single opening (several openings in ONE bucket-pipeline commit
-    // would need a point base per problem in msm_enqueue's sort keys: not built)
+    // need a point base per problem in msm_enqueue's sort keys: zkhip_kzg_commit_polys has it now; the openings do not go through it yet)
     for (uint32_t b = 0; b < batch; ++b)
         ZK_TRY(kzg_open_one(c, h_eval_ptrs[b], n, n_vars, h_points + 4 * (size_t)n_vars * b, d_points_xy, d_points_inf, d_folded_xy, d_folded_inf,
                             d_level_tables, h_evaluations + 4 * (size_t)b, h_proofs_xy + 12 * (size_t)n_vars * b, h_proofs_inf + (size_t)n_vars * b));

@@ -126,9 +126,14 @@ inline MsmLevelWidths msm_level_table_widths(size_t nj, size_t batch_total) {
 // 2^19 buckets at 2^20 points, wider than the size below 2^19 points (a small commit is as long as its longest bucket list and its
 // reduction passes: 2^19 buckets for 2^12 points were a millisecond of empty reduction).
 inline MsmLevelWidths msm_table_widths(size_t n_points) { return msm_level_table_widths(n_points, n_points); }
-inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t table_stride, int delta, MsmGeometry& g);
-inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_stride, MsmGeometry& g);
-inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_stride, MsmGeometry& g) {
+// ONE SET OF POINTS (one_points; zkhip_kzg_commit_polys: B polynomials against one SRS): the problems' scalars lie end to end LOGICALLY --
+// problem j owns the indices [off[j], off[j+1]) of the pass -- but scalar i of problem j belongs to point i - off[j] of the one SRS, so
+// every window of problem j carries the point base in its entry_off: -off[j] mod 2^32 with plain points (widths as for several
+// problems), w * table_stride - off[j] with the shifted-SRS table (every problem the widths msm_table_widths(table_stride) and one
+// bucket set of its own: the table's layout fixes them).  Nothing else differs: a problem's windows and sets are its own.
+inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t table_stride, int delta, MsmGeometry& g, bool one_points = false);
+inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_stride, MsmGeometry& g, bool one_points = false);
+inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_stride, MsmGeometry& g, bool one_points) {
     // widths log2(n_j) - delta, delta = the smallest from 1 on whose partitions fit the sort (MultilinearKZG::open: 3-4 at 2^20, where the
     // pass is throughput bound and the width hardly matters -- 4.92 / 4.97 / 5.36 ms at delta 4 / 3 / 5 -- and 1 below 2^19, where the accumulate
     // pass is as long as its longest lists: 2^16 1.66 / 1.74 / 1.96 / 2.77 ms at delta 1 / 2 / 3 / 4)
@@ -136,10 +141,10 @@ inline int msm_build_geometry(const MsmProblems& pr, bool shared, size_t table_s
     int delta = first_delta;
     int rc = ZKHIP_ERR_SHAPE;
     // narrower windows until the sort's partitions suffice (at 8 bits -- the floor -- 64 problems have 2048)
-    for (; delta <= 24 && rc == ZKHIP_ERR_SHAPE; ++delta) rc = msm_build_geometry_at(pr, shared, table_stride, delta, g);
+    for (; delta <= 24 && rc == ZKHIP_ERR_SHAPE; ++delta) rc = msm_build_geometry_at(pr, shared, table_stride, delta, g, one_points);
     return rc;
 }
-inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t table_stride, int delta, MsmGeometry& g) {
+inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t table_stride, int delta, MsmGeometry& g, bool one_points) {
     g = MsmGeometry();
     uint32_t max_chain = 1, rc_max = 1;
     size_t level_entries = 0;
@@ -184,7 +189,14 @@ inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t tabl
         g.win_first[j] = (uint16_t)g.wins.size();
         uint32_t lg = 0;
         while (((size_t)1 << lg) < nj) ++lg;
-        if (shared && pr.n > 1) {                     // level tables: see msm_level_table_widths
+        if (shared && one_points) {                   // one of several problems against the ONE shifted-SRS table of table_stride points
+            const MsmLevelWidths lw = msm_table_widths(table_stride);
+            if ((size_t)lw.W * table_stride >= ((size_t)1 << 31) || nj > table_stride) return ZKHIP_ERR_SHAPE;   // entry index + sign bit in 32 bits
+            const MsmSet s = add_set(lw.hi, 0);
+            for (uint32_t w = 0; w < lw.W; ++w) add_win(s, w < lw.n_hi ? lw.hi : lw.hi - 1, (uint32_t)(w * table_stride) - pr.off[j]);
+            g.items += nj * lw.W;
+            max_chain = std::max<uint32_t>(max_chain, (uint32_t)((nj * lw.W + (1u << (lw.hi - 1)) - 1) >> (lw.hi - 1)));
+        } else if (shared && pr.n > 1) {              // level tables: see msm_level_table_widths
             const MsmLevelWidths lw = msm_level_table_widths(nj, pr.off[pr.n]);
             const uint32_t c = lw.hi, W = lw.W;
             const MsmSet s = add_set(c, 0);
@@ -215,7 +227,7 @@ inline int msm_build_geometry_at(const MsmProblems& pr, bool shared, size_t tabl
             for (uint32_t v = 0; v < w; ++v) {
                 const uint32_t c = v < n_hi ? hi : hi - 1;
                 const MsmSet s = add_set(c, bit);
-                add_win(s, c, 0);
+                add_win(s, c, one_points ? 0u - pr.off[j] : 0u);
                 bit += c;
             }
             const uint32_t c_lo = n_hi < w ? hi - 1 : hi;

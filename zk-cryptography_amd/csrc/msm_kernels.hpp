@@ -119,20 +119,41 @@ __device__ __forceinline__ uint32_t msm_problem_of(const MsmSortTables& t, uint3
 __device__ __forceinline__ uint32_t msm_win_sub_bits(const uint4& w) { return (w.z >> 16) & 0xffu; }   // w = an MsmWin
 __device__ __forceinline__ uint32_t msm_partition_of(const uint4& w, uint32_t mag) { return w.x + ((mag - 1) >> msm_win_sub_bits(w)); }
 
-static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_count_kernel(const uint64_t* __restrict__ scalars,
-                                                                          const uint8_t* __restrict__ inf, size_t n, MsmPlan pl,
-                                                                          MsmProblems pr, uint32_t* __restrict__ wg_counts) {
-    __shared__ uint32_t local[SORT_MAX_PARTS];
-    __shared__ MsmSortTables tab;
-    for (uint32_t i = threadIdx.x; i < pl.n_parts; i += MSM_BLOCK) local[i] = 0;
-    msm_load_tables(pl, pr, tab);
-    __syncthreads();
+// ONE SET OF POINTS (zkhip_kzg_commit_polys, msm_geometry.hpp): problem j's scalars are a device buffer of their own, read in place
+// through this table -- index i of the pass is scalar i - off[j] of ptrs.p[j] -- and belong to the points 0 .. n_j - 1 of the one
+// SRS: the infinity flag is the POINT's (i - off[j]), the window's entry_off carries the same base into the sort item.  The table is a
+// kernel argument (512 bytes) that each workgroup copies to LDS beside MsmSortTables: 16 KiB of counters + 33.3 KiB of tables + 0.5 KiB,
+// three workgroups per CU with it as without.
+struct MsmPtrTable { const uint64_t* p[MSM_MAX_PROBLEMS]; };
+// One scalar of a pass: which problem it belongs to, whether its point is the identity, its value.  PTRS = false is the text both passes
+// had before they learned the pointer table; lptr is the workgroup's LDS copy of the table (PTRS only).
+template <bool PTRS>
+__device__ __forceinline__ bool msm_sort_fetch(const uint64_t* __restrict__ scalars, const uint64_t* const* lptr, const uint8_t* __restrict__ inf,
+                                               size_t n, size_t i, const MsmProblems& pr, const MsmSortTables& tab, uint32_t& j, Fr& sc) {
+    if constexpr (PTRS) {
+        if (i >= n) return false;
+        j = msm_problem_of(tab, pr.n, (uint32_t)i);
+        const uint32_t k = (uint32_t)i - tab.off[j];      // the scalar's place in its polynomial = its point
+        if (inf && inf[k]) return false;
+        sc = load_fr(lptr[j], k);
+    } else {
+        if (i >= n || (inf && inf[i])) return false;
+        sc = load_fr(scalars, i);
+        j = pr.n > 1 ? msm_problem_of(tab, pr.n, (uint32_t)i) : 0u;
+    }
+    return true;
+}
+template <bool PTRS>
+__device__ __forceinline__ void msm_sort_count_body(const uint64_t* __restrict__ scalars, const uint64_t* const* lptr,
+                                                    const uint8_t* __restrict__ inf, size_t n, const MsmPlan& pl, const MsmProblems& pr,
+                                                    uint32_t* __restrict__ wg_counts, uint32_t* local, const MsmSortTables& tab) {
     const size_t base = (size_t)blockIdx.x * SORT_TILE;
     for (uint32_t u = 0; u < SORT_TILE / MSM_BLOCK; ++u) {
         const size_t i = base + u * MSM_BLOCK + threadIdx.x;
-        if (i >= n || (inf && inf[i])) continue;
-        DigitStream ds(load_fr(scalars, i).from_mont());
-        const uint32_t j = pr.n > 1 ? msm_problem_of(tab, pr.n, (uint32_t)i) : 0u;
+        uint32_t j;
+        Fr sc;
+        if (!msm_sort_fetch<PTRS>(scalars, lptr, inf, n, i, pr, tab, j, sc)) continue;
+        DigitStream ds(sc.from_mont());
         uint32_t v = tab.win_first[j];
         const uint32_t v_end = tab.win_first[j + 1];
         uint4 w = tab.wl[v];
@@ -145,6 +166,27 @@ static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_count_kernel(const 
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < pl.n_parts; i += MSM_BLOCK) wg_counts[(size_t)blockIdx.x * pl.n_parts + i] = local[i];
+}
+static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_count_kernel(const uint64_t* __restrict__ scalars,
+                                                                          const uint8_t* __restrict__ inf, size_t n, MsmPlan pl,
+                                                                          MsmProblems pr, uint32_t* __restrict__ wg_counts) {
+    __shared__ uint32_t local[SORT_MAX_PARTS];
+    __shared__ MsmSortTables tab;
+    for (uint32_t i = threadIdx.x; i < pl.n_parts; i += MSM_BLOCK) local[i] = 0;
+    msm_load_tables(pl, pr, tab);
+    __syncthreads();
+    msm_sort_count_body<false>(scalars, nullptr, inf, n, pl, pr, wg_counts, local, tab);
+}
+static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_count_ptrs_kernel(MsmPtrTable ptrs, const uint8_t* __restrict__ inf, size_t n,
+                                                                               MsmPlan pl, MsmProblems pr, uint32_t* __restrict__ wg_counts) {
+    __shared__ uint32_t local[SORT_MAX_PARTS];
+    __shared__ MsmSortTables tab;
+    __shared__ const uint64_t* lptr[MSM_MAX_PROBLEMS];
+    for (uint32_t i = threadIdx.x; i < pl.n_parts; i += MSM_BLOCK) local[i] = 0;
+    msm_load_tables(pl, pr, tab);
+    if (threadIdx.x < pr.n) lptr[threadIdx.x] = ptrs.p[threadIdx.x];
+    __syncthreads();
+    msm_sort_count_body<true>(nullptr, lptr, inf, n, pl, pr, wg_counts, local, tab);
 }
 
 // per partition: exclusive scan of the workgroups' counts (in place) and the partition total.  One WAVE per partition:
@@ -203,6 +245,34 @@ static __global__ __launch_bounds__(1024) void msm_sort_part_scan_kernel(const u
     if (threadIdx.x == 1023) part_off[n_parts] = part[1023];
 }
 
+template <bool PTRS>
+__device__ __forceinline__ void msm_sort_scatter_body(const uint64_t* __restrict__ scalars, const uint64_t* const* lptr,
+                                                      const uint8_t* __restrict__ inf, size_t n, const MsmProblems& pr,
+                                                      uint2* __restrict__ items, uint32_t* cur, const MsmSortTables& tab) {
+    const size_t base = (size_t)blockIdx.x * SORT_TILE;
+    for (uint32_t u = 0; u < SORT_TILE / MSM_BLOCK; ++u) {
+        const size_t i = base + u * MSM_BLOCK + threadIdx.x;
+        uint32_t j;
+        Fr sc;
+        if (!msm_sort_fetch<PTRS>(scalars, lptr, inf, n, i, pr, tab, j, sc)) continue;
+        DigitStream ds(sc.from_mont());
+        uint32_t v = tab.win_first[j];
+        const uint32_t v_end = tab.win_first[j + 1];
+        uint4 w = tab.wl[v];
+        for (; v < v_end; ++v) {
+            const uint4 w_next = tab.wl[v + 1];
+            const int32_t d = ds.next(w.z & 0xffu);
+            if (d != 0) {
+                const bool neg = d < 0;
+                const uint32_t mag = neg ? (uint32_t)(-d) : (uint32_t)d;
+                const uint32_t pos = atomicAdd(&cur[msm_partition_of(w, mag)], 1u);
+                // (one set of points: w.y holds the window's table offset MINUS the problem's first index, so w.y + i is the point's entry)
+                items[pos] = make_uint2((w.y + (uint32_t)i) | (neg ? 0x80000000u : 0u), (mag - 1) & ((1u << msm_win_sub_bits(w)) - 1));
+            }
+            w = w_next;
+        }
+    }
+}
 static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_scatter_kernel(const uint64_t* __restrict__ scalars,
                                                                             const uint8_t* __restrict__ inf, size_t n, MsmPlan pl,
                                                                             MsmProblems pr, const uint32_t* __restrict__ wg_bases,
@@ -214,27 +284,20 @@ static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_scatter_kernel(cons
         cur[i] = part_off[i] + wg_bases[(size_t)blockIdx.x * pl.n_parts + i];
     msm_load_tables(pl, pr, tab);
     __syncthreads();
-    const size_t base = (size_t)blockIdx.x * SORT_TILE;
-    for (uint32_t u = 0; u < SORT_TILE / MSM_BLOCK; ++u) {
-        const size_t i = base + u * MSM_BLOCK + threadIdx.x;
-        if (i >= n || (inf && inf[i])) continue;
-        DigitStream ds(load_fr(scalars, i).from_mont());
-        const uint32_t j = pr.n > 1 ? msm_problem_of(tab, pr.n, (uint32_t)i) : 0u;
-        uint32_t v = tab.win_first[j];
-        const uint32_t v_end = tab.win_first[j + 1];
-        uint4 w = tab.wl[v];
-        for (; v < v_end; ++v) {
-            const uint4 w_next = tab.wl[v + 1];
-            const int32_t d = ds.next(w.z & 0xffu);
-            if (d != 0) {
-                const bool neg = d < 0;
-                const uint32_t mag = neg ? (uint32_t)(-d) : (uint32_t)d;
-                const uint32_t pos = atomicAdd(&cur[msm_partition_of(w, mag)], 1u);
-                items[pos] = make_uint2((w.y + (uint32_t)i) | (neg ? 0x80000000u : 0u), (mag - 1) & ((1u << msm_win_sub_bits(w)) - 1));
-            }
-            w = w_next;
-        }
-    }
+    msm_sort_scatter_body<false>(scalars, nullptr, inf, n, pr, items, cur, tab);
+}
+static __global__ __launch_bounds__(MSM_BLOCK) void msm_sort_scatter_ptrs_kernel(MsmPtrTable ptrs, const uint8_t* __restrict__ inf, size_t n,
+                                                                                 MsmPlan pl, MsmProblems pr, const uint32_t* __restrict__ wg_bases,
+                                                                                 const uint32_t* __restrict__ part_off, uint2* __restrict__ items) {
+    __shared__ uint32_t cur[SORT_MAX_PARTS];
+    __shared__ MsmSortTables tab;
+    __shared__ const uint64_t* lptr[MSM_MAX_PROBLEMS];
+    for (uint32_t i = threadIdx.x; i < pl.n_parts; i += MSM_BLOCK)
+        cur[i] = part_off[i] + wg_bases[(size_t)blockIdx.x * pl.n_parts + i];
+    msm_load_tables(pl, pr, tab);
+    if (threadIdx.x < pr.n) lptr[threadIdx.x] = ptrs.p[threadIdx.x];
+    __syncthreads();
+    msm_sort_scatter_body<true>(nullptr, lptr, inf, n, pr, items, cur, tab);
 }
 
 // Heavy buckets (pass 4 below walks a bucket with one lane): a bucket holding more than `heavy_min` points is filed as records of
@@ -657,7 +720,7 @@ struct MsmSmallArgs {
 // owns the partials [b][plane][slot] and the terms [b][j][plane]; a lone launch is b = 0, sc_base = 0)
 // (INF_BY_POINT: the flags are indexed by the point alone, not like the scalars -- commits of several vectors against ONE table)
 template <bool INF_BY_POINT = false>
-__device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uint32_t b, size_t sc_base) {
+__device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uint32_t b, size_t sc_base, const uint64_t* __restrict__ scalars) {
     const uint32_t slot = blockIdx.x, plane = blockIdx.y, lane = threadIdx.x;
     uint32_t j = 0;
     while (j + 1 < a.nprob && slot >= a.slot_first[j + 1]) ++j;
@@ -668,7 +731,7 @@ __device__ __forceinline__ void msm_small_planes_body(const MsmSmallArgs& a, uin
     for (uint32_t p = s * 64 + lane; p < pairs; p += lanes_total) {
         const uint32_t w = p / n, i = p - w * n;
         if (a.inf && a.inf[(INF_BY_POINT ? 0u : a.sc_off[j]) + i]) continue;
-        DigitStream ds(load_fr(a.scalars, sc_base + a.sc_off[j] + i).from_mont());
+        DigitStream ds(load_fr(scalars, sc_base + a.sc_off[j] + i).from_mont());
         int32_t d = 0;
         for (uint32_t v = 0; v <= w; ++v) d = ds.next(v < n_hi ? hi : hi - 1);
         const uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
@@ -695,20 +758,26 @@ __device__ __forceinline__ void msm_small_reduce_body(const MsmSmallArgs& a, uin
         store_fq(o + 18, fqu_to_ark(acc.zzz));
     }
 }
-static __global__ __launch_bounds__(64) void msm_small_planes_kernel(MsmSmallArgs a) { msm_small_planes_body(a, 0, 0); }
+static __global__ __launch_bounds__(64) void msm_small_planes_kernel(MsmSmallArgs a) { msm_small_planes_body(a, 0, 0, a.scalars); }
 static __global__ __launch_bounds__(64) void msm_small_reduce_kernel(MsmSmallArgs a) { msm_small_reduce_body(a, 0); }
 // B openings of ONE SRS (zkhip_kzg_open_batch): round j of every opening commits against the same level table with the same widths,
 // so the per-round arrays above describe all of them; only the scalars (opening b's quotients lie q_stride scalars behind opening
 // b - 1's) and the outputs gain the batch index, a grid dimension: (slot, plane, b) and (plane, round, b).
 static __global__ __launch_bounds__(64) void msm_small_batch_planes_kernel(MsmSmallArgs a, size_t q_stride) {
-    msm_small_planes_body(a, blockIdx.z, (size_t)blockIdx.z * q_stride);
+    msm_small_planes_body(a, blockIdx.z, (size_t)blockIdx.z * q_stride, a.scalars);
 }
 static __global__ __launch_bounds__(64) void msm_small_batch_reduce_kernel(MsmSmallArgs a) { msm_small_reduce_body(a, blockIdx.z); }
 // B proofs of one circuit (zkhip_plonk_prove_batch): problem j of every proof is a commit of n[j] scalars, sc_off[j] scalars into the
 // proof's work area, against the ONE shifted-SRS table (tab_off = 0); proof b's area lies q_stride scalars behind proof b - 1's.  The
 // reduce launch is msm_small_batch_reduce_kernel.
 static __global__ __launch_bounds__(64) void msm_small_commit_batch_planes_kernel(MsmSmallArgs a, size_t q_stride) {
-    msm_small_planes_body<true>(a, blockIdx.z, (size_t)blockIdx.z * q_stride);
+    msm_small_planes_body<true>(a, blockIdx.z, (size_t)blockIdx.z * q_stride, a.scalars);
+}
+// B polynomials of ONE length against the one table (zkhip_kzg_commit_polys, a length class of a chunk): polynomial b of the class is a
+// device buffer of its own, ptrs.p[first + b], read in place (a.scalars is not read; a.nprob = 1, sc_off = tab_off = 0); a.partials and
+// a.terms are the class's.  The reduce launch is msm_small_batch_reduce_kernel.
+static __global__ __launch_bounds__(64) void msm_small_commit_polys_planes_kernel(MsmSmallArgs a, MsmPtrTable ptrs, uint32_t first) {
+    msm_small_planes_body<true>(a, blockIdx.z, 0, ptrs.p[first + blockIdx.z]);
 }
 
 // ---- shifted-SRS table (zkhip_srs_precompute) -------------------------------------------------------------

@@ -374,6 +374,27 @@ class TrustedSetup:
 
 
 def _commit(points, inf, n_points, scalars, n_scalars, require_equal_len, table=None):
+    """The commitment of `scalars` (a tensor, n_scalars of them) against the SRS -> G1Affine; a LIST of tensors with a list of lengths
+    is a batch against the one SRS in one call (zkhip_kzg_commit_polys) -> a list of G1Affine, each what the single call returns."""
+    if isinstance(scalars, (list, tuple)):
+        b = len(scalars)
+        if b == 0:
+            return []
+        for s in scalars:
+            assert s.is_contiguous()
+            if s.device != points.device:
+                raise ValueError("commitment_batch: the polynomials must live on the device of the SRS")
+        xy = np.zeros((b, 12), dtype=np.uint64)
+        oinf = np.zeros(b, dtype=np.uint8)
+        ptrs = (C.c_void_p * b)(*[s.data_ptr() if n else None for s, n in zip(scalars, n_scalars)])
+        lens = (C.c_size_t * b)(*[int(n) for n in n_scalars])
+        ctx = N.Context.get(points.device.index)
+        vp = C.c_void_p
+        st = N.lib().zkhip_kzg_commit_polys(ctx.handle, None if table is not None else N.ptr(points), N.ptr(table) if table is not None else None,
+                                            N.ptr(inf), C.c_size_t(n_points), C.c_uint32(b), ptrs, lens, C.c_int(1 if require_equal_len else 0),
+                                            xy.ctypes.data_as(vp), oinf.ctypes.data_as(vp))
+        N.check(st, "The length of powers_of_tau_in_g1 and the length of the evaluations of the polynomial should tally!")
+        return [G1Affine(xy[j], oinf[j]) for j in range(b)]
     out = np.empty(12, dtype=np.uint64)
     oinf = C.c_uint8(0)
     ctx = N.Context.get(points.device.index)
@@ -449,6 +470,18 @@ class MultilinearKZG:
         """MultilinearKZGInterface::commitment (multilinear_kzg.rs:33-48)"""
         assert isinstance(poly, Multilinear)
         return _commit(srs.powers_of_tau_in_g1, srs.inf, len(srs), poly.evaluations, len(poly), True, srs.table_for(len(poly)))
+
+    @staticmethod
+    def commitment_batch(polys, srs):
+        """`commitment` of every polynomial of `polys` against the one SRS in one call (zkhip_kzg_commit_polys) -> a list of G1Affine,
+        each limb for limb what `commitment` returns; the same object may appear several times.  A polynomial whose length is not the
+        SRS's raises `commitment`'s AssertionError before anything is committed; [] returns []."""
+        for p in polys:
+            assert isinstance(p, Multilinear)
+        if not polys:
+            return []
+        lens = [len(p) for p in polys]
+        return _commit(srs.powers_of_tau_in_g1, srs.inf, len(srs), [p.evaluations for p in polys], lens, True, srs.table_for(max(lens)))
 
     @staticmethod
     def commitment_begin(poly, srs):
@@ -646,3 +679,15 @@ class UnivariateKZG:
         than the SRS indexes out of bounds (IndexError), exactly what the unregistered bench would hit."""
         assert isinstance(poly, DenseUnivariatePolynomial)
         return _commit(srs.powers_of_tau_in_g1, srs.inf, len(srs), poly.coefficients, len(poly), False, srs.table_for(len(poly)))
+
+    @staticmethod
+    def commitment_batch(polys, srs):
+        """`commitment` of every polynomial of `polys` against the one SRS in one call (zkhip_kzg_commit_polys) -> a list of G1Affine,
+        each limb for limb what `commitment` returns.  The polynomials may differ in length (the zero polynomial commits to the
+        identity); one with more coefficients than the SRS has points raises `commitment`'s IndexError before anything is committed."""
+        for p in polys:
+            assert isinstance(p, DenseUnivariatePolynomial)
+        if not polys:
+            return []
+        lens = [len(p) for p in polys]
+        return _commit(srs.powers_of_tau_in_g1, srs.inf, len(srs), [p.coefficients for p in polys], lens, False, srs.table_for(max(lens)))
