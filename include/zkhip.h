@@ -34,14 +34,15 @@
  *     zkhip_sumcheck_prove_batch refuse, every other entry point serves (a proof in flight runs on streams, workspace and scratch of
  *     its own).  Commits in flight and sessions hold the WORKSPACE: every entry point that takes any of it refuses, at every size --
  *     also where a small input would not have needed scratch -- and the others serve.  (Two inputs leave a user nothing to do that
- *     needs the workspace, and are served: zkhip_univariate_kzg_open of at most one coefficient, whose quotient is empty, and
+ *     needs the workspace, and are served: zkhip_univariate_kzg_open of at most one coefficient, whose quotient is empty -- and
+ *     zkhip_univariate_kzg_open_batch where every polynomial has at most one --, and
  *     zkhip_circuit_add_mult_mle without gates, which clears its two tables.)
  *     WORKSPACE USERS: zkhip_mle_partial_evaluations, zkhip_mle_evaluation, zkhip_mle_evaluation_batch, zkhip_transcript_challenge, zkhip_circuit_layer_eval,
  *     zkhip_circuit_add_mult_mle, zkhip_gkr_prove, zkhip_gkr_prove_circuit, zkhip_gkr_prove_sharded, zkhip_sumcheck_prove,
  *     zkhip_sumcheck_prove_batch, zkhip_composed_prove, zkhip_composed_prove_batch, zkhip_multi_composed_prove, zkhip_multi_composed_prove_batch,
  *     zkhip_mc_begin, zkhip_mc_begin_ex, zkhip_kzg_commit, zkhip_kzg_commit_table, zkhip_kzg_commit_batch, zkhip_kzg_commit_polys, zkhip_srs_precompute, zkhip_srs_multilinear_g1,
  *     zkhip_srs_univariate_g1, zkhip_srs_multilinear_g2, zkhip_srs_univariate_g2, zkhip_srs_fold_levels, zkhip_srs_level_tables,
- *     zkhip_kzg_open, zkhip_kzg_open_tables, zkhip_kzg_open_batch, zkhip_univariate_kzg_open, zkhip_g2_prepare, zkhip_kzg_prepare,
+ *     zkhip_kzg_open, zkhip_kzg_open_tables, zkhip_kzg_open_batch, zkhip_univariate_kzg_open, zkhip_univariate_kzg_open_batch, zkhip_g2_prepare, zkhip_kzg_prepare,
  *     zkhip_pairing, zkhip_pairing_prepared, zkhip_kzg_verify_batch, zkhip_univariate_kzg_verify_batch, zkhip_ntt, zkhip_domain_transform,
  *     zkhip_univariate_multiply, zkhip_domain_transform_batch, zkhip_univariate_multiply_batch, zkhip_plonk_key_create, zkhip_plonk_prove,
  *     zkhip_plonk_prove_batch, zkhip_plonk_verify, zkhip_plonk_verify_batch.
@@ -779,6 +780,32 @@ int zkhip_kzg_open_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *
 int zkhip_univariate_kzg_open(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *h_z,
                               const uint64_t *d_points_xy, const uint8_t *d_points_inf, size_t n_points,
                               uint64_t *h_evaluation, uint64_t *h_proof_xy, uint8_t *h_proof_inf);
+/* `batch` openings against ONE SRS in one call: opening b is the polynomial h_coeff_ptrs[b] (a HOST array of `batch` device pointers;
+ * a pointer may repeat: one polynomial at several points) of h_n_coeffs[b] coefficients -- the lengths may differ -- at the point
+ * h_z[b][4].  Exactly one of d_points_xy and d_table (the shifted-SRS table WITH header of zkhip_srs_precompute, as in
+ * zkhip_kzg_commit_polys) is given; d_points_inf as in zkhip_kzg_commit.
+ *   Result (host): h_evaluations[batch][4], h_proofs_xy[batch][12], h_proofs_inf[batch] -- opening b limb for limb what
+ *   zkhip_univariate_kzg_open returns for (h_coeff_ptrs[b], h_n_coeffs[b], h_z + 4 b) against the plain points: the same evaluation, the
+ *   same group element and therefore the same affine point, whichever route runs and whether or not a table is used.  Length 0 gives
+ *   evaluation 0 and the identity (flag 1, coordinates zero), length 1 the evaluation c0 and the identity; batch == 0 returns ZKHIP_OK
+ *   and touches nothing; batch == 1 (with plain points) is the single call's path.
+ *   Checks run once, before anything is launched, reserved or written, with the single call's status codes: a NULL context, array or
+ *   output, a NULL pointer for a non-empty polynomial -> ZKHIP_ERR_ARG; some n_coeffs[b] - 1 > n_points -> ZKHIP_ERR_INDEX; some
+ *   n_coeffs[b] >= 2^31 -> ZKHIP_ERR_SHAPE; both or neither of d_points_xy / d_table when some quotient is non-empty, a table whose header
+ *   does not match n_points -> ZKHIP_ERR_ARG; the workspace lent and some polynomial of more than one coefficient -> ZKHIP_ERR_BUSY (a
+ *   batch of polynomials of at most one coefficient commits nothing and is served).  A refused call leaves all three outputs untouched.
+ *   Routes (csrc/univariate_open_plan.hpp, csrc/horner_jobs_kernels.hpp): the batch is cut into chunks of at most 1024 consecutive
+ *   openings and at most 64 MiB of quotients and scan rows, whatever `batch` is (a lone longer polynomial takes what the single call
+ *   takes).  Per chunk: one copy of the job table; ONE launch for all polynomials of at most 2048 coefficients (a workgroup each, no
+ *   carry pass) and three for all longer ones; the quotients, read in place, through the routes of zkhip_kzg_commit_polys; one copy and
+ *   one synchronisation for the evaluations.  Measured per opening against a loop of zkhip_univariate_kzg_open (one MI355X,
+ *   tools/perf_univariate_open_batch.py, profiles/univariate_open_batch/NOTES.md): at B = 64 with plain points 0.027 ms at 2^8
+ *   coefficients (29 x the loop's 0.78), 0.050 at 2^12 (23 x), 0.106 at 2^14 (10 x), 0.33 at 2^16 (3.3 x); with the table 0.015 / 0.034 /
+ *   0.078 / 0.43 ms; at B = 2 1.6 - 2.0 x with plain points.  No shape measured slower than the loop, so none is run as one. */
+int zkhip_univariate_kzg_open_batch(zkhip_ctx *ctx, uint32_t batch, const uint64_t *const *h_coeff_ptrs, const size_t *h_n_coeffs,
+                                    const uint64_t *h_z /* [batch][4] */, const uint64_t *d_points_xy, const void *d_table,
+                                    const uint8_t *d_points_inf, size_t n_points,
+                                    uint64_t *h_evaluations /* [batch][4] */, uint64_t *h_proofs_xy /* [batch][12] */, uint8_t *h_proofs_inf /* [batch] */);
 /* DenseUnivariatePolynomial::evaluate (dense_univariate.rs:184-196: sum c_i z^i; here the Horner suffix scan's V_0) and
  * ::degree (:199-207: index of the last non-zero coefficient, 0 for none or an empty vector) of device coefficients. */
 int zkhip_dense_evaluate(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *h_z, uint64_t *h_out);

@@ -686,6 +686,35 @@ struct UnivariateKZG {
         pr.proof.infinity = inf != 0;
         return pr;
     }
+    // `open` of polys[b] at evaluation_points[b] for every b against the one SRS in one call (zkhip_univariate_kzg_open_batch; the SRS's
+    // table when it has one): each proof what `open` returns.  The lengths may differ; a polynomial may repeat (copies share
+    // the device buffer).
+    static std::vector<UnivariateKZGProof> open_batch(const std::vector<DenseUnivariatePolynomial>& polys, const std::vector<Fr>& evaluation_points,
+                                                      const TrustedSetup& srs) {
+        if (polys.size() != evaluation_points.size()) throw Panic("open_batch: one evaluation point per polynomial");
+        const size_t b = polys.size();
+        std::vector<UnivariateKZGProof> out(b);
+        if (b == 0) return out;
+        std::vector<const uint64_t*> ptrs;
+        std::vector<size_t> lens;
+        std::vector<uint64_t> z(4 * b), ev(4 * b), xy(12 * b);
+        std::vector<uint8_t> inf(b);
+        for (size_t i = 0; i < b; ++i) {
+            ptrs.push_back(polys[i].n ? polys[i].dev->u64() : nullptr);
+            lens.push_back(polys[i].n);
+            std::memcpy(&z[4 * i], evaluation_points[i].l, 32);
+        }
+        int st = zkhip_univariate_kzg_open_batch(ctx(), (uint32_t)b, ptrs.data(), lens.data(), z.data(), srs.table() ? nullptr : srs.points(), srs.table(), srs.inf(),
+                                                 srs.len(), ev.data(), xy.data(), inf.data());
+        if (st == ZKHIP_ERR_INDEX) throw std::out_of_range("index out of bounds: the len of powers_of_tau_in_g1 is smaller than the quotient");
+        check(st, "univariate_kzg_open_batch");
+        for (size_t i = 0; i < b; ++i) {
+            std::memcpy(out[i].evaluation.l, &ev[4 * i], 32);
+            std::memcpy(out[i].proof.xy, &xy[12 * i], 96);
+            out[i].proof.infinity = inf[i] != 0;
+        }
+        return out;
+    }
     static TrustedSetup generate_srs(const Fr& tau, size_t max_degree, bool g2 = false) {      // univariate_kzg.rs:18-35
         TrustedSetup s(max_degree + 1);
         check(zkhip_srs_univariate_g1(ctx(), tau.l, max_degree, s.pts_->u64(), s.inf_->u8()), "generate_srs");

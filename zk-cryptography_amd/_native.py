@@ -61,6 +61,7 @@ def lib():
         _lib.zkhip_sumcheck_prove_begin.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_uint32, vp]
         _lib.zkhip_sumcheck_prove_end.argtypes = [vp, C.c_uint32, vp, vp, vp]
         _lib.zkhip_mle_evaluation_batch.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]
+        _lib.zkhip_univariate_kzg_open_batch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
         _lib.zkhip_mle_evaluation_batch_min.argtypes = [C.c_size_t]
         _lib.zkhip_mle_evaluation_batch_min.restype = C.c_uint32
     return _lib

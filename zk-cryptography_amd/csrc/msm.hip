@@ -16,10 +16,12 @@
 #include "ctx.hpp"
 #include "host_util.hpp"
 #include "host_g1.hpp"
+#include "horner_jobs_kernels.hpp"
 #include "mle_kernels.hpp"
 #include "msm_kernels.hpp"
 #include "srs_kernels.hpp"
 #include "tunables.hpp"
+#include "univariate_open_plan.hpp"
 
 using namespace zk;
 
@@ -1374,6 +1376,29 @@ static int commit_polys_check_lengths(size_t n_points, const size_t* h_n_scalars
     for (uint32_t b = 0; b < batch; ++b) if (h_n_scalars[b] > n_points) return ZKHIP_ERR_INDEX;         // univariate_kzg.rs:53
     return ZKHIP_OK;
 }
+// The call behind its argument checks, in two steps that zkhip_univariate_kzg_open_batch shares (its quotients are the polynomials):
+// ADMIT -- the plan of the m >= 1 non-empty polynomials, the refusal beside a lent workspace, the table's header; nothing is launched,
+// reserved or written -- and the ROUTES, which deliver polynomial k at where[k] of the outputs.
+static int commit_polys_admit(zkhip_ctx* c, const void* d_table_with_header, size_t n_points, const size_t* len, uint32_t m,
+                              std::shared_ptr<const CppPlan>* plan, const uint32_t** d_table) {
+    ZK_TRY(commit_polys_plan(n_points, len, m, d_table_with_header != nullptr, plan));
+    if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
+    ZK_TRY(c->activate());
+    *d_table = nullptr;
+    if (d_table_with_header) {
+        int trc = ZKHIP_OK;
+        *d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);       // built for THESE n_points, with the widths used below?
+        if (!*d_table) return trc;
+    }
+    return ZKHIP_OK;
+}
+static int commit_polys_routes(zkhip_ctx* c, const uint64_t* d_points_xy, const void* d_table_with_header, const uint32_t* d_table,
+                               const uint8_t* d_points_inf, size_t n_points, const CppPlan& plan, uint32_t m, const uint64_t* const* ptrs,
+                               const size_t* len, const uint32_t* where, uint64_t* h_out_xy, uint8_t* h_out_inf) {
+    if (plan.route == CPP_SHORT) return commit_polys_short(c, d_table, d_points_inf, n_points, plan, ptrs, len, where, h_out_xy, h_out_inf);
+    if (plan.route == CPP_BUCKET) return commit_polys_bucket(c, d_points_xy, d_table, d_points_inf, n_points, plan, ptrs, where, h_out_xy, h_out_inf);
+    return commit_polys_single(c, d_points_xy, d_table_with_header, d_table, d_points_inf, n_points, m, ptrs, len, where, h_out_xy, h_out_inf);
+}
 extern "C" int zkhip_kzg_commit_polys(zkhip_ctx* c, const uint64_t* d_points_xy, const void* d_table_with_header, const uint8_t* d_points_inf,
                                       size_t n_points, uint32_t batch, const uint64_t* const* h_scalar_ptrs, const size_t* h_n_scalars,
                                       int require_equal_len, uint64_t* h_out_xy, uint8_t* h_out_inf) {
@@ -1393,22 +1418,12 @@ extern "C" int zkhip_kzg_commit_polys(zkhip_ctx* c, const uint64_t* d_points_xy,
     const uint32_t m = (uint32_t)ptrs.size();
     const uint32_t* d_table = nullptr;
     std::shared_ptr<const CppPlan> plan;
-    if (m) {
-        ZK_TRY(commit_polys_plan(n_points, len.data(), m, d_table_with_header != nullptr, &plan));
-        if (c->ws_loans.lent()) return ZKHIP_ERR_BUSY;
-        ZK_TRY(c->activate());
-        if (d_table_with_header) {
-            int trc = ZKHIP_OK;
-            d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);       // built for THESE n_points, with the widths used below?
-            if (!d_table) return trc;
-        }
-    }
+    if (m) ZK_TRY(commit_polys_admit(c, d_table_with_header, n_points, len.data(), m, &plan, &d_table));
     for (uint32_t b = 0; b < batch; ++b)
         if (h_n_scalars[b] == 0) { std::memset(h_out_xy + 12 * (size_t)b, 0, 96); h_out_inf[b] = 1; }       // P::G1::default()
     if (!m) return ZKHIP_OK;
-    if (plan->route == CPP_SHORT) return commit_polys_short(c, d_table, d_points_inf, n_points, *plan, ptrs.data(), len.data(), where.data(), h_out_xy, h_out_inf);
-    if (plan->route == CPP_BUCKET) return commit_polys_bucket(c, d_points_xy, d_table, d_points_inf, n_points, *plan, ptrs.data(), where.data(), h_out_xy, h_out_inf);
-    return commit_polys_single(c, d_points_xy, d_table_with_header, d_table, d_points_inf, n_points, m, ptrs.data(), len.data(), where.data(), h_out_xy, h_out_inf);
+    return commit_polys_routes(c, d_points_xy, d_table_with_header, d_table, d_points_inf, n_points, *plan, m, ptrs.data(), len.data(), where.data(),
+                               h_out_xy, h_out_inf);
 }
 extern "C" int zkhip_commit_polys_plan_info(size_t n_points, const size_t* h_n_scalars, uint32_t batch, int with_table, uint32_t* h_route,
                                             uint32_t* h_n_chunks, uint32_t* h_chunk_counts, size_t* h_chunk_ws) {
@@ -1501,6 +1516,137 @@ extern "C" int zkhip_univariate_kzg_open(zkhip_ctx* c, const uint64_t* d_coeffs,
     std::memcpy(h_evaluation, c->pinned_u64(ZK_PIN_RES), 32);
     if (n == 1) { *h_proof_inf = 1; return ZKHIP_OK; }          // degree 0 < 1: quotient zero, proof = G1::default()
     return msm_commit(c, d_points_xy, d_points_inf, d_q, n - 1, h_proof_xy, h_proof_inf);
+}
+
+// ---------------------------------------------------------------------------------------
+// zkhip_univariate_kzg_open_batch: a BATCH of openings against one SRS
+// ---------------------------------------------------------------------------------------
+// A lone opening is three scan launches, a synchronisation for the evaluation and a whole commit of the quotient -- the bucket pipeline's
+// ~0.7 ms of latency even for 2^8 coefficients.  A batch shares both halves: the scans of a chunk of jobs run as one launch (short jobs)
+// or three (long jobs) over a job table in device memory (horner_jobs_kernels.hpp), and the chunk's quotients are the polynomials of
+// zkhip_kzg_commit_polys's routes, read in place.  univariate_open_plan.hpp cuts the batch into chunks and bounds a chunk's scratch.
+//
+// WHERE THE QUOTIENTS LIVE.  In the `aux` arena, like the single call's quotient across msm_commit, reserved ONCE for the largest chunk
+// before the first launch.  That is safe because no route of the commit touches that arena: commit_polys_short, commit_polys_bucket and
+// msm_enqueue carve the WORKSPACE (reserve_ws) and the pinned result slots (reserve_msm_pin); commit_polys_single goes through
+// msm_commit / msm_commit_small / zkhip_kzg_commit_begin, which reserve the workspace and side streams; reserve_aux is called by the
+// multilinear openings (kzg_open_one, kzg_open_small_batch), by this call and its single form, and by zkhip_dense_evaluate only -- none
+// of them runs inside a commit.  The commits in flight of the single route read the quotients from side streams that wait for an event
+// recorded on the caller's stream behind the scans, and are ended before the route returns, so the next chunk's scans overwrite nothing
+// that is still read.
+static_assert(UOP_BLOCK == (size_t)HS_T * HS_L, "univariate_open_plan.hpp classes a job by the scan's workgroup");
+// No shape runs as a loop of the single call (the rule and its measurements: univariate_open_plan.hpp): the scans of a chunk are never
+// more launches than one opening's, and where commit_polys_plan.hpp finds no shared pass worth it, its own single route (three commits in
+// flight) already is the loop, minus a synchronisation per opening.
+extern "C" int zkhip_univariate_kzg_open_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_coeff_ptrs, const size_t* h_n_coeffs,
+                                               const uint64_t* h_z, const uint64_t* d_points_xy, const void* d_table_with_header,
+                                               const uint8_t* d_points_inf, size_t n_points, uint64_t* h_evaluations, uint64_t* h_proofs_xy,
+                                               uint8_t* h_proofs_inf) {
+    if (!c) return ZKHIP_ERR_ARG;
+    if (batch == 0) return ZKHIP_OK;
+    if (!h_coeff_ptrs || !h_n_coeffs || !h_z || !h_evaluations || !h_proofs_xy || !h_proofs_inf) return ZKHIP_ERR_ARG;
+    bool any_quotient = false;
+    for (uint32_t b = 0; b < batch; ++b) {
+        if (h_n_coeffs[b] && !h_coeff_ptrs[b]) return ZKHIP_ERR_ARG;
+        any_quotient = any_quotient || h_n_coeffs[b] > 1;
+    }
+    const UopPlan plan = uop_plan(n_points, h_n_coeffs, batch);                 // ZKHIP_ERR_INDEX, ZKHIP_ERR_SHAPE: the single call's
+    ZK_TRY(plan.status);
+    const bool table = d_table_with_header != nullptr;
+    if (any_quotient && (!d_points_xy == !d_table_with_header)) return ZKHIP_ERR_ARG;
+    if (any_quotient && table && n_points * msm_table_widths(n_points).W >= ((size_t)1 << 31)) return ZKHIP_ERR_SHAPE;   // (as the commit against a table)
+    if (any_quotient && c->ws_loans.lent()) return ZKHIP_ERR_BUSY;              // the quotients' commits need the workspace
+    if (batch == 1 && (d_points_xy || !any_quotient))                           // one opening: the single call's path
+        return zkhip_univariate_kzg_open(c, h_coeff_ptrs[0], h_n_coeffs[0], h_z, d_points_xy, d_points_inf, n_points, h_evaluations, h_proofs_xy, h_proofs_inf);
+    ZK_TRY(c->activate());
+    const uint32_t* d_table = nullptr;
+    if (any_quotient && table) {
+        int trc = ZKHIP_OK;
+        d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);
+        if (!d_table) return trc;
+    }
+    // the arena: [ job table | evaluations | the chunk's scratch ], for the largest chunk, once
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    uint32_t max_jobs = 0;
+    for (const UopChunk& ch : plan.chunks) max_jobs = std::max(max_jobs, ch.count);
+    const size_t o_evals = al(sizeof(HornerJobsHead) + (size_t)max_jobs * (sizeof(HornerJob) + 4)), o_scratch = o_evals + al(32 * (size_t)max_jobs);
+    if (!plan.chunks.empty()) ZK_TRY(c->reserve_aux(o_scratch + plan.scratch_max + 256));
+    // the openings that need no device: the zero polynomial (evaluation 0, the identity)
+    for (uint32_t b = 0; b < batch; ++b)
+        if (h_n_coeffs[b] == 0) {
+            std::memset(h_evaluations + 4 * (size_t)b, 0, 32);
+            std::memset(h_proofs_xy + 12 * (size_t)b, 0, 96);
+            h_proofs_inf[b] = 1;
+        }
+    std::vector<char> h_table;
+    std::vector<uint64_t> h_ev;
+    std::vector<const uint64_t*> q_ptrs;
+    std::vector<size_t> q_len;
+    std::vector<uint32_t> q_where;
+    for (const UopChunk& ch : plan.chunks) {
+        char* const aux = (char*)c->aux.ptr;
+        const HornerJobsHead* d_head = (const HornerJobsHead*)aux;
+        const HornerJob* d_jobs = (const HornerJob*)(aux + sizeof(HornerJobsHead));
+        const uint32_t* d_order = (const uint32_t*)(aux + sizeof(HornerJobsHead) + (size_t)ch.count * sizeof(HornerJob));
+        uint64_t* d_evals = (uint64_t*)(aux + o_evals);
+        uint64_t* d_scratch = (uint64_t*)(aux + o_scratch);
+        // 1. the job table: short jobs first in `order`, then the long ones
+        const size_t table_bytes = sizeof(HornerJobsHead) + (size_t)ch.count * (sizeof(HornerJob) + 4);
+        h_table.assign(table_bytes, 0);
+        HornerJob* hj = (HornerJob*)(h_table.data() + sizeof(HornerJobsHead));
+        uint32_t* order = (uint32_t*)(h_table.data() + sizeof(HornerJobsHead) + (size_t)ch.count * sizeof(HornerJob));
+        uint32_t n_s = 0, n_l = 0;
+        q_ptrs.clear(); q_len.clear(); q_where.clear();
+        for (uint32_t k = 0; k < ch.count; ++k) {
+            const UopJob& j = plan.jobs[ch.first + k];
+            hj[k].coeffs = h_coeff_ptrs[j.index];
+            hj[k].n = j.n;
+            std::memcpy(hj[k].z, h_z + 4 * (size_t)j.index, 32);
+            hj[k].q_off = j.q_off;
+            hj[k].row_off = j.row_off;
+            if (uop_short(j.n)) order[n_s++] = k;
+            else order[ch.n_short + n_l++] = k;
+            if (j.n >= 2) {
+                q_ptrs.push_back(d_scratch + 4 * j.q_off); q_len.push_back(j.n - 1); q_where.push_back(j.index);
+            } else {
+                std::memset(h_proofs_xy + 12 * (size_t)j.index, 0, 96);         // degree 0 < 1: quotient zero, proof = G1::default()
+                h_proofs_inf[j.index] = 1;
+            }
+        }
+        // (from here to the chunk's synchronisation nothing returns: the copy reads h_table, the scans write the arena)
+        hipError_t he = hipMemcpyAsync(aux, h_table.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
+        // 2. the scans
+        if (he == hipSuccess) {
+            ProfScope ps(c, "horner_jobs", 0.0);
+            if (ch.n_short)
+                hipLaunchKernelGGL(horner_jobs_short_kernel, dim3(1, ch.n_short), dim3(HS_T), 0, c->stream, d_head, d_jobs, d_order, d_scratch, d_evals);
+            if (ch.n_long) {
+                hipLaunchKernelGGL(horner_jobs_scan_kernel<false>, dim3(ch.max_blocks, ch.n_long), dim3(HS_T), 0, c->stream, d_jobs, d_order, ch.n_short, d_scratch, d_evals);
+                hipLaunchKernelGGL(horner_jobs_top_kernel, dim3(ch.n_long), dim3(1024), 0, c->stream, d_jobs, d_order, ch.n_short, d_scratch);
+                hipLaunchKernelGGL(horner_jobs_scan_kernel<true>, dim3(ch.max_blocks, ch.n_long), dim3(HS_T), 0, c->stream, d_jobs, d_order, ch.n_short, d_scratch, d_evals);
+            }
+        }
+        if (he == hipSuccess) he = hipGetLastError();
+        // 3. the quotients' commits: zkhip_kzg_commit_polys behind its checks
+        int rc = ZKHIP_OK;
+        if (he == hipSuccess && !q_ptrs.empty()) {
+            std::shared_ptr<const CppPlan> cplan;
+            rc = commit_polys_plan(n_points, q_len.data(), (uint32_t)q_len.size(), table, &cplan);
+            if (rc == ZKHIP_OK)
+                rc = commit_polys_routes(c, d_points_xy, d_table_with_header, d_table, d_points_inf, n_points, *cplan, (uint32_t)q_ptrs.size(), q_ptrs.data(),
+                                         q_len.data(), q_where.data(), h_proofs_xy, h_proofs_inf);
+        }
+        // 4. the evaluations: one copy and one synchronisation per chunk (the synchronisation also after an error: h_table and the
+        // arena are in use until the stream is idle)
+        h_ev.resize(4 * (size_t)ch.count);
+        if (he == hipSuccess && rc == ZKHIP_OK) he = hipMemcpyAsync(h_ev.data(), d_evals, 32 * (size_t)ch.count, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t se = hipStreamSynchronize(c->stream);
+        ZK_TRY(rc);
+        ZK_HIP(c, he);
+        ZK_HIP(c, se);
+        for (uint32_t k = 0; k < ch.count; ++k) std::memcpy(h_evaluations + 4 * (size_t)plan.jobs[ch.first + k].index, h_ev.data() + 4 * (size_t)k, 32);
+    }
+    return ZKHIP_OK;
 }
 
 // DenseUnivariatePolynomial::evaluate (dense_univariate.rs:184-196) and ::degree (:199-207) on a device coefficient vector

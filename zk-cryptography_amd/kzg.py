@@ -617,7 +617,28 @@ class UnivariateKZGProof:
 class UnivariateKZG:
     @staticmethod
     def open(poly, evaluation_point, srs):
-        """UnivariateKZGInterface::open (univariate_kzg.rs:60-81)"""
+        """UnivariateKZGInterface::open (univariate_kzg.rs:60-81); a LIST of polynomials with a list of points is a batch against the
+        one SRS in one call (zkhip_univariate_kzg_open_batch) -> a list of UnivariateKZGProof, each what the single call returns."""
+        if isinstance(poly, (list, tuple)):
+            b = len(poly)
+            if b == 0:
+                return []
+            for p in poly:
+                if len(p) and p.coefficients.device != srs.powers_of_tau_in_g1.device:
+                    raise ValueError("open_batch: the polynomials must live on the device of the SRS")
+            z = np.ascontiguousarray(np.stack([_fr_host(e).reshape(4) for e in evaluation_point]), dtype=np.uint64)
+            ev, xy, oinf = np.zeros((b, 4), dtype=np.uint64), np.zeros((b, 12), dtype=np.uint64), np.zeros(b, dtype=np.uint8)
+            ptrs = (C.c_void_p * b)(*[p.coefficients.data_ptr() if len(p) else None for p in poly])
+            lens = (C.c_size_t * b)(*[len(p) for p in poly])
+            table = srs.table_for(max(lens) - 1) if max(lens) > 1 else None      # the quotients are what is committed
+            ctx = N.Context.get(srs.powers_of_tau_in_g1.device.index)
+            vp = C.c_void_p
+            st = N.lib().zkhip_univariate_kzg_open_batch(ctx.handle, C.c_uint32(b), ptrs, lens, z.ctypes.data_as(vp),
+                                                         None if table is not None else N.ptr(srs.powers_of_tau_in_g1),
+                                                         N.ptr(table) if table is not None else None, N.ptr(srs.inf), C.c_size_t(len(srs)),
+                                                         ev.ctypes.data_as(vp), xy.ctypes.data_as(vp), oinf.ctypes.data_as(vp))
+            N.check(st, "univariate open")
+            return [UnivariateKZGProof(ev[j].copy(), G1Affine(xy[j], oinf[j])) for j in range(b)]
         assert isinstance(poly, DenseUnivariatePolynomial)
         z = _fr_host(evaluation_point).reshape(4)
         ev, xy, inf = np.empty(4, dtype=np.uint64), np.empty(12, dtype=np.uint64), C.c_uint8(0)
@@ -628,6 +649,20 @@ class UnivariateKZG:
                                                C.byref(inf))
         N.check(st, "univariate open")
         return UnivariateKZGProof(ev, G1Affine(xy, inf.value))
+
+    @staticmethod
+    def open_batch(polys, evaluation_points, srs):
+        """`open` of polys[b] at evaluation_points[b], for every b, against the one SRS in one call (zkhip_univariate_kzg_open_batch)
+        -> a list of UnivariateKZGProof, each limb for limb what `open` returns.  The polynomials may differ in length and may repeat
+        (one polynomial at several points); one too long for the SRS raises `open`'s IndexError before anything is opened."""
+        polys = list(polys)
+        evaluation_points = list(evaluation_points)
+        for p in polys:
+            assert isinstance(p, DenseUnivariatePolynomial)
+        assert len(polys) == len(evaluation_points), "open_batch: one evaluation point per polynomial"
+        if not polys:
+            return []
+        return UnivariateKZG.open(polys, evaluation_points, srs)
 
     @staticmethod
     def generate_srs(tau, max_degree, g2=False):
