@@ -52,10 +52,10 @@
  *     zkhip_mle_mul_distinct, zkhip_mle_elementwise, zkhip_mle_add_to_front, zkhip_mle_add_to_back, zkhip_mle_to_bytes,
  *     zkhip_mle_block_sums, zkhip_mle_block_sums_deferred, zkhip_mle_block_sums_total, zkhip_composed_sum, zkhip_multi_composed_sum,
  *     zkhip_composed_element_wise, zkhip_circuit_create, zkhip_circuit_evaluate_batch, zkhip_gkr_prove_batch, zkhip_gkr_layer_tables, zkhip_srs_fingerprint,
- *     zkhip_table_release, zkhip_dense_evaluate, zkhip_dense_degree, zkhip_sc_begin, zkhip_plonk_vkey_create,
+ *     zkhip_table_release, zkhip_dense_evaluate, zkhip_dense_degree, zkhip_dense_points, zkhip_sc_begin, zkhip_plonk_vkey_create,
  *     zkhip_plonk_key_destroy.
  *     (zkhip_gkr_prove_batch proves on lanes with a workspace each.  zkhip_circuit_evaluate_batch keeps its pointer table in a buffer of the
- *     circuit's own.  zkhip_sc_begin takes an allocation of its own while the workspace
+ *     circuit's own.  zkhip_dense_points keeps its scratch in an allocation of its own.  zkhip_sc_begin takes an allocation of its own while the workspace
  *     is lent.  zkhip_mle_block_sums* need none at the granularity zkhip_sumcheck_plan_log_blocks asks for; with more than 2^15 chunks of
  *     4096 entries, or fine blocks of more than 256 entries, they take a buffer from it and are then refused like the users above.)
  */
@@ -810,6 +810,35 @@ int zkhip_univariate_kzg_open_batch(zkhip_ctx *ctx, uint32_t batch, const uint64
  * ::degree (:199-207: index of the last non-zero coefficient, 0 for none or an empty vector) of device coefficients. */
 int zkhip_dense_evaluate(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *h_z, uint64_t *h_out);
 int zkhip_dense_degree(zkhip_ctx *ctx, const uint64_t *d_coeffs, size_t n_coeffs, size_t *h_degree);
+/* A batch of polynomials at many points, and the polynomials through many points: the two directions of the Vandermonde map
+ * V[j][k] = x_j^k of a node set.  Everything is in device memory, strides count field elements, job b < batch <= 65535 uses the rows
+ * d_in + 4 b in_stride, d_x + 4 b x_stride and d_out + 4 b out_stride, and the call runs on the context's stream.
+ *   ZKHIP_DENSE_EVALUATE     d_in: n_in coefficients per job, low degree first; d_x: n_x points; d_out: the n_x values
+ *       (dense_univariate.rs:184-196 at every point).  in_stride == 0: one polynomial at every job's points; x_stride == 0: every
+ *       polynomial at the same points.  n_in == 0 writes zeros, the empty polynomial.  The call does not synchronise.
+ *   ZKHIP_DENSE_INTERPOLATE  DenseUnivariatePolynomial::interpolate(point_ys, point_xs) (dense_univariate.rs:76-85): d_in holds the
+ *       values y, d_x the nodes, n_in == n_x == n <= 2^14 (anything else is ZKHIP_ERR_SHAPE: the panic of dense_langrange_basis,
+ *       polynomial/src/utils.rs:108-114; beyond 2^14 nodes a product-tree algorithm is the right tool); d_out receives the n
+ *       coefficients of the unique polynomial of degree < n through the job's points, trailing zeros included (where every y is zero
+ *       the reference's Add fold returns the EMPTY vector; here the n coefficients are zero).  x_stride == 0: shared nodes, whose
+ *       weights are computed once for the batch.  A repeated node in ANY job is ZKHIP_ERR_ARG (the reference's inverse().unwrap() on
+ *       zero) and the caller may then rely on no output row.  To report that the call reads ONE flag word back -- written by a plain
+ *       vector store of 1 from the lane that meets a zero denominator -- and that copy is the call's single synchronisation.
+ *   Both: batch == 0 or n_x == 0 is a successful no-op; batch > 65535 is ZKHIP_ERR_SHAPE, and so are rows of a batch that overlap (a
+ *   non-zero stride below its row's length); the output must not overlap an input (d_out == d_in or d_out == d_x is ZKHIP_ERR_ARG);
+ *   only the n_x elements of each output row are written, the padding of a wider out_stride stays as it was.
+ *   The call takes no byte of the context's workspace: its scratch -- the weights, the partial records and the domain values in front
+ *   of the inverse transform -- is an allocation of the context's own that only grows, so the call is served beside proofs in flight,
+ *   commits in flight and sessions, bit for bit as on an idle context.  Both ops are O(n_in n_x) field products in loops private to a
+ *   lane; a call with few points cuts each job's inner range into segments so that it still fills the chip (csrc/dense_points_plan.hpp,
+ *   DESIGN.md section 9a; measured: profiles/dense_points/NOTES.md).
+ * zkhip_dense_points_plan_info (host only, no handle): the plan of such a call -- h_info[8] = regime (0 no-op, 1 evaluate, 2 interpolate,
+ *   3 refused), segments per job, lanes of a workgroup, launches per chunk of jobs, scratch bytes (low, high word), the coefficients or
+ *   nodes a workgroup stages at a time, jobs per chunk.  Returns ZKHIP_ERR_SHAPE where the call would. */
+enum { ZKHIP_DENSE_EVALUATE = 0, ZKHIP_DENSE_INTERPOLATE = 1 };
+int zkhip_dense_points(zkhip_ctx *ctx, int op, uint32_t batch, const uint64_t *d_in, size_t in_stride, size_t n_in,
+                       const uint64_t *d_x, size_t x_stride, size_t n_x, uint64_t *d_out, size_t out_stride);
+int zkhip_dense_points_plan_info(int op, uint32_t batch, size_t n_in, size_t n_x, uint32_t *h_info);
 /* Sum of n affine points given on the host (combining per-GPU partial commitments after an all-gather). */
 int zkhip_g1_sum_affine(const uint64_t *h_points_xy, const uint8_t *h_points_inf, size_t n, uint64_t *h_out_xy,
                         uint8_t *h_out_inf);

@@ -510,8 +510,66 @@ struct DenseUnivariatePolynomial {                                              
         check(zkhip_dense_degree(ctx(), n ? dev->u64() : nullptr, n, &d), "dense_degree");
         return d;
     }
+    // at many points in one call (zkhip_dense_points)
+    std::vector<Fr> evaluate(const std::vector<Fr>& points) const {
+        const auto rows = dense_points(ZKHIP_DENSE_EVALUATE, 1, n ? dev->u64() : nullptr, 0, n, flat({points}), 0, points.size(), "dense_points evaluate");
+        return rows.empty() ? std::vector<Fr>() : rows[0];
+    }
+    // polynomials of one length, each at its own points (points.size() == polys.size()) or all at the same (points.size() == 1)
+    static std::vector<std::vector<Fr>> evaluate_batch(const std::vector<DenseUnivariatePolynomial>& polys, const std::vector<std::vector<Fr>>& points) {
+        if (polys.empty()) return {};
+        if (points.size() != polys.size() && points.size() != 1) throw Panic("evaluate_batch: one row of points, or one per polynomial");
+        const size_t len = polys[0].n, m = points[0].size();
+        std::vector<Fr> coeffs;
+        for (const auto& p : polys) {
+            if (p.n != len) throw Panic("evaluate_batch: polynomials of one length");
+            const auto c = p.coefficients();
+            coeffs.insert(coeffs.end(), c.begin(), c.end());
+        }
+        DeviceBuffer d_c(32 * coeffs.size());
+        if (!coeffs.empty()) d_c.upload(coeffs.data(), 32 * coeffs.size());
+        return dense_points(ZKHIP_DENSE_EVALUATE, polys.size(), len ? d_c.u64() : nullptr, len, len, flat(points), points.size() == 1 ? 0 : m, m, "dense_points evaluate");
+    }
+    // DenseUnivariatePolynomial::interpolate(point_ys, point_xs) (:76-85): n coefficients, also where the reference's fold leaves fewer
+    static DenseUnivariatePolynomial interpolate(const std::vector<Fr>& point_ys, const std::vector<Fr>& point_xs) {
+        return DenseUnivariatePolynomial(interpolate_batch({point_ys}, {point_xs}).at(0));
+    }
+    // ys.size() jobs; xs holds one row of nodes per job, or one row shared by all (their weights are then computed once)
+    static std::vector<std::vector<Fr>> interpolate_batch(const std::vector<std::vector<Fr>>& ys, const std::vector<std::vector<Fr>>& xs) {
+        if (ys.empty()) return {};
+        if (xs.size() != ys.size() && xs.size() != 1) throw Panic("interpolate_batch: one row of nodes, or one per job");
+        const size_t len = ys[0].size();
+        if (xs[0].size() != len) throw Panic("interpolate: as many ys as xs");                 // dense_langrange_basis, utils.rs:108-114
+        const std::vector<Fr> y = flat(ys);
+        DeviceBuffer d_y(32 * y.size());
+        if (!y.empty()) d_y.upload(y.data(), 32 * y.size());
+        return dense_points(ZKHIP_DENSE_INTERPOLATE, ys.size(), d_y.u64(), len, len, flat(xs), xs.size() == 1 ? 0 : len, len, "dense_points interpolate");
+    }
     size_t n;
     std::shared_ptr<DeviceBuffer> dev;
+
+  private:
+    static std::vector<Fr> flat(const std::vector<std::vector<Fr>>& rows) {
+        std::vector<Fr> v;
+        for (const auto& r : rows) {
+            if (r.size() != rows[0].size()) throw Panic("rows of one length");
+            v.insert(v.end(), r.begin(), r.end());
+        }
+        return v;
+    }
+    // zkhip_dense_points on rows already on the device (d_in) and rows uploaded here (x) -> batch rows of n_x elements
+    static std::vector<std::vector<Fr>> dense_points(int op, size_t batch, const uint64_t* d_in, size_t in_stride, size_t n_in, const std::vector<Fr>& x,
+                                                     size_t x_stride, size_t n_x, const char* what) {
+        if (batch > 65535) throw Panic(std::string(what) + ": at most 65535 jobs");
+        DeviceBuffer d_x(32 * x.size()), d_out(32 * batch * n_x);
+        if (!x.empty()) d_x.upload(x.data(), 32 * x.size());
+        check(zkhip_dense_points(ctx(), op, (uint32_t)batch, d_in, in_stride, n_in, d_x.u64(), x_stride, n_x, d_out.u64(), n_x), what);
+        std::vector<Fr> out(batch * n_x);
+        if (!out.empty()) d_out.download(out.data(), 32 * out.size());
+        std::vector<std::vector<Fr>> rows(batch);
+        for (size_t b = 0; b < batch; ++b) rows[b].assign(out.begin() + b * n_x, out.begin() + (b + 1) * n_x);
+        return rows;
+    }
 };
 class TrustedSetup {                                                                           // trusted_setup.rs:9-13
   public:

@@ -7,6 +7,7 @@ Host-side mirror (Python over ctypes) of the reference's Rust surfaces for the h
     circuit::Circuit, gkr::GKRProtocol::prove -> .gkr
     polynomial::univariate::{Domain, UnivariateEval} -> .univariate
     plonk::{compiler, protocol}, merlin::MerlinTranscript -> .plonk
+    polynomial::DenseUnivariatePolynomial::{interpolate, evaluate}, shamir_secret_sharing -> .kzg, .shamir
 Every operation runs hand-written HIP kernels in csrc/libzkhip.so through the C ABI of
 include/zkhip.h; there is no CPU fallback (a missing library or GPU raises).
 """
@@ -20,6 +21,7 @@ from zk_cryptography_amd.composed import (ComposedMultilinear, ComposedSumcheck,
                                           MultiComposedSumcheckProof, MultiComposedSumcheckProver,
                                           SparseUnivariatePolynomial)
 from zk_cryptography_amd.univariate import Domain, UnivariateEval  # noqa: F401
+from zk_cryptography_amd import shamir  # noqa: F401
 from zk_cryptography_amd.gkr import (Circuit, CircuitLayer, DeviceFiatShamirTranscript, FiatShamirTranscript, Gate, GKRProof, GKRProtocol,  # noqa: F401
                                      SuccintGKRProof, SuccintGKRProtocol)
 from zk_cryptography_amd.plonk import (AssemblyEqn, CommonPreprocessedInput, MerlinTranscript, PlonkProof, PlonkProver,  # noqa: F401

@@ -14,6 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libzkhip.so")
 
 ZKHIP_OK, ERR_HIP, ERR_SHAPE, ERR_INDEX, ERR_ARG, ERR_NOMEM, ERR_BUSY, ERR_PEER, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
+DENSE_EVALUATE, DENSE_INTERPOLATE = 0, 1          # the `op` of zkhip_dense_points
 
 
 class ZkhipError(RuntimeError):
@@ -64,6 +65,8 @@ def lib():
         _lib.zkhip_univariate_kzg_open_batch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
         _lib.zkhip_mle_evaluation_batch_min.argtypes = [C.c_size_t]
         _lib.zkhip_mle_evaluation_batch_min.restype = C.c_uint32
+        _lib.zkhip_dense_points.argtypes = [vp, C.c_int, C.c_uint32, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]
+        _lib.zkhip_dense_points_plan_info.argtypes = [C.c_int, C.c_uint32, C.c_size_t, C.c_size_t, vp]
     return _lib
 
 

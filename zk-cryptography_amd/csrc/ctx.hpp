@@ -85,6 +85,7 @@ struct zkhip_ctx {
     zk::DevMem d_gen_table;          // SRS generation: d * 2^(8w) * G for 32 windows x 255 digits, affine (+ infinity flags); built on first use
     std::unique_ptr<NttCache, NttCacheDelete> ntt_state;   // twiddle tables and pass plans of the transforms this context has run (ntt.hip)
     zk::GrowBuf aux;                 // second grow-only buffer for entry points that call others which own the workspace (kzg_open)
+    zk::GrowBuf dense_scratch;       // zkhip_dense_points: weights, records and domain values (dense_points_plan.hpp); grows only, never the workspace
     uint32_t outer_token = 0;   // sessions that feed an outer transcript (composed_kernels.hpp): a value no earlier session's flags hold
     // pinned result buffers + events for commits whose host epilogue is deferred (msm_enqueue / msm_finish), and the side
     // streams on which MultilinearKZG::open runs its per-round commits next to each other

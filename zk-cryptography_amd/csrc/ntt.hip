@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "dense_points_kernels.hpp"
 #include "host_fr.hpp"
 #include "host_util.hpp"
 #include "ntt_batch_kernels.hpp"
@@ -419,6 +420,97 @@ extern "C" int zkhip_univariate_multiply_batch(zkhip_ctx* c, uint32_t batch, con
         }
     }
     return ZKHIP_OK;
+}
+
+// ---- DenseUnivariatePolynomial at many points, and through many points (dense_points_kernels.hpp) -----------------------------------
+// The plan -- segments, chunks of jobs, scratch layout -- is dense_points_plan.hpp.  The scratch is zkhip_ctx::dense_scratch, an
+// allocation of this call's own that only grows: the call takes no byte of the workspace, is never refused for a lent one, and runs
+// beside proofs in flight, commits in flight and sessions.  The inverse transforms of an interpolation are ntt_small_batch /
+// ntt_big_batch with that scratch as their work buffer; their twiddle tables and pass plans are the context's (NttCache).
+extern "C" int zkhip_dense_points_plan_info(int op, uint32_t batch, size_t n_in, size_t n_x, uint32_t* h_info) {
+    if (!h_info || (op != DP_OP_EVALUATE && op != DP_OP_INTERPOLATE)) return ZKHIP_ERR_ARG;
+    const DpPlan p = dp_plan(op, batch, n_in, n_x);
+    h_info[DP_INFO_REGIME] = p.regime;
+    h_info[DP_INFO_SEGS] = p.segs;
+    h_info[DP_INFO_LANES] = p.lanes;
+    h_info[DP_INFO_LAUNCHES] = p.launches;
+    h_info[DP_INFO_SCRATCH_LO] = (uint32_t)p.scratch_bytes;
+    h_info[DP_INFO_SCRATCH_HI] = (uint32_t)((uint64_t)p.scratch_bytes >> 32);
+    h_info[DP_INFO_CHUNK_LEN] = DP_CHUNK;
+    h_info[DP_INFO_JOBS_PER_CHUNK] = p.chunk;
+    return p.regime == DP_REFUSED ? ZKHIP_ERR_SHAPE : ZKHIP_OK;
+}
+
+extern "C" int zkhip_dense_points(zkhip_ctx* c, int op, uint32_t batch, const uint64_t* d_in, size_t in_stride, size_t n_in,
+                                  const uint64_t* d_x, size_t x_stride, size_t n_x, uint64_t* d_out, size_t out_stride) {
+    if (!c || (op != DP_OP_EVALUATE && op != DP_OP_INTERPOLATE)) return ZKHIP_ERR_ARG;
+    const DpPlan p = dp_plan(op, batch, n_in, n_x);
+    if (p.regime == DP_REFUSED) return ZKHIP_ERR_SHAPE;
+    if (p.regime == DP_NOOP) return ZKHIP_OK;
+    if (!d_out || !d_x || (n_in && !d_in) || d_out == d_in || d_out == d_x) return ZKHIP_ERR_ARG;
+    if (batch > 1 && (out_stride < n_x || (in_stride && in_stride < n_in) || (x_stride && x_stride < n_x))) return ZKHIP_ERR_SHAPE;   // rows that overlap
+    ZK_TRY(c->activate());
+    ZK_TRY(c->dense_scratch.reserve(p.scratch_bytes, {c->stream}, &c->last_hip));
+    char* const base = (char*)c->dense_scratch.ptr;
+    if (p.regime == DP_EVALUATE) {
+        const dim3 grid(p.grid_x, p.segs, batch);
+        ProfScope ps(c, "dense_points_eval", 0.0);
+        if (p.segs == 1) {
+            hipLaunchKernelGGL(dp_eval_kernel<false>, grid, dim3(DP_LANES), 0, c->stream, d_in, in_stride, n_in, d_x, x_stride, n_x, d_out, out_stride, p.seg_len);
+        } else {
+            uint64_t* rec = (uint64_t*)(base + p.o_rec2);
+            hipLaunchKernelGGL(dp_eval_kernel<true>, grid, dim3(DP_LANES), 0, c->stream, d_in, in_stride, n_in, d_x, x_stride, n_x, rec, (size_t)0, p.seg_len);
+            hipLaunchKernelGGL(dp_eval_sum_kernel, dim3(p.grid_x, 1, batch), dim3(DP_LANES), 0, c->stream, (const uint64_t*)rec, p.segs, n_x, d_out, out_stride);
+        }
+        ZK_HIP(c, hipGetLastError());
+        return ZKHIP_OK;
+    }
+    const uint32_t n = (uint32_t)n_x, N = 1u << p.log_N, seg_len = (uint32_t)p.seg_len;
+    const bool shared = batch == 1 || x_stride == 0;                 // one node set: its 1 / D_i are computed once for the batch
+    uint32_t* flag = (uint32_t*)(base + p.o_flag);
+    uint64_t *winv = (uint64_t*)(base + p.o_winv), *rec1 = (uint64_t*)(base + p.o_rec1), *rec2 = (uint64_t*)(base + p.o_rec2);
+    uint64_t *vals = (uint64_t*)(base + p.o_vals), *work = (uint64_t*)(base + p.o_work);
+    FrArg omega;
+    { const zkhost::Fr w = root_of_unity(p.log_N); std::memcpy(omega.v, w.l, 32); }
+    ZK_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    const uint32_t node_blocks = (n + DP_LANES - 1) / DP_LANES;
+    auto weights = [&](const uint64_t* x, size_t stride, uint32_t rows) {
+        ProfScope ps(c, "dense_points_weights", 0.0);
+        if (p.segs == 1) {
+            hipLaunchKernelGGL(dp_weights_kernel<false>, dim3(node_blocks, 1, rows), dim3(DP_LANES), 0, c->stream, x, stride, n, seg_len, winv, flag);
+        } else {
+            hipLaunchKernelGGL(dp_weights_kernel<true>, dim3(node_blocks, p.segs, rows), dim3(DP_LANES), 0, c->stream, x, stride, n, seg_len, rec1, flag);
+            hipLaunchKernelGGL(dp_weights_fold_kernel, dim3(node_blocks, 1, rows), dim3(DP_LANES), 0, c->stream, (const uint64_t*)rec1, p.segs, n, winv, flag);
+        }
+    };
+    if (shared) weights(d_x, 0, 1);
+    for (uint32_t i = 0; i < p.n_chunks; ++i) {
+        const DpChunk ch = dp_chunk(p, i);
+        const uint64_t* x = shared ? d_x : d_x + 4 * (size_t)ch.first * x_stride;
+        const uint64_t* y = d_in + 4 * (size_t)ch.first * in_stride;
+        uint64_t* out = d_out + 4 * (size_t)ch.first * out_stride;
+        if (!shared) weights(x, x_stride, ch.count);
+        {
+            ProfScope ps(c, "dense_points_domain", 0.0);
+            const size_t xs = shared ? 0 : x_stride, ws = shared ? 0 : (size_t)n;
+            if (p.segs == 1) {
+                hipLaunchKernelGGL(dp_domain_kernel<false>, dim3(p.grid_x, 1, ch.count), dim3(DP_LANES), 0, c->stream, y, in_stride, x, xs,
+                                   (const uint64_t*)winv, ws, n, N, seg_len, omega, vals);
+            } else {
+                hipLaunchKernelGGL(dp_domain_kernel<true>, dim3(p.grid_x, p.segs, ch.count), dim3(DP_LANES), 0, c->stream, y, in_stride, x, xs,
+                                   (const uint64_t*)winv, ws, n, N, seg_len, omega, rec2);
+                hipLaunchKernelGGL(dp_domain_fold_kernel, dim3(p.grid_x, 1, ch.count), dim3(DP_LANES), 0, c->stream, (const uint64_t*)rec2, p.segs, N, vals);
+            }
+        }
+        ZK_HIP(c, hipGetLastError());
+        if (p.log_N < DP_NTT_WORK_LOG) ZK_TRY(ntt_small_batch(c, ch.count, vals, N, N, nullptr, 0, out, out_stride, n, p.log_N, 1));
+        else ZK_TRY(ntt_big_batch(c, ch.count, vals, N, N, nullptr, 0, out, out_stride, n, p.log_N, 1, work, N));
+    }
+    // the call's single synchronisation: one flag word, raised by a lane that met D_i == 0 (a repeated node)
+    uint32_t* h_flag = (uint32_t*)c->pinned_u64(ZK_PIN_RES);
+    ZK_HIP(c, hipMemcpyAsync(h_flag, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return *h_flag ? ZKHIP_ERR_ARG : ZKHIP_OK;
 }
 
 // ---- host-side Fr helpers ------------------------------------------------------------------------------

@@ -120,6 +120,45 @@ def pairing(g1_points, g2_points=None, prepared=None):
     return out.cpu().numpy().view(np.uint64)[:n]
 
 
+def _is_points(x):
+    """a 2-D [m, 4] argument (numpy or torch), as opposed to one field element"""
+    return x.dim() == 2 if hasattr(x, "is_cuda") else np.ndim(x) == 2
+
+
+def _empty_fr(n, device):
+    import torch
+    return torch.empty((n, 4), dtype=torch.int64, device=device)
+
+
+def _rows_device(a, device):
+    """[..., 4] limbs (numpy uint64 or an int64 tensor) -> a contiguous int64 device tensor of the same shape"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.int64 or a.shape[-1] != 4:
+            raise AssertionError("field elements are int64 [..., 4]")
+        return (a if a.is_cuda else a.cuda(device)).contiguous()
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim < 2 or a.shape[-1] != 4:
+        raise AssertionError("field elements are uint64 [..., 4] Montgomery limbs")
+    return torch.from_numpy(a.view(np.int64)).cuda(device)
+
+
+def _points_device(points, device):
+    """[m, 4] points -> (device tensor, whether the caller gave host memory and gets host memory back)"""
+    t = _rows_device(points, device)
+    if t.dim() != 2:
+        raise AssertionError("points are [m, 4]")
+    return t, not hasattr(points, "is_cuda") or not points.is_cuda
+
+
+def _rows_or_shared_device(a, batch, device, what):
+    """[m, 4] shared by the batch or [batch, m, 4] -> (device tensor, whether the caller gave host memory)"""
+    t = _rows_device(a, device)
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != batch):
+        raise AssertionError(what)
+    return t, not hasattr(a, "is_cuda") or not a.is_cuda
+
+
 class DenseUnivariatePolynomial:
     """polynomial::DenseUnivariatePolynomial (dense_univariate.rs:15-17): coefficients, low degree first, in HBM."""
 
@@ -142,13 +181,80 @@ class DenseUnivariatePolynomial:
         return d.value
 
     def evaluate(self, point):
-        """dense_univariate.rs:184-196 -> uint64[4] (Montgomery)"""
+        """dense_univariate.rs:184-196 -> uint64[4] (Montgomery).  A 2-D [m, 4] argument is m points in one call
+        (zkhip_dense_points): a numpy array gives a numpy [m, 4], a device tensor gives a device tensor without a synchronisation."""
+        if _is_points(point):
+            if len(point) == 1 and not hasattr(point, "is_cuda"):
+                # one host point: the single call's scan cuts the coefficients finer than a lane's Horner can (measured 115 against
+                # 212 us at 2^8 coefficients, 117 against 735 at 2^16: profiles/dense_points/NOTES.md, "One point")
+                return self.evaluate(np.asarray(point, dtype=np.uint64)[0]).reshape(1, 4)
+            pts, to_host = _points_device(point, self.coefficients.device)
+            out = _empty_fr(pts.shape[0], pts.device)
+            ctx = N.Context.get(pts.device.index)
+            N.check(N.lib().zkhip_dense_points(ctx.handle, N.DENSE_EVALUATE, 1, self.coefficients.data_ptr(), 0, len(self),
+                                               pts.data_ptr(), 0, pts.shape[0], out.data_ptr(), pts.shape[0]), "evaluate")
+            return out.cpu().numpy().view(np.uint64) if to_host else out
         out = np.zeros(4, dtype=np.uint64)
         if len(self):
             z = _fr_host(point).reshape(4)
             ctx = N.Context.get(self.coefficients.device.index)
             N.check(N.lib().zkhip_dense_evaluate(ctx.handle, N.ptr(self.coefficients), C.c_size_t(len(self)),
                                                  z.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "evaluate")
+        return out
+
+    @staticmethod
+    def evaluate_batch(polys, points):
+        """B polynomials of one length at many points in one call (zkhip_dense_points).  polys: a list of polynomials, or their
+        coefficients as [B, n, 4]; points: [m, 4] shared by all polynomials or [B, m, 4], one row per polynomial -> [B, m, 4]
+        (numpy when the points are numpy, a device tensor otherwise)."""
+        import torch
+        if isinstance(polys, (list, tuple)):
+            if not polys:
+                return np.empty((0, 0, 4), dtype=np.uint64)
+            if any(len(p) != len(polys[0]) for p in polys):
+                raise AssertionError("evaluate_batch: polynomials of one length")
+            coeffs = torch.stack([p.coefficients for p in polys])
+        else:
+            coeffs = _rows_device(polys, None)
+        B, n = coeffs.shape[0], coeffs.shape[1]
+        pts, to_host = _rows_or_shared_device(points, B, coeffs.device, "evaluate_batch: points are [m, 4] or [B, m, 4]")
+        m = pts.shape[-2]
+        out = torch.empty((B, m, 4), dtype=torch.int64, device=coeffs.device)
+        ctx = N.Context.get(coeffs.device.index)
+        N.check(N.lib().zkhip_dense_points(ctx.handle, N.DENSE_EVALUATE, B, coeffs.data_ptr(), n, n, pts.data_ptr(),
+                                           m if pts.dim() == 3 else 0, m, out.data_ptr(), m), "evaluate_batch")
+        return out.cpu().numpy().view(np.uint64) if to_host else out
+
+    @staticmethod
+    def interpolate(point_ys, point_xs):
+        """DenseUnivariatePolynomial::interpolate (dense_univariate.rs:76-85; the reference's argument order): the polynomial of
+        degree < n through (point_xs[i], point_ys[i]), n <= 2^14, as n device coefficients.  Repeated nodes raise ValueError (the
+        reference unwraps the inverse of zero), different lengths AssertionError (dense_langrange_basis, utils.rs:108-114).
+        One deviation: when all ys are zero the result holds n zero coefficients where the reference's Add fold returns the empty
+        vector; degree() and evaluate agree on both."""
+        ys = _to_device(point_ys)
+        xs = _to_device(point_xs, ys.device)
+        if ys.shape[0] != xs.shape[0]:
+            raise AssertionError("interpolate: as many ys as xs")
+        return DenseUnivariatePolynomial(DenseUnivariatePolynomial.interpolate_batch(ys[None], xs)[0])
+
+    @staticmethod
+    def interpolate_batch(ys, xs):
+        """B interpolations in one call (zkhip_dense_points): ys [B, n, 4]; xs [n, 4] for shared nodes -- their weights are computed
+        once -- or [B, n, 4] for nodes per job -> the coefficients as a device tensor [B, n, 4]"""
+        import torch
+        ys = _rows_device(ys, None)
+        B, n = ys.shape[0], ys.shape[1]
+        xs, _ = _rows_or_shared_device(xs, B, ys.device, "interpolate_batch: xs are [n, 4] or [B, n, 4]")
+        if xs.shape[-2] != n:
+            raise AssertionError("interpolate_batch: as many ys as xs")
+        out = torch.empty((B, n, 4), dtype=torch.int64, device=ys.device)
+        ctx = N.Context.get(ys.device.index)
+        st = N.lib().zkhip_dense_points(ctx.handle, N.DENSE_INTERPOLATE, B, ys.data_ptr(), n, n, xs.data_ptr(), n if xs.dim() == 3 else 0,
+                                        n, out.data_ptr(), n)
+        if st == N.ERR_ARG:
+            raise ValueError("interpolate: a node is repeated")
+        N.check(st, "interpolate")
         return out
 
     def __mul__(self, other):
