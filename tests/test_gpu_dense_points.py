@@ -2,10 +2,13 @@
 Horner and, limb for limb, against the single call; interpolate / interpolate_batch against a Lagrange model in Python integers
 (tests/dense_points_model.py) and, at the large sizes, by uniqueness; both sides of the segment decision; every stride combination;
 the refusals; both ops beside a commit and a proof in flight; and shamir secret sharing on top.  Every raw call writes into a buffer
-filled with a pattern, with a wider out_stride, and the padding is checked to be untouched."""
+filled with a pattern, with a wider out_stride, and the padding is checked to be untouched.  Section 9 takes the plans the small
+shapes above never select: a batch and a cut together, segments of several staged chunks, and a batch of interpolations that the entry
+point runs as two chunks of jobs (the kernels alone, at chosen grids and cuts: tests/test_gpu_dense_points_kernels.py)."""
 import ctypes as C
 import itertools
 import os
+import time
 
 import numpy as np
 import pytest
@@ -363,3 +366,86 @@ def test_shamir_batches_are_the_loop(zk, ora):
     assert np.array_equal(got, secrets_)
     for b in range(B):
         assert np.array_equal(zk.shamir.reconstruct_secret([(xs[i], ys[b, i]) for i in pick], 0), got[b])
+
+
+# ---- 9. plans the small shapes never select ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,n_in,n_x", [(3, 600, 5), (2, 769, 257)])
+def test_evaluation_with_a_batch_and_a_cut_together(N, ora, B, n_in, n_x):
+    """records at (job * segs + seg) * n_x + p with job > 0 and seg > 0 at once, at every stride combination"""
+    info = plan_info(N, EVALUATE, B, n_in, n_x)
+    assert info["segs"] > 1 and info["launches"] == 2, info
+    polys = np.stack([T.fill(T.FILLS_ARITH[b % 4], n_in, 42000 + b) for b in range(B)])
+    pts = np.stack([np.roll(points(n_x), b, axis=0) for b in range(B)])
+    pts[1:, n_x // 2] = T.fill("uniform_r", B - 1, 42100)                    # the jobs' points differ in more than their order
+    value = {(b, c): oracle_values(ora, polys[b], pts[c]) for b, c in {(b, b) for b in range(B)} | {(b, 0) for b in range(B)} | {(0, c) for c in range(B)}}
+    assert np.array_equal(raw(N, EVALUATE, polys, pts, n_x), np.stack([value[b, b] for b in range(B)]))
+    assert np.array_equal(raw(N, EVALUATE, polys, pts[0], n_x), np.stack([value[b, 0] for b in range(B)]))          # x_stride == 0
+    assert np.array_equal(raw(N, EVALUATE, polys[0], pts, n_x), np.stack([value[0, c] for c in range(B)]))          # in_stride == 0
+    assert np.array_equal(raw(N, EVALUATE, polys[0], pts[0], n_x, batch=B), np.stack([value[0, 0]] * B))            # both
+    assert not np.array_equal(value[1, 1], value[0, 0]) and not np.array_equal(value[1, 0], value[0, 0])
+
+
+def test_evaluation_segments_of_more_than_one_chunk(N, ora):
+    """20000 coefficients at 3 points: segments of two staged chunks, a last segment of one partial chunk, x^lo with lo up to 19968"""
+    n_in = 20000
+    info = plan_info(N, EVALUATE, 1, n_in, 3)
+    assert info["segs"] > 1 and -(-n_in // info["segs"]) > info["L"], info   # a segment is at least the mean: more than one chunk
+    assert n_in % info["L"] and info["segs"] <= 64
+    xs = points(3)
+    for kind in ("uniform_r", "top"):
+        coeffs = T.fill(kind, n_in, 42200)
+        assert np.array_equal(raw(N, EVALUATE, coeffs, xs, 3)[0], oracle_values(ora, coeffs, xs)), kind
+
+
+def test_interpolation_in_two_chunks(N, ora):
+    """n = 65, B = 65535: the entry point runs the batch as two launch chains and offsets d_in, d_x and d_out by the chunk's first job.
+    The values of job b are row b % 7 of seven rows (and its nodes row b % 5 of five) and seven is coprime to the chunk's length, so a
+    second chunk that starts at a wrong job -- 4 * ch.first * in_stride dropped, say, or x_stride, or out_stride -- reads or writes
+    rows that differ from the right ones; every output row is compared with the model's coefficients for its (b % 5, b % 7).  Then a
+    repeated node in the LAST job only (second chunk) and in job 0 only (first chunk).  The rows are built and compared on the device:
+    136 MB per buffer."""
+    import torch
+    t0 = time.perf_counter()
+    n, B = 65, 65535
+    info = plan_info(N, INTERPOLATE, B, n, n)
+    chunk = info["chunk"]
+    assert info["regime"] == 2 and 0 < chunk < B and chunk % 7 and chunk % 5, info
+    ctx = N.Context.get(0)
+    lib = N.lib()
+    xs5 = [nodes(n, 43000 + k, special=k % 2 == 0) for k in range(5)]
+    ys7 = [T.canonical(T.fill(("uniform_r", "top", "limb_edges")[k % 3], n, 43100 + k)) for k in range(7)]   # seven DISTINCT rows
+    want35 = np.stack([ora.fr_from_ints(c) for k in range(5) for c in lagrange_coefficients_many(xs5[k], ys7)])   # row 7 k5 + k7
+    assert len({w.tobytes() for w in want35}) == 35
+    b = torch.arange(B, device="cuda")
+    d_Y = dev(np.stack([ora.fr_from_ints(y) for y in ys7])).reshape(7, n, 4)[b % 7].contiguous()
+    d_X = dev(np.stack([ora.fr_from_ints(x) for x in xs5])).reshape(5, n, 4)[b % 5].contiguous()
+    d_want = dev(want35).reshape(35, n, 4)
+    stride = n + PAD
+    fill = int(np.array([FILL]).view(np.int64)[0])
+    out = torch.empty((B, stride, 4), dtype=torch.int64, device="cuda")
+
+    def call(x_stride):
+        out.fill_(fill)
+        torch.cuda.synchronize()                                             # torch's stream wrote the buffers; the library has its own
+        st = lib.zkhip_dense_points(ctx.handle, INTERPOLATE, B, d_Y.data_ptr(), n, n, d_X.data_ptr(), x_stride, n, out.data_ptr(), stride)
+        assert lib.zkhip_last_hip_error(ctx.handle) == 0
+        return st
+
+    def rows_are(which):
+        assert bool((out[:, n:] == fill).all()), "the padding of a wider out_stride was written"
+        bad = (out[:, :n] != d_want[which]).any(dim=2).any(dim=1).nonzero()
+        assert not len(bad), "%d rows differ, the first is job %d (the chunk holds %d jobs)" % (len(bad), int(bad[0]), chunk)
+
+    assert call(0) == N.ZKHIP_OK                                             # shared nodes: row 0 of d_X
+    rows_are(b % 7)
+    assert call(n) == N.ZKHIP_OK                                             # nodes of the job's own
+    own = (b % 5) * 7 + b % 7
+    rows_are(own)
+    for job in (B - 1, 0):
+        kept = d_X[job, 7].clone()
+        d_X[job, 7] = d_X[job, 3]
+        assert call(n) == N.ERR_ARG, job
+        d_X[job, 7] = kept
+    assert call(n) == N.ZKHIP_OK
+    rows_are(own)
+    print("interpolation in two chunks (B = %d, chunk %d): %.2f s" % (B, chunk, time.perf_counter() - t0))
