@@ -1,7 +1,7 @@
 // The HOST-only product code of libzkhip that does real arithmetic -- csrc/host_g1.hpp (the MSM's epilogue: XYZZ group law, the
 // weighted double-and-add sweep, affine conversion), csrc/host_fr.hpp (Fr, the interpolation matrices, SHA-256, the Fiat-Shamir
-// transcript), csrc/msm_geometry.hpp (the digit windows / bucket sets of a pass), csrc/host_util.hpp (the thread pool), csrc/tunables.hpp
-// (the environment switches' parser) -- compiled with
+// transcript), csrc/msm_geometry.hpp (the digit windows / bucket sets of a pass), csrc/msm_small_fold.hpp (the short path's host fold),
+// csrc/host_util.hpp (the thread pool), csrc/tunables.hpp (the environment switches' parser) -- compiled with
 // g++ -fsanitize=address,undefined (sanitizers on the CPU build only) and checked against the CPU oracle.  Run twice by
 // tests/test_host_sanitizers_cpu.py: the outputs must be identical (determinism).  Exit code 0 = everything matched.
 #include <cstdio>
@@ -13,6 +13,7 @@
 #include "../../zk-cryptography_amd/csrc/host_g1.hpp"
 #include "../../zk-cryptography_amd/csrc/host_util.hpp"
 #include "../../zk-cryptography_amd/csrc/msm_geometry.hpp"
+#include "../../zk-cryptography_amd/csrc/msm_small_fold.hpp"
 #include "../../zk-cryptography_amd/csrc/tunables.hpp"
 extern "C" {
 #include "../../oracle/zkoracle.h"
@@ -205,6 +206,51 @@ static void test_geometry() {
     (void)msm_build_geometry(too_many, false, 0, g);                   // any status, but no overrun (the sanitizers watch)
 }
 
+// the short path's host fold: 3 instances x 2 problems of 5 and 3 planes (planes = 5: the narrower problem's rows end in two terms nobody
+// may read), results to every fifth place from 2 on -- each the weighted sum of its plane sums done by hand, and the oracle's sum; every
+// other place of the outputs untouched; serially and on a pool of 4
+static void test_small_fold() {
+    zk::MsmSmallGeometry g = {};
+    g.nprob = 2; g.planes = 5; g.hi[0] = 5; g.hi[1] = 3;
+    const uint32_t count = 3 * g.nprob;
+    g1_jac_t gen, id; ora_g1_generator(&gen); ora_g1_identity(&id);
+    std::vector<zkhost::Xyzz> terms(count * g.planes);
+    std::vector<g1_jac_t> want(count, id);
+    for (uint32_t k = 0; k < count; ++k)
+        for (uint32_t t = 0; t < g.planes; ++t) {
+            uint64_t s[4] = {rng(), rng(), rng(), rng() >> 2};
+            g1_jac_t p; ora_g1_mul_bigint(&p, &gen, s, 4);
+            if ((k + t) % 4 == 3) p = id;                                // identities among the plane sums
+            terms[k * g.planes + t] = from_jac(p);
+            if (t >= g.hi[k % g.nprob]) continue;                        // behind the problem's planes: not part of its sum
+            uint64_t e[4] = {1ULL << t, 0, 0, 0};
+            g1_jac_t term, acc; ora_g1_mul_bigint(&term, &p, e, 4); ora_g1_add(&acc, &want[k], &term); want[k] = acc;
+        }
+    auto out_of = [](uint32_t k) { return (size_t)5 * k + 2; };
+    ZkHostPool four(4);
+    for (ZkHostPool* pool : {(ZkHostPool*)nullptr, &four}) {
+        std::vector<uint64_t> xy(12 * 5 * count, 0xababababababababULL);
+        std::vector<uint8_t> inf(5 * count, 0xab);
+        zk::msm_small_fold((const char*)terms.data(), g, count, pool, xy.data(), inf.data(), out_of);
+        for (uint32_t k = 0; k < count; ++k) {
+            const uint32_t hi = g.hi[k % g.nprob];
+            std::vector<zkhost::Xyzz> pts(terms.begin() + k * g.planes, terms.begin() + k * g.planes + hi);
+            std::vector<uint32_t> exps(hi);
+            for (uint32_t t = 0; t < hi; ++t) exps[t] = t;
+            const zkhost::Xyzz sum = zkhost::weighted_sum_pow2(pts, exps);
+            uint64_t hand[12];
+            const bool finite = zkhost::xyzz_to_affine(sum, hand);
+            EXPECT(std::memcmp(hand, xy.data() + 12 * out_of(k), 96) == 0 && inf[out_of(k)] == (finite ? 0 : 1));
+            EXPECT(same_point(sum, want[k]));
+        }
+        for (size_t o = 0; o < inf.size(); ++o) {
+            if (o % 5 == 2) continue;
+            EXPECT(inf[o] == 0xab);
+            for (int i = 0; i < 12; ++i) EXPECT(xy[12 * o + i] == 0xababababababababULL);
+        }
+    }
+}
+
 static void test_pool() {
     ZkHostPool pool(3);
     for (int r = 0; r < 2000; ++r) {
@@ -266,6 +312,7 @@ int main() {
     test_transcript();
     test_g1();
     test_geometry();
+    test_small_fold();
     test_pool();
     test_tunables();
     std::printf("digest %016llx\n%s\n", (unsigned long long)g_digest, g_failed ? "FAILED" : "ok");

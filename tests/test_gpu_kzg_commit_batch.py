@@ -203,6 +203,27 @@ def test_commitment_batch_short_route_mixed_lengths(zk, ora):
         _is(singles[k], want[:12].copy(), bool(want[12]))
 
 
+def test_commitment_batch_short_route_launches_per_length(zk, ora):
+    """the short route's launch shape: one plane-sums and one reduce launch per distinct non-zero length of the chunk and nothing of the
+    single call's or the bucket pipeline's, where the loop of single commitments is one short-path call per non-empty polynomial"""
+    from test_gpu_kzg_open_batch import _profiled
+    srs = zk.UnivariateKZG.generate_srs(ora.random_fr(1, 7420)[0], 255)
+    lens = [17, 1, 256, 17, 0, 256]
+    assert len(srs) == 256 and _plan(256, lens, True)[0] == ROUTE_SHORT
+    coeffs = ora.random_fr(256 + 8, 7421)
+    polys = [zk.DenseUnivariatePolynomial(np.ascontiguousarray(coeffs[k:k + n])) for k, n in enumerate(lens)]
+    zk.UnivariateKZG.commitment(polys[0], srs)           # builds the table: its launches are not counted below
+    names = ("commit_polys_planes", "commit_polys_reduce", "msm_small", "msm_accumulate")
+    got, c_batch = _profiled(lambda: zk.UnivariateKZG.commitment_batch(polys, srs), names)
+    singles, c_loop = _profiled(lambda: [zk.UnivariateKZG.commitment(p, srs) for p in polys], names)
+    assert c_batch == {"commit_polys_planes": 3, "commit_polys_reduce": 3, "msm_small": 0, "msm_accumulate": 0}
+    assert c_loop == {"commit_polys_planes": 0, "commit_polys_reduce": 0, "msm_small": 5, "msm_accumulate": 0}
+    _same_points(got, singles)
+    for g, w in zip(got, singles):
+        assert np.array_equal(g.xy, w.xy)
+    assert got[4].infinity and not got[4].xy.any()
+
+
 # ---- 4. skewed scalars and shared structure ----------------------------------------------------------------------------------------------
 def _skewed(zk, ora, kind, n, seed):
     rng = np.random.default_rng(seed)

@@ -52,6 +52,7 @@ def lib():
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
         _lib.zkhip_status_string.restype = C.c_char_p
+        _lib.zkhip_g2_prepared_bytes.restype = C.c_size_t
         _lib.zkhip_sumcheck_plan_log_blocks.argtypes = [C.c_size_t]
         # the prover's hot calls take plain integers for their pointers (no ctypes object per argument: host time between a
         # proof and the next call's first launch is GPU idle time)

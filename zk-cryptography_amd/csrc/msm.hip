@@ -19,6 +19,7 @@
 #include "horner_jobs_kernels.hpp"
 #include "mle_kernels.hpp"
 #include "msm_kernels.hpp"
+#include "msm_small_fold.hpp"
 #include "srs_kernels.hpp"
 #include "tunables.hpp"
 #include "univariate_open_plan.hpp"
@@ -602,59 +603,45 @@ extern "C" int zkhip_srs_level_tables(zkhip_ctx* c, const uint64_t* d_folded_xy,
 
 // Commits of at most MSM_SMALL_MAX scalars against a shifted-SRS table: the plane sums of msm_kernels.hpp "commits of a few thousand
 // points" -- two launches, one copy, a host epilogue of <= 20 doublings.  ZKHIP_MSM_SMALL=0 keeps the bucket pipeline (A/B runs).
-// problem j: n[j] scalars from sc_off[j] on against the table at tab_off[j] (entries) of stride[j] points with the widths lw[j]; results
-// h_out_xy[12 j], h_out_inf[j]
-struct MsmSmallProblem { size_t n, stride, tab_off, sc_off; MsmLevelWidths lw; };
+// The launches' arguments: a geometry (msm_small_plan.hpp: the problems, the slot rule, the workspace) and the caller's pointers.
+static MsmSmallArgs msm_small_args(const MsmSmallGeometry& g, const uint32_t* table, const uint8_t* inf, const uint64_t* scalars, void* partials, void* terms) {
+    MsmSmallArgs a = {};
+    a.table = table; a.inf = inf; a.scalars = scalars; a.partials = (uint32_t*)partials; a.terms = (uint64_t*)terms;
+    a.nprob = g.nprob; a.planes = g.planes; a.total_slots = g.total_slots;
+    std::memcpy(a.n, g.n, sizeof a.n); std::memcpy(a.stride, g.stride, sizeof a.stride); std::memcpy(a.W, g.W, sizeof a.W);
+    std::memcpy(a.hi, g.hi, sizeof a.hi); std::memcpy(a.n_hi, g.n_hi, sizeof a.n_hi); std::memcpy(a.tab_off, g.tab_off, sizeof a.tab_off);
+    std::memcpy(a.sc_off, g.sc_off, sizeof a.sc_off); std::memcpy(a.slot_first, g.slot_first, sizeof a.slot_first);
+    return a;
+}
+// The end of a chunk: ONE copy of its terms (and what lies behind them) into the pinned buffer behind ONE synchronisation ...
+static int msm_small_fetch(zkhip_ctx* c, const void* d_terms, size_t bytes) {
+    ZK_HIP(c, hipGetLastError());
+    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, d_terms, bytes, hipMemcpyDeviceToHost, c->stream));
+    ZK_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKHIP_OK;
+}
+// ... and the host fold of its `count` problems (msm_small_fold.hpp): result k to out_of(k)
+template <class OutOf>
+static void msm_small_finish(zkhip_ctx* c, const MsmSmallGeometry& g, uint32_t count, uint64_t* h_out_xy, uint8_t* h_out_inf, OutOf out_of) {
+    msm_small_fold((const char*)c->msm_pin[0].ptr, g, count, count > 1 ? c->pool() : nullptr, h_out_xy, h_out_inf, out_of);
+}
+// problem j of pr: results h_out_xy[12 j], h_out_inf[j]
 static int msm_small_batch(zkhip_ctx* c, const uint32_t* d_table, const uint8_t* d_inf, const uint64_t* d_scalars, const MsmSmallProblem* pr,
                            uint32_t nprob, uint64_t* h_out_xy, uint8_t* h_out_inf) {
     if (nprob == 0 || nprob > (uint32_t)MSM_SMALL_PROBS) return ZKHIP_ERR_SHAPE;
-    MsmSmallArgs a = {};
-    a.table = d_table; a.scalars = d_scalars; a.inf = d_inf; a.nprob = nprob;
-    size_t total_pairs = 0;
-    for (uint32_t j = 0; j < nprob; ++j) {
-        a.n[j] = (uint32_t)pr[j].n; a.stride[j] = (uint32_t)pr[j].stride; a.W[j] = pr[j].lw.W; a.hi[j] = pr[j].lw.hi; a.n_hi[j] = pr[j].lw.n_hi;
-        a.tab_off[j] = (uint32_t)pr[j].tab_off; a.sc_off[j] = (uint32_t)pr[j].sc_off;
-        a.planes = std::max(a.planes, pr[j].lw.hi);
-        total_pairs += pr[j].n * pr[j].lw.W;
-    }
-    // ~2 waves per SIMD in all, dealt to the problems by their share of the pairs (at least one slot each, at most a wave per 64 pairs)
-    const size_t budget = std::max<size_t>(1, 2048 / a.planes);
-    for (uint32_t j = 0; j < nprob; ++j) {
-        const size_t pairs = pr[j].n * pr[j].lw.W, chunks = (pairs + 63) / 64;
-        const size_t share = total_pairs ? (budget * pairs + total_pairs - 1) / total_pairs : 1;
-        a.slot_first[j + 1] = a.slot_first[j] + (uint32_t)std::max<size_t>(1, std::min(chunks, share));
-    }
-    a.total_slots = a.slot_first[nprob];
-    const size_t part_bytes = (size_t)a.planes * a.total_slots * 256, terms_bytes = (size_t)nprob * a.planes * 192;
-    ZK_TRY(c->reserve_ws(part_bytes + 256 + terms_bytes));
-    a.partials = (uint32_t*)c->ws.ptr;
-    a.terms = (uint64_t*)((char*)c->ws.ptr + ((part_bytes + 255) & ~(size_t)255));
+    const MsmSmallGeometry g = msm_small_plan(pr, nprob, 1);
+    const size_t terms_bytes = g.terms_bytes(1);
+    const MsmSmallCarve cv = msm_small_carve(g.part_bytes(1), terms_bytes);
+    ZK_TRY(c->reserve_ws(cv.ws_bytes));
+    ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
+    const MsmSmallArgs a = msm_small_args(g, d_table, d_inf, d_scalars, c->ws.ptr, (char*)c->ws.ptr + cv.terms_off);
     {
-        ProfScope ps(c, "msm_small", 128.0 * (double)total_pairs / std::max<uint32_t>(1, a.W[0]));
+        ProfScope ps(c, "msm_small", 128.0 * (double)g.total_pairs / std::max<uint32_t>(1, a.W[0]));
         hipLaunchKernelGGL(msm_small_planes_kernel, dim3(a.total_slots, a.planes), dim3(64), 0, c->stream, a);
         hipLaunchKernelGGL(msm_small_reduce_kernel, dim3(a.planes, nprob), dim3(64), 0, c->stream, a);
     }
-    ZK_HIP(c, hipGetLastError());
-    ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
-    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, a.terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const char* pin = (const char*)c->msm_pin[0].ptr;
-    auto finish = [&](uint32_t j) {                                  // the weighted sum of a problem's plane sums: <= 20 doublings
-        std::vector<zkhost::Xyzz> pts(a.hi[j]);
-        std::vector<uint32_t> exps(a.hi[j]);
-        for (uint32_t t = 0; t < a.hi[j]; ++t) {
-            std::memcpy(&pts[t], pin + 192 * ((size_t)j * a.planes + t), 192);
-            exps[t] = t;
-        }
-        const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
-        h_out_inf[j] = zkhost::xyzz_to_affine(res, h_out_xy + 12 * (size_t)j) ? 0 : 1;
-    };
-    ZkHostPool* pool = nprob > 1 ? c->pool() : nullptr;
-    if (!pool) {
-        for (uint32_t j = 0; j < nprob; ++j) finish(j);
-    } else {
-        pool->run(nprob, [&](unsigned j) { finish(j); });
-    }
+    ZK_TRY(msm_small_fetch(c, a.terms, terms_bytes));
+    msm_small_finish(c, g, nprob, h_out_xy, h_out_inf, [](uint32_t j) { return (size_t)j; });
     return ZKHIP_OK;
 }
 static int msm_commit_small(zkhip_ctx* c, const uint32_t* d_table, size_t stride, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n,
@@ -988,60 +975,39 @@ extern "C" int zkhip_kzg_open_tables(zkhip_ctx* c, const uint64_t* d_evals, size
 // stay of the size a few dozen single openings' worth, whatever B a caller passes; 64 openings are >= 512 (opening, round) problems
 // of <= 14 planes each, several waves for every SIMD of the chip, so a larger chunk has nothing left to fill.
 constexpr uint32_t OPEN_BATCH_CHUNK = 64;
-constexpr size_t OPEN_BATCH_LANE_PAIRS = 32;      // most (point, window) pairs a lane of the batched plane sums walks
 static int kzg_open_small_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* const* h_eval_ptrs, size_t n, uint32_t n_vars, const uint64_t* h_points,
                                 const uint8_t* d_folded_inf, const uint32_t* d_level_tables, uint64_t* h_evaluations, uint64_t* h_proofs_xy,
                                 uint8_t* h_proofs_inf, uint32_t chunk_max) {
     if (n_vars > (uint32_t)MSM_SMALL_PROBS || chunk_max == 0) return ZKHIP_ERR_SHAPE;
     const uint32_t bc_max = std::min(batch, chunk_max);
-    // the rounds' geometry, once for the whole batch: round j commits n >> (j + 1) quotients against level j as zkhip_srs_level_tables laid it out
-    MsmSmallArgs a = {};
-    a.table = d_level_tables; a.inf = d_folded_inf; a.nprob = n_vars;
-    size_t entry = 0, lvl_off = 0, total_pairs = 0;
+    // the rounds, once for the whole batch: round j commits n >> (j + 1) quotients against level j as zkhip_srs_level_tables laid it out;
+    // the slots are dealt over the WHOLE chunk (msm_small_plan.hpp)
+    MsmSmallProblem sp[MSM_SMALL_PROBS];
+    size_t entry = 0, lvl_off = 0;
     for (uint32_t j = 0; j < n_vars; ++j) {
         const size_t h = n >> (j + 1);
-        const MsmLevelWidths lw = msm_level_table_widths(h, n - 1);
-        a.n[j] = (uint32_t)h; a.stride[j] = (uint32_t)h; a.W[j] = lw.W; a.hi[j] = lw.hi; a.n_hi[j] = lw.n_hi;
-        a.tab_off[j] = (uint32_t)entry; a.sc_off[j] = (uint32_t)lvl_off;
-        a.planes = std::max(a.planes, lw.hi);
-        total_pairs += h * lw.W;
-        entry += (size_t)lw.W * h;
+        sp[j] = {h, h, entry, lvl_off, msm_level_table_widths(h, n - 1)};
+        entry += (size_t)sp[j].lw.W * h;
         lvl_off += h;
     }
-    // the slots: msm_small_batch's ~2 waves per SIMD in all, dealt over the WHOLE chunk -- an opening's share of them goes to its rounds by
-    // their pairs, at least one slot per (opening, round).  One opening: the single call's split.  From a dozen openings on the minimum
-    // alone is more than the budget: one wave per (opening, round, plane), and the chip is full of them.
-    // But no lane walks more than OPEN_BATCH_LANE_PAIRS pairs: a full chip is as fast as its longest wave lets it be, and with one slot per
-    // round the first round of a 2^12 opening is ONE wave of 608 pairs per lane beside waves of a handful -- measured at B = 64: 32 ms in
-    // this launch, no faster per opening than the loop, against 0.31 ms per opening at B = 16, whose share still split the round five ways
-    // (profiles/open_batch/NOTES.md).  The single call's own split is 8-17 pairs per lane: the cap changes nothing for B <= 2.
-    const size_t budget = std::max<size_t>(1, 2048 / a.planes / bc_max);
-    for (uint32_t j = 0; j < n_vars; ++j) {
-        const size_t pairs = (size_t)a.n[j] * a.W[j], chunks = (pairs + 63) / 64;
-        const size_t share = (budget * pairs + total_pairs - 1) / total_pairs, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
-        a.slot_first[j + 1] = a.slot_first[j] + (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(share, capped)));
-    }
-    a.total_slots = a.slot_first[n_vars];
+    const MsmSmallGeometry g = msm_small_plan(sp, n_vars, bc_max);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // staging (pinned -> aux): the chunk's table pointers, then its points
     const size_t o_pts = al((size_t)bc_max * 8), stage_bytes = o_pts + al((size_t)bc_max * n_vars * 32);
     const size_t q_stride = n, ping_stride = n / 2, pong_stride = n / 4;             // scalars per opening
     const size_t o_q = stage_bytes, o_ping = o_q + al(bc_max * q_stride * 32), o_pong = o_ping + al(bc_max * ping_stride * 32);
     ZK_TRY(c->reserve_aux(o_pong + al(bc_max * pong_stride * 32)));
-    const size_t part_bytes = al((size_t)bc_max * a.planes * a.total_slots * 256);
-    const size_t terms_bytes = (size_t)bc_max * n_vars * a.planes * 192, out_bytes = al(terms_bytes + (size_t)bc_max * 32);    // terms | evaluations: ONE copy
-    ZK_TRY(c->reserve_ws(part_bytes + out_bytes));
+    const size_t out_bytes = al(g.terms_bytes(bc_max) + (size_t)bc_max * 32);    // terms | evaluations: ONE copy
+    const MsmSmallCarve cv = msm_small_carve(g.part_bytes(bc_max), out_bytes);
+    ZK_TRY(c->reserve_ws(cv.ws_bytes));
     ZK_TRY(c->reserve_msm_pin(0, out_bytes + stage_bytes));
     char* aux = (char*)c->aux.ptr;
     char* pin = (char*)c->msm_pin[0].ptr;
-    a.partials = (uint32_t*)c->ws.ptr;
-    a.terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
-    a.scalars = (const uint64_t*)(aux + o_q);
-    ZkHostPool* pool = c->pool();
+    const MsmSmallArgs a = msm_small_args(g, d_level_tables, d_folded_inf, (const uint64_t*)(aux + o_q), c->ws.ptr, (char*)c->ws.ptr + cv.terms_off);
     for (uint32_t b0 = 0; b0 < batch; b0 += bc_max) {
         const uint32_t bc = std::min(bc_max, batch - b0);
-        uint64_t* d_evals_out = a.terms + 24 * (size_t)bc * n_vars * a.planes;
-        const size_t copy_bytes = (size_t)bc * n_vars * a.planes * 192 + (size_t)bc * 32;
+        const size_t terms_bytes = g.terms_bytes(bc);
+        uint64_t* d_evals_out = a.terms + terms_bytes / 8;
         // (the previous chunk's upload has ended: every chunk ends in a synchronisation)
         std::memcpy(pin + out_bytes, h_eval_ptrs + b0, (size_t)bc * 8);
         std::memcpy(pin + out_bytes + o_pts, h_points + 4 * (size_t)n_vars * b0, (size_t)bc * n_vars * 32);
@@ -1053,44 +1019,25 @@ static int kzg_open_small_batch(zkhip_ctx* c, uint32_t batch, const uint64_t* co
                                (uint64_t*)(aux + o_pong), pong_stride, d_evals_out);
         }
         {
-            ProfScope ps(c, "open_batch_planes", 128.0 * (double)total_pairs * bc);
+            ProfScope ps(c, "open_batch_planes", 128.0 * (double)g.total_pairs * bc);
             hipLaunchKernelGGL(msm_small_batch_planes_kernel, dim3(a.total_slots, a.planes, bc), dim3(64), 0, c->stream, a, q_stride);
         }
         {
             ProfScope ps(c, "open_batch_reduce", 0.0);
             hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(a.planes, n_vars, bc), dim3(64), 0, c->stream, a);
         }
-        ZK_HIP(c, hipGetLastError());
-        ZK_HIP(c, hipMemcpyAsync(pin, a.terms, copy_bytes, hipMemcpyDeviceToHost, c->stream));
-        ZK_HIP(c, hipStreamSynchronize(c->stream));
-        // the single call's host fold per (opening, round): the weighted sum of its plane sums, <= 20 doublings.  (With the profile on,
-        // events on the now idle stream bracket it: their distance is the host time.)
+        ZK_TRY(msm_small_fetch(c, a.terms, terms_bytes + (size_t)bc * 32));
+        // the host fold per (opening, round); with the profile on, events on the now idle stream bracket it: their distance is the host time
         ProfScope ps(c, "open_batch_fold", 0.0);
-        auto finish = [&](uint32_t k) {
-            const uint32_t j = k % n_vars;
-            std::vector<zkhost::Xyzz> pts(a.hi[j]);
-            std::vector<uint32_t> exps(a.hi[j]);
-            for (uint32_t t = 0; t < a.hi[j]; ++t) {
-                std::memcpy(&pts[t], pin + 192 * ((size_t)k * a.planes + t), 192);
-                exps[t] = t;
-            }
-            const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
-            const size_t o = (size_t)b0 * n_vars + k;
-            h_proofs_inf[o] = zkhost::xyzz_to_affine(res, h_proofs_xy + 12 * o) ? 0 : 1;
-        };
-        if (!pool) {
-            for (uint32_t k = 0; k < bc * n_vars; ++k) finish(k);
-        } else {
-            pool->run(bc * n_vars, [&](unsigned k) { finish(k); });
-        }
-        std::memcpy(h_evaluations + 4 * (size_t)b0, pin + (size_t)bc * n_vars * a.planes * 192, (size_t)bc * 32);
+        msm_small_finish(c, g, bc * n_vars, h_proofs_xy, h_proofs_inf, [&](uint32_t k) { return (size_t)b0 * n_vars + k; });
+        std::memcpy(h_evaluations + 4 * (size_t)b0, pin + terms_bytes, (size_t)bc * 32);
     }
     return ZKHIP_OK;
 }
 // The commits of one round of a CHUNK of PLONK proofs (zkhip_plonk_prove_batch, ctx.hpp): m <= 3 polynomials per proof, polynomial j of
 // proof b being lens[j] scalars from d_scalars + 4 (b q_stride + sc_off[j]) on, all against the one shifted-SRS table.  ONE launch of the
 // plane sums with the proof as grid.z, one of the reduce, one copy, one synchronisation -- which also completes whatever the caller
-// enqueued before -- and the weighted_sum_pow2 epilogues on the context's pool.  Result (b, j) goes to h_out_xy + 12 (b out_stride + j),
+// enqueued before -- and the host folds on the context's pool.  Result (b, j) goes to h_out_xy + 12 (b out_stride + j),
 // h_out_inf[b out_stride + j].  The group elements are those of any other commit path, so are the affine points.
 bool zk_msm_commit_batch_serves(size_t n_points, size_t longest) {
     return msm_small_on() && longest <= MSM_SMALL_MAX && n_points * msm_table_widths(n_points).W < ((size_t)1 << 31);
@@ -1111,58 +1058,24 @@ int zk_msm_commit_batch(zkhip_ctx* c, const void* d_table_with_header, const uin
     const uint32_t* d_table = table_check(c, d_table_with_header, ZK_TABLE_SHIFTED_SRS, n_points, &trc);
     if (!d_table) return trc;
     const MsmLevelWidths lw = msm_table_widths(n_points);
-    MsmSmallArgs a = {};
-    a.table = d_table; a.scalars = d_scalars; a.inf = d_points_inf; a.nprob = m; a.planes = lw.hi;
-    size_t total_pairs = 0;
-    for (uint32_t j = 0; j < m; ++j) {
-        a.n[j] = (uint32_t)lens[j]; a.stride[j] = (uint32_t)n_points; a.W[j] = lw.W; a.hi[j] = lw.hi; a.n_hi[j] = lw.n_hi;
-        a.tab_off[j] = 0; a.sc_off[j] = (uint32_t)sc_off[j];
-        total_pairs += lens[j] * lw.W;
-    }
-    // the slots of kzg_open_small_batch: ~2 waves per SIMD over the whole chunk, a proof's share dealt to its polynomials by their pairs,
-    // at least one slot each -- and no lane walks more than OPEN_BATCH_LANE_PAIRS pairs, however many proofs share the chip
-    const size_t budget = std::max<size_t>(1, 2048 / a.planes / batch);
-    for (uint32_t j = 0; j < m; ++j) {
-        const size_t pairs = lens[j] * lw.W, chunks = (pairs + 63) / 64;
-        const size_t share = (budget * pairs + total_pairs - 1) / total_pairs, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
-        a.slot_first[j + 1] = a.slot_first[j] + (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(share, capped)));
-    }
-    a.total_slots = a.slot_first[m];
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t part_bytes = al((size_t)batch * a.planes * a.total_slots * 256), terms_bytes = (size_t)batch * m * a.planes * 192;
-    ZK_TRY(c->reserve_ws(part_bytes + al(terms_bytes)));
+    MsmSmallProblem sp[3];
+    for (uint32_t j = 0; j < m; ++j) sp[j] = {lens[j], n_points, 0, sc_off[j], lw};
+    const MsmSmallGeometry g = msm_small_plan(sp, m, batch);            // the slots: dealt over the whole chunk of proofs
+    const size_t terms_bytes = g.terms_bytes(batch);
+    const MsmSmallCarve cv = msm_small_carve(g.part_bytes(batch), terms_bytes);
+    ZK_TRY(c->reserve_ws(cv.ws_bytes));
     ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
-    a.partials = (uint32_t*)c->ws.ptr;
-    a.terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
+    const MsmSmallArgs a = msm_small_args(g, d_table, d_points_inf, d_scalars, c->ws.ptr, (char*)c->ws.ptr + cv.terms_off);
     {
-        ProfScope ps(c, "plonk_batch_commit_planes", 128.0 * (double)total_pairs * batch / std::max<uint32_t>(1, lw.W));
+        ProfScope ps(c, "plonk_batch_commit_planes", 128.0 * (double)g.total_pairs * batch / std::max<uint32_t>(1, lw.W));
         hipLaunchKernelGGL(msm_small_commit_batch_planes_kernel, dim3(a.total_slots, a.planes, batch), dim3(64), 0, c->stream, a, q_stride);
     }
     {
         ProfScope ps(c, "plonk_batch_commit_reduce", 0.0);
         hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(a.planes, m, batch), dim3(64), 0, c->stream, a);
     }
-    ZK_HIP(c, hipGetLastError());
-    ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, a.terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
-    ZK_HIP(c, hipStreamSynchronize(c->stream));
-    const char* pin = (const char*)c->msm_pin[0].ptr;
-    auto finish = [&](uint32_t k) {                                  // k = b m + j: the weighted sum of its plane sums, <= 20 doublings
-        std::vector<zkhost::Xyzz> pts(lw.hi);
-        std::vector<uint32_t> exps(lw.hi);
-        for (uint32_t t = 0; t < lw.hi; ++t) {
-            std::memcpy(&pts[t], pin + 192 * ((size_t)k * a.planes + t), 192);
-            exps[t] = t;
-        }
-        const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
-        const size_t o = (size_t)(k / m) * out_stride + k % m;
-        h_out_inf[o] = zkhost::xyzz_to_affine(res, h_out_xy + 12 * o) ? 0 : 1;
-    };
-    ZkHostPool* pool = batch * m > 1 ? c->pool() : nullptr;
-    if (!pool) {
-        for (uint32_t k = 0; k < batch * m; ++k) finish(k);
-    } else {
-        pool->run(batch * m, [&](unsigned k) { finish(k); });
-    }
+    ZK_TRY(msm_small_fetch(c, a.terms, terms_bytes));
+    msm_small_finish(c, g, batch * m, h_out_xy, h_out_inf, [&](uint32_t k) { return (size_t)(k / m) * out_stride + k % m; });      // k = b m + j
     return ZKHIP_OK;
 }
 
@@ -1205,13 +1118,11 @@ static int commit_polys_one(zkhip_ctx* c, const uint64_t* d_points_xy, const uin
 }
 // SHORT route: a chunk's polynomials in the order of their lengths; every run of one length (a CLASS) is one launch of the plane sums
 // with the polynomial as grid.z and one of the reduce, all classes of the chunk in front of ONE copy and ONE synchronisation; then the
-// weighted sums on the pool (zk_msm_commit_batch does the same for PLONK's fixed-stride layout).  A class's slots: kzg_open_small_batch's
-// rule -- ~2 waves per SIMD over the whole chunk, and no lane walks more than OPEN_BATCH_LANE_PAIRS pairs.
+// weighted sums on the pool (zk_msm_commit_batch does the same for PLONK's fixed-stride layout).
 // ptrs / len / where: the non-empty polynomials, their lengths and their places in the outputs.
 static int commit_polys_short(zkhip_ctx* c, const uint32_t* d_table, const uint8_t* d_points_inf, size_t n_points, const CppPlan& plan,
                               const uint64_t* const* ptrs, const size_t* len, const uint32_t* where, uint64_t* h_out_xy, uint8_t* h_out_inf) {
     const MsmLevelWidths lw = msm_table_widths(n_points);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     for (const CppChunk& ch : plan.chunks) {
         static_assert(CPP_SMALL_CHUNK <= (uint32_t)MSM_MAX_PROBLEMS, "a chunk's pointers are one MsmPtrTable");
         uint32_t order[CPP_SMALL_CHUNK];
@@ -1219,60 +1130,36 @@ static int commit_polys_short(zkhip_ctx* c, const uint32_t* d_table, const uint8
         std::stable_sort(order, order + ch.count, [&](uint32_t x, uint32_t y) { return len[x] < len[y]; });
         MsmPtrTable pt = {};
         for (uint32_t k = 0; k < ch.count; ++k) pt.p[k] = ptrs[order[k]];
-        struct Class { uint32_t first, count, slots; size_t part_off; };
+        struct Class { uint32_t first, count; size_t part_off; MsmSmallGeometry g; };
         std::vector<Class> classes;
-        const size_t budget = std::max<size_t>(1, 2048 / lw.hi / ch.count);
         size_t part_bytes = 0;
         for (uint32_t k = 0; k < ch.count;) {
             uint32_t e = k + 1;
             while (e < ch.count && len[order[e]] == len[order[k]]) ++e;
-            const size_t pairs = len[order[k]] * lw.W, chunks = (pairs + 63) / 64, capped = (chunks + OPEN_BATCH_LANE_PAIRS - 1) / OPEN_BATCH_LANE_PAIRS;
-            const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min(chunks, std::max(budget, capped)));
-            classes.push_back({k, e - k, slots, part_bytes});
-            part_bytes += al((size_t)(e - k) * lw.hi * slots * 256);
+            const MsmSmallProblem one = {len[order[k]], n_points, 0, 0, lw};
+            classes.push_back({k, e - k, part_bytes, msm_small_plan(&one, 1, ch.count)});      // the slots: dealt over the whole chunk
+            part_bytes += classes.back().g.part_bytes(e - k);
             k = e;
         }
         const size_t terms_bytes = (size_t)ch.count * lw.hi * 192;
-        ZK_TRY(c->reserve_ws(part_bytes + al(terms_bytes)));
+        const MsmSmallCarve cv = msm_small_carve(part_bytes, terms_bytes);
+        ZK_TRY(c->reserve_ws(cv.ws_bytes));
         ZK_TRY(c->reserve_msm_pin(0, terms_bytes));
-        uint64_t* d_terms = (uint64_t*)((char*)c->ws.ptr + part_bytes);
+        uint64_t* d_terms = (uint64_t*)((char*)c->ws.ptr + cv.terms_off);
         for (const Class& cl : classes) {
-            MsmSmallArgs a = {};
-            a.table = d_table; a.inf = d_points_inf; a.nprob = 1; a.planes = lw.hi; a.total_slots = cl.slots;
-            a.partials = (uint32_t*)((char*)c->ws.ptr + cl.part_off);
-            a.terms = d_terms + 24 * (size_t)cl.first * lw.hi;
-            a.n[0] = (uint32_t)len[order[cl.first]]; a.stride[0] = (uint32_t)n_points; a.W[0] = lw.W; a.hi[0] = lw.hi; a.n_hi[0] = lw.n_hi;
-            a.slot_first[1] = cl.slots;
+            const MsmSmallArgs a = msm_small_args(cl.g, d_table, d_points_inf, nullptr, (char*)c->ws.ptr + cl.part_off, d_terms + 24 * (size_t)cl.first * lw.hi);
             {
                 ProfScope ps(c, "commit_polys_planes", 128.0 * (double)a.n[0] * cl.count);
-                hipLaunchKernelGGL(msm_small_commit_polys_planes_kernel, dim3(cl.slots, lw.hi, cl.count), dim3(64), 0, c->stream, a, pt, cl.first);
+                hipLaunchKernelGGL(msm_small_commit_polys_planes_kernel, dim3(a.total_slots, lw.hi, cl.count), dim3(64), 0, c->stream, a, pt, cl.first);
             }
             {
                 ProfScope ps(c, "commit_polys_reduce", 0.0);
                 hipLaunchKernelGGL(msm_small_batch_reduce_kernel, dim3(lw.hi, 1, cl.count), dim3(64), 0, c->stream, a);
             }
         }
-        ZK_HIP(c, hipGetLastError());
-        ZK_HIP(c, hipMemcpyAsync(c->msm_pin[0].ptr, d_terms, terms_bytes, hipMemcpyDeviceToHost, c->stream));
-        ZK_HIP(c, hipStreamSynchronize(c->stream));
-        const char* pin = (const char*)c->msm_pin[0].ptr;
-        auto finish = [&](uint32_t k) {                                  // the weighted sum of polynomial order[k]'s plane sums: <= 20 doublings
-            std::vector<zkhost::Xyzz> pts(lw.hi);
-            std::vector<uint32_t> exps(lw.hi);
-            for (uint32_t t = 0; t < lw.hi; ++t) {
-                std::memcpy(&pts[t], pin + 192 * ((size_t)k * lw.hi + t), 192);
-                exps[t] = t;
-            }
-            const zkhost::Xyzz res = zkhost::weighted_sum_pow2(pts, exps);
-            const size_t o = where[order[k]];
-            h_out_inf[o] = zkhost::xyzz_to_affine(res, h_out_xy + 12 * o) ? 0 : 1;
-        };
-        ZkHostPool* pool = ch.count > 1 ? c->pool() : nullptr;
-        if (!pool) {
-            for (uint32_t k = 0; k < ch.count; ++k) finish(k);
-        } else {
-            pool->run(ch.count, [&](unsigned k) { finish(k); });
-        }
+        ZK_TRY(msm_small_fetch(c, d_terms, terms_bytes));
+        // (every class has one problem of lw.hi planes: any of their geometries describes the chunk's terms)
+        msm_small_finish(c, classes[0].g, ch.count, h_out_xy, h_out_inf, [&](uint32_t k) { return (size_t)where[order[k]]; });
     }
     return ZKHIP_OK;
 }

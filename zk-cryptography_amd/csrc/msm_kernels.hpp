@@ -27,6 +27,7 @@
 #include "g1.hpp"
 #include "g1u.hpp"
 #include "msm_geometry.hpp"
+#include "msm_small_plan.hpp"
 
 namespace zk {
 
@@ -704,8 +705,8 @@ static __global__ __launch_bounds__(64) void msm_rowcol_terms_kernel(const uint3
 // quads of lanes (msm_wave_tree_sum: 7 passes of ~3 k instructions); the host epilogue is the weighted sum of <= 20 plane sums (one
 // doubling and one addition each).  Same group element, so the same affine commitment.  0.245 ms at 2^8, 0.47 ms at 2^12.
 // A BATCH of such commits (the rounds of a small MultilinearKZG::open against their level tables) takes the same two launches: the
-// slots are dealt to the problems in proportion to their pairs, a problem's planes are its own digit width.
-constexpr int MSM_SMALL_PROBS = 16;
+// slots are dealt to the problems in proportion to their pairs (msm_small_plan.hpp: MSM_SMALL_PROBS, the slot rule), a problem's planes
+// are its own digit width.
 struct MsmSmallArgs {
     const uint32_t* table;       // problem j: [tab_off[j] + w * stride[j] + i]: 2^(first bit of window w) * point i, affine, 28-bit limbs
     const uint64_t* scalars;     // problem j: n[j] of them from sc_off[j] on, Montgomery

@@ -84,7 +84,6 @@ def g2_prepare(g2_points):
     import torch
     n = len(g2_points)
     qxy, qinf = _g2_device(g2_points)
-    N.lib().zkhip_g2_prepared_bytes.restype = C.c_size_t
     prep = torch.empty(max(N.lib().zkhip_g2_prepared_bytes(C.c_size_t(n)), 1), dtype=torch.uint8, device=qxy.device)
     ctx = N.Context.get(qxy.device.index)
     st = N.lib().zkhip_g2_prepare(ctx.handle, N.ptr(qxy), N.ptr(qinf), C.c_size_t(n), N.ptr(prep))
@@ -352,7 +351,6 @@ class TrustedSetup:
                     raise IndexError("powers_of_tau_in_g2[1]: the G2 half has %d points" % g2.shape[0])
                 g2, inf = g2[1:2], inf[1:2]
             n = g2.shape[0]
-            N.lib().zkhip_g2_prepared_bytes.restype = C.c_size_t
             buf = torch.empty(N.lib().zkhip_g2_prepared_bytes(C.c_size_t(n + 1)), dtype=torch.uint8, device=g2.device)
             ctx = N.Context.get(g2.device.index)
             _check_points(N.lib().zkhip_kzg_prepare(ctx.handle, N.ptr(g2), N.ptr(inf), C.c_size_t(n), N.ptr(buf)), "kzg_prepare")
@@ -596,6 +594,18 @@ class MultilinearKZG:
         return _commit_begin(srs.powers_of_tau_in_g1, srs.inf, len(srs), poly.evaluations, len(poly), True, srs.table)
 
     @staticmethod
+    def _open_srs(srs, n, cache_folded_srs):
+        """what an opening of n entries commits against -> (folded xy, folded inf, level tables): pointers to the SRS's folded levels and
+        the tensor of their tables, or None where the call folds the SRS itself / runs without tables"""
+        if not (cache_folded_srs and len(srs) == n and n >= 4 and n & (n - 1) == 0):
+            return None, None, None
+        fxy, finf = srs.folded()
+        tables = getattr(srs, "_level_tables", None)       # present after srs.precompute_open(); folded() has just run the cache guard
+        if tables is None and n <= TrustedSetup.SMALL_SRS:  # a small SRS builds them on first use (a few ms): its openings take the
+            tables = srs.precompute_open()._level_tables    # short path, two launches for all rounds (zkhip_kzg_open_tables)
+        return N.ptr(fxy), N.ptr(finf), tables
+
+    @staticmethod
     def open(poly, evaluation_points, srs, cache_folded_srs=True):
         """MultilinearKZGInterface::open (multilinear_kzg.rs:50-88)"""
         assert isinstance(poly, Multilinear)
@@ -606,15 +616,7 @@ class MultilinearKZG:
         pinf = np.zeros(max(nv, 1), dtype=np.uint8)
         ctx = N.Context.get(poly.evaluations.device.index)
         n = len(poly)
-        tables = None
-        if cache_folded_srs and len(srs) == n and n >= 4 and n & (n - 1) == 0:
-            fxy, finf = srs.folded()
-            fxy_p, finf_p = N.ptr(fxy), N.ptr(finf)
-            tables = getattr(srs, "_level_tables", None)       # present after srs.precompute_open(); folded() has just run the cache guard
-            if tables is None and n <= TrustedSetup.SMALL_SRS:  # a small SRS builds them on first use (a few ms): its openings take the
-                tables = srs.precompute_open()._level_tables    # short path, two launches for all rounds (zkhip_kzg_open_tables)
-        else:
-            fxy_p = finf_p = None
+        fxy_p, finf_p, tables = MultilinearKZG._open_srs(srs, n, cache_folded_srs)
         st = N.lib().zkhip_kzg_open_tables(ctx.handle, N.ptr(poly.evaluations), C.c_size_t(n), pts.ctypes.data_as(C.c_void_p),
                                            C.c_size_t(nv), N.ptr(srs.powers_of_tau_in_g1), N.ptr(srs.inf), C.c_size_t(len(srs)),
                                            fxy_p, finf_p, N.ptr(tables) if tables is not None else None,
@@ -652,15 +654,7 @@ class MultilinearKZG:
         pxy = np.zeros((b * max(nv, 1), 12), dtype=np.uint64)
         pinf = np.zeros(b * max(nv, 1), dtype=np.uint8)
         ctx = N.Context.get(device.index)
-        tables = None
-        if cache_folded_srs and len(srs) == n and n >= 4 and n & (n - 1) == 0:      # as `open`
-            fxy, finf = srs.folded()
-            fxy_p, finf_p = N.ptr(fxy), N.ptr(finf)
-            tables = getattr(srs, "_level_tables", None)
-            if tables is None and n <= TrustedSetup.SMALL_SRS:
-                tables = srs.precompute_open()._level_tables
-        else:
-            fxy_p = finf_p = None
+        fxy_p, finf_p, tables = MultilinearKZG._open_srs(srs, n, cache_folded_srs)
         for p in polys:
             assert p.evaluations.is_contiguous()
         ptrs = (C.c_void_p * b)(*[p.evaluations.data_ptr() for p in polys])
